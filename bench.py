@@ -3,7 +3,7 @@
 Headline benchmark: fp64 SpMV (the reference's mult_vec, csr/kernels/numba/__init__.py:55-67)
 on a 10M x 10M power-law CSR with nnz = 2e8, through the libcsrk C ABI on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N = 1 runs in-process; for N > 1 the driver launches one rank per GPU
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) -- or, started plainly as
@@ -71,7 +71,32 @@ def parse():
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU baseline time budget')
     ap.add_argument('--secondary-seconds', type=float, default=240.0, help='N = 1: time limit of the secondary block (a child process)')
     ap.add_argument('--traffic-json', default=None, help='rocprofv3 PMC summary with per-launch HBM bytes')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (a fixed, seeded sample of y, float64, '
+                         'with its row indices) as DIR/<name>.npy, so that two builds can be compared output for output')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_SAMPLE = 1 << 21      # rows of y written by --dump-outputs: 2 x 16 MB (all of y when it is shorter)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, y):
+    "--dump-outputs: y of the last timed step at a fixed, seeded sample of rows -> y_sample.npy, y_sample_index.npy"
+    import numpy as np
+    import torch
+    n = int(y.numel())
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SAMPLE, replace=False))
+    vals = y[torch.from_numpy(idx).to(y.device)].to(torch.float64).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'y_sample.npy'), vals)
+    np.save(os.path.join(path, 'y_sample_index.npy'), idx.astype(np.float64))      # row numbers < 2^53: exact
 
 
 def load_traffic(path, workload, kernel):
@@ -384,6 +409,9 @@ def main():
             check(lib.csrk_free(hc))
         collective = 'allgather'
         op, op_handles = make_op(collective)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)          # every rank holds the complete y
 
     algo_name = lib.csrk_spmv_algo_name(hp).decode()
     n_tiles, tile_items = C.c_int64(0), C.c_int32(0)

@@ -1,35 +1,45 @@
 """
-INTEGRATION.md section 1, executed: the `hip` kernel module registers into the REFERENCE's own
-registry (csr/kernels/__init__.py:7) and the reference's CSR.mult_vec / CSR.multiply dispatch into
-libcsrk.  Runs only where the reference checkout exists (this container; never on the GPU box), in a
-subprocess with the stand-in numba package.  Without a GPU the call must reach libcsrk and fail loudly
-there (CsrkError from csrk_create), which proves the routing; with a GPU it must produce the product.
+INTEGRATION.md section 1, executed without the reference: the `hip` kernel module is registered as an out-of-tree
+module through the public registry dict (csr_amd.kernels mirrors csr/kernels/__init__.py:7-123), and a caller that
+knows nothing of csr_amd drives it the way the reference's CSR.mult_vec / CSR.multiply do (csr/csr.py:543-567,
+580-590): get_kernel(), to_handle on a plain object with only the fields of the reference's struct (csr/csr.py:79-100),
+the product, release_handle.  Runs in a subprocess.  Without a GPU the call must reach libcsrk and fail loudly there
+(CsrkError from csrk_create), which proves the routing; with a GPU it must produce the product.
 """
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 
 SCRIPT = r'''
-import sys, numpy as np
+import sys, types, numpy as np
 sys.dont_write_bytecode = True
-import csr, csr.kernels
-from csr import CSR
+import csr_amd.kernels as KS
 import csr_amd.kernels.hip as hip
 from csr_amd._lib import CsrkError
-csr.kernels.kernels['hip'] = hip
-A = CSR.from_coo(np.array([0, 0, 1, 3]), np.array([1, 2, 0, 1]), np.arange(4.0))
-with csr.kernels.use_kernel('hip'):
-    assert csr.kernels.get_kernel() is hip
+
+
+def foreign_csr(nrows, ncols, rowptrs, colinds, values):
+    "the reference's CSR as the kernel protocol sees it: nrows / ncols / nnz / rowptrs / colinds / values, nothing else"
+    return types.SimpleNamespace(nrows=nrows, ncols=ncols, nnz=len(colinds), rowptrs=np.asarray(rowptrs, np.int32),
+                                 colinds=np.asarray(colinds, np.int32), values=values)
+
+
+KS.kernels['hip_plugin'] = hip
+A = foreign_csr(4, 3, [0, 2, 3, 3, 4], [1, 2, 0, 1], np.arange(4.0))
+At = foreign_csr(3, 4, [0, 1, 3, 4], [1, 0, 3, 0], np.array([2.0, 0.0, 3.0, 1.0]))
+with KS.use_kernel('hip_plugin'):
+    K = KS.get_kernel()
+    assert K is hip
     try:
-        y = A.mult_vec(np.ones(3))
+        with KS.releasing(K.to_handle(A), K) as h:
+            y = K.mult_vec(h, np.ones(3))
         assert list(y) == [1.0, 2.0, 0.0, 3.0], y
-        P = A.multiply(A.transpose())
-        assert sorted(P.values.tolist()) == [1.0, 4.0, 9.0]
+        with KS.releasing(K.to_handle(A), K) as ha, KS.releasing(K.to_handle(At), K) as hb, \
+                KS.releasing(K.mult_ab(ha, hb), K) as hp:
+            P = K.from_handle(hp)
+        assert sorted(v for v in np.asarray(P.values).tolist() if v != 0.0) == [1.0, 4.0, 9.0]
         print('COMPUTED')
     except CsrkError as e:
         assert 'hip' in str(e).lower()
@@ -37,10 +47,8 @@ with csr.kernels.use_kernel('hip'):
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'csr')), reason='reference checkout not present')
-def test_hip_kernel_registers_into_reference_registry():
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1',
-               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'oracle', 'gen', 'numba_stub'), REF, ROOT]))
-    r = subprocess.run([sys.executable, '-c', SCRIPT], env=env, capture_output=True, text=True, cwd='/tmp')
+def test_hip_kernel_registers_through_the_plugin_registry(tmp_path):
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1', PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, '-c', SCRIPT], env=env, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout.strip().splitlines()[-1] in ('ROUTED', 'COMPUTED')

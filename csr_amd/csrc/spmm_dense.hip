@@ -387,7 +387,8 @@ __global__ __launch_bounds__(HR_THREADS) void spmm_hrows_kernel(const int64_t *_
         nn = (int32_t)(bp[bk + bstep + 1] - e0n);
     }
     // (thread's offset inside a tile of B: row tid / 32, column pair tid % 32; fits 32 bits when a tile's rows do)
-    const bool can_whole = kc == HR_KC && (int64_t)HR_TILE * ldb * 8 < (1ll << 31);
+    // (EVEN also says B and ldb keep the 16-B pieces aligned: spmm_device)
+    const bool can_whole = EVEN && kc == HR_KC && (int64_t)HR_TILE * ldb * 8 < (1ll << 31);
     const uint32_t voff = (uint32_t)(((int64_t)(tid >> 5) * ldb + (tid & 31) * 2) * 8);
     {
         const bool whole = can_whole && (int64_t)(t0 + 1) * HR_TILE <= ncols;
@@ -811,7 +812,12 @@ static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, doub
         CSRK_TRY(p->part.alloc((size_t)p->n_multi * k * 8));
         p->part_k = k;
     }
-    const bool full4 = (k % 4) == 0;
+    // The 16-B loads and stores (FULL4, EVEN) need 16-B aligned B / C rows: a column block of a wider panel that starts
+    // at an odd column, or an odd ldb / ldc, takes the 8-B forms instead (same products, same order of the sums: the
+    // bits do not depend on the form)
+    const bool b_al = ((uintptr_t)dB & 15) == 0 && (ldb & 1) == 0;
+    const bool c_al = ((uintptr_t)dC & 15) == 0 && (ldc & 1) == 0;
+    const bool full4 = (k % 4) == 0 && b_al && c_al;
     if (p->hr_on) {
         const unsigned wgs = (unsigned)(p->hr_G * p->hr_R);
         const unsigned rgrid = (unsigned)ceil_div((int64_t)p->hr_n * WAVE, 256);
@@ -821,7 +827,7 @@ static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, doub
     spmm_hrows_kernel<EVEN><<<wgs, HR_THREADS, HR_LDS, s>>>(p->hr_bp.as<int64_t>(), p->hr_idx.as<uint32_t>(),             \
                                                            p->hr_vals.as<double>(), dB + c0, kc, ldb, m->ncols,          \
                                                            p->hr_range.as<int32_t>(), p->hr_G, p->hr_part.as<double>())
-            if (kc % 2 == 0) HROWS(true);
+            if (kc % 2 == 0 && b_al) HROWS(true);
             else HROWS(false);
 #undef HROWS
             CSRK_LAUNCH_CHECK();

@@ -215,7 +215,12 @@ CSRK_API int csrk_spgemm_last_route(int *route);
 
 /* ---- dense-panel SpMM: C = A B, B dense row-major [ncols x k] --------------------------
  * Not a reference entry point (the reference's mult_ab is sparse x sparse only); serves
- * BASELINE.json configs[2].  Equals mult_ab(A, CSR(B)) densified.  ldb/ldc in elements. */
+ * BASELINE.json configs[2].  Equals mult_ab(A, CSR(B)) densified.  ldb/ldc in elements.
+ * Column blocks of a wider panel: d_B may point at column c0 of a panel with ldb > k, and d_C into a wider output
+ * (ldc > k); every column of C is computed as it is in a full-width call on the same handle, bit for bit.  B and C need
+ * only 8-B alignment: when d_B or d_C is not 16-B aligned, or ldb or ldc is odd, the kernels take their 8-B loads and
+ * stores for that call.  The plan is built by a handle's first call and serves every k after it (the first call's
+ * k * ncols decides whether the longest rows take the register-accumulator form). */
 CSRK_API int csrk_spmm_dense(csrk_handle_t a, const double *B, int32_t k, int64_t ldb,
                              double *C, int64_t ldc);
 CSRK_API int csrk_spmm_dense_device(csrk_handle_t a, const double *d_B, int32_t k, int64_t ldb,

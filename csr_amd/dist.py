@@ -20,8 +20,7 @@ step of the path:
              every sum has one non-zero term and is exact), about twice the bytes per link.
 
 SplitPhaseRowPartitionedSpMV: point-to-point sends of the slices straight into y, hidden behind the tiers' part of one
-product (csrk_spmv_device_part).  (Rounds 2-3 also carried chunk-pipelined, plain point-to-point and IPC-push forms; none
-has ever run with two RCCL ranks, so they were removed: `git log -- csr_amd/dist.py`.)
+product (csrk_spmv_device_part).
 
 torch is plumbing here (device buffers + the collective); the product kernels run behind
 `local_spmv`, a callable that writes y[r0:r1] = A[r0:r1, :] x into the buffer it is given.
@@ -38,83 +37,129 @@ block width.  Only one RCCL rank (and two gloo ranks sharing one GPU, in the tes
 exchange -- the 1 GB C of configs[2], 7/8 of it arriving at every rank -- is a cost model, not a
 measurement.
 """
-import contextlib
+import ctypes as C
 
 import torch
 import torch.distributed as dist
 
+from ._lib import lib, check
 
-class RowPartitionedSpMV:
+_MODES = ('allgather', 'allgatherv', 'allreduce')
+
+
+class _RowPartition:
+    """
+    What the three operators share: rank `rank` of `world` owns rows r0:r1 = bounds[rank]:bounds[rank + 1] of
+    nrows = bounds[-1], and the device timing of its local products.  timing = True brackets every launch of a local
+    product with an event pair (CUDA outputs only); compute_ms() is their mean device time per step.
+    """
+
+    def __init__(self, bounds, rank, world, group, launches_per_step):
+        assert len(bounds) == world + 1
+        self.bounds = [int(b) for b in bounds]
+        self.rank, self.world, self.group = rank, world, group
+        self.nrows = self.bounds[-1]
+        self.r0, self.r1 = self.bounds[rank], self.bounds[rank + 1]
+        self.lens = [self.bounds[g + 1] - self.bounds[g] for g in range(world)]
+        self.timing = False
+        self._per_step, self._ev = launches_per_step, []
+
+    def _launch(self, local, x, out, *args):
+        "local(x, out, *args), timed when `timing` is set"
+        if not (self.timing and out.is_cuda):
+            return local(x, out, *args)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        local(x, out, *args)
+        e1.record()
+        self._ev.append((e0, e1))
+
+    def compute_ms(self):
+        "mean device time per step of the local products over the steps timed so far (call after a synchronize)"
+        ev, self._ev = self._ev, []
+        if not ev:
+            return 0.0
+        return sum(a.elapsed_time(b) for a, b in ev) * self._per_step / len(ev)
+
+
+class _Exchange:
+    """
+    One exchange that completes `dst` -- a full-height [nrows] or [nrows x w] float64 tensor, possibly a strided column
+    block -- on every rank of `part` (a _RowPartition).  The local product writes this rank's rows into `out`
+    (contiguous); prepare() goes before that product, finish() after it: the one collective, then the rows into dst.
+    """
+
+    def __init__(self, part, mode, dst):
+        self.part, self.mode, self.dst = part, mode, dst
+        bounds, lens = part.bounds, part.lens
+        whole = dst.is_contiguous()
+        if mode == 'allgather':
+            # this rank's rows padded to the longest rank's: ONE all_gather_into_tensor, then the unpadded pieces go
+            # into dst by one concatenation (or, into a column block, one strided copy each)
+            m = max(lens)
+            self.loc = dst.new_zeros((m,) + dst.shape[1:])
+            self.gath = dst.new_zeros((part.world * m,) + dst.shape[1:])
+            self.out = self.loc[:part.r1 - part.r0]
+            pieces = [(dst[bounds[g]:bounds[g + 1]], self.gath[g * m:g * m + lens[g]])
+                      for g in range(part.world) if lens[g]]
+            self.cat = [p for _, p in pieces] if whole else []
+            self.copies = [] if whole else pieces
+        else:
+            # every rank's rows of a full-height buffer (dst itself when it is contiguous), as the output list of ONE
+            # all_gather (RCCL: a group of broadcasts when the lengths differ; gloo only takes equal ones), or summed
+            # by ONE all_reduce after the other ranks' rows were zeroed
+            self.full = dst if whole else dst.new_zeros(dst.shape)
+            self.views = [self.full[bounds[g]:bounds[g + 1]] for g in range(part.world)]
+            self.out = self.views[part.rank]
+
+    def prepare(self):
+        "allreduce: zero what the previous step left in the other ranks' rows"
+        if self.mode == 'allreduce':
+            p = self.part
+            if p.r0 > 0:
+                self.full[:p.r0].zero_()
+            if p.r1 < p.nrows:
+                self.full[p.r1:].zero_()
+
+    def finish(self):
+        group = self.part.group
+        if self.mode == 'allgather':
+            dist.all_gather_into_tensor(self.gath, self.loc, group=group)
+            if self.cat:
+                torch.cat(self.cat, out=self.dst)
+            for d, p in self.copies:
+                d.copy_(p)
+            return
+        if self.mode == 'allgatherv':
+            dist.all_gather(self.views, self.out, group=group)
+        else:
+            dist.all_reduce(self.full, op=dist.ReduceOp.SUM, group=group)
+        if self.full is not self.dst:
+            self.dst.copy_(self.full)
+
+
+class RowPartitionedSpMV(_RowPartition):
     def __init__(self, bounds, rank, world, local_spmv, device, mode='allgather', group=None):
         """
         bounds: world+1 row indices (rank g owns rows bounds[g]:bounds[g+1]).
         local_spmv(x, out): computes this rank's rows into `out` (a float64 tensor of
         bounds[rank+1]-bounds[rank] entries on `device`); asynchronous on the current stream.
         """
-        assert len(bounds) == world + 1 and mode in ('allgather', 'allgatherv', 'allreduce')
-        self.bounds = [int(b) for b in bounds]
-        self.rank, self.world, self.mode, self.group = rank, world, mode, group
+        assert mode in _MODES
+        super().__init__(bounds, rank, world, group, 1)
+        self.mode = mode
         self.local_spmv = local_spmv
-        self.nrows = self.bounds[-1]
-        self.r0, self.r1 = self.bounds[rank], self.bounds[rank + 1]
-        self.lens = [self.bounds[g + 1] - self.bounds[g] for g in range(world)]
         self.y = torch.zeros(self.nrows, dtype=torch.float64, device=device)
-        self.timing = False            # set True to record device events around the local product
-        self._ev = []
-        if world > 1 and mode == 'allgather':
-            self.maxlen = max(self.lens)
-            self.loc = torch.zeros(self.maxlen, dtype=torch.float64, device=device)
-            self.gath = torch.zeros(world * self.maxlen, dtype=torch.float64, device=device)
-            # the slices of `gath` that make up y, in rank order: unpadded by ONE concatenation kernel
-            self.pieces = [self.gath[g * self.maxlen:g * self.maxlen + self.lens[g]] for g in range(world)
-                           if self.lens[g]]
-
-        if world > 1 and mode == 'allgatherv':
-            # every rank's slice of y itself, as the output list of ONE all_gather: with slices of different lengths
-            # RCCL runs it as a group of broadcasts straight into place (nothing padded, nothing concatenated);
-            # gloo only takes equal lengths
-            self.views = [self.y[self.bounds[g]:self.bounds[g + 1]] for g in range(world)]
-
-    def _local(self, x, out):
-        if self.timing and out.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self.local_spmv(x, out)
-            e1.record()
-            self._ev.append((e0, e1))
-        else:
-            self.local_spmv(x, out)
-
-    def compute_ms(self):
-        "mean device time of the local product over the steps timed so far (call after a synchronize)"
-        if not self._ev:
-            return 0.0
-        ms = sum(a.elapsed_time(b) for a, b in self._ev) / len(self._ev)
-        self._ev = []
-        return ms
+        self._ex = _Exchange(self, mode, self.y) if world > 1 else None
 
     def step(self, x):
         "y = A x, complete on every rank; returns the (reused) y tensor"
         if self.world == 1:
-            self._local(x, self.y)
+            self._launch(self.local_spmv, x, self.y)
             return self.y
-        if self.mode == 'allgather':
-            self._local(x, self.loc[:self.r1 - self.r0])
-            dist.all_gather_into_tensor(self.gath, self.loc, group=self.group)
-            if self.pieces:
-                torch.cat(self.pieces, out=self.y)
-            return self.y
-        if self.mode == 'allgatherv':
-            self._local(x, self.views[self.rank])
-            dist.all_gather(self.views, self.views[self.rank], group=self.group)
-            return self.y
-        # allreduce: zero what the previous step left in the other ranks' slices
-        if self.r0 > 0:
-            self.y[:self.r0].zero_()
-        if self.r1 < self.nrows:
-            self.y[self.r1:].zero_()
-        self._local(x, self.y[self.r0:self.r1])
-        dist.all_reduce(self.y, op=dist.ReduceOp.SUM, group=self.group)
+        self._ex.prepare()
+        self._launch(self.local_spmv, x, self._ex.out)
+        self._ex.finish()
         return self.y
 
 
@@ -127,7 +172,7 @@ def _sync_if_host_backend(t, group):
         torch.cuda.synchronize(t.device)
 
 
-class SplitPhaseRowPartitionedSpMV:
+class SplitPhaseRowPartitionedSpMV(_RowPartition):
     """
     The exchange hidden behind the part of the product that touches few rows.  A rank's SpMV has two parts
     (csrk_spmv_device_part): part 1 computes every row of the row-major path and writes 0.0 into the rows the plan
@@ -143,22 +188,16 @@ class SplitPhaseRowPartitionedSpMV:
     """
 
     def __init__(self, bounds, rank, world, local_part, cut_rows, device, group=None):
-        assert len(bounds) == world + 1
-        self.bounds = [int(b) for b in bounds]
-        self.rank, self.world, self.group = rank, world, group
+        super().__init__(bounds, rank, world, group, 2)
         self.local_part = local_part
-        self.nrows = self.bounds[-1]
-        self.r0, self.r1 = self.bounds[rank], self.bounds[rank + 1]
         self.y = torch.zeros(self.nrows, dtype=torch.float64, device=device)
-        self.timing = False
-        self._ev = []
         self.ops = []
         mine = self.y[self.r0:self.r1]
         for d in range(1, world):
             to, frm = (rank + d) % world, (rank - d) % world
             if self.r1 > self.r0:
                 self.ops.append(dist.P2POp(dist.isend, mine, to, group))
-            if self.bounds[frm + 1] > self.bounds[frm]:
+            if self.lens[frm]:
                 self.ops.append(dist.P2POp(dist.irecv, self.y[self.bounds[frm]:self.bounds[frm + 1]], frm, group))
         # the cut rows of every rank, as global row indices: exchanged once
         cut = cut_rows.to(device=device, dtype=torch.int64) + self.r0
@@ -183,32 +222,15 @@ class SplitPhaseRowPartitionedSpMV:
             self.dst_rows = rows_all.index_select(0, self.src_pos)
             self.tmp = torch.zeros(int(self.src_pos.numel()), dtype=torch.float64, device=device)
 
-    def compute_ms(self):
-        "mean device time per step of the two local parts over the steps timed so far"
-        if not self._ev:
-            return 0.0
-        ms = sum(a.elapsed_time(b) for a, b in self._ev) * 2 / len(self._ev)
-        self._ev = []
-        return ms
-
-    def _part(self, x, out, part):
-        if self.timing and out.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self.local_part(x, out, part)
-            e1.record()
-            self._ev.append((e0, e1))
-        else:
-            self.local_part(x, out, part)
-
     def step(self, x):
         "y = A x, complete on every rank; returns the (reused) y tensor"
         mine = self.y[self.r0:self.r1]
-        self._part(x, mine, 1)
-        if self.world > 1 and self.ops:
+        self._launch(self.local_part, x, mine, 1)
+        works = []
+        if self.ops:                    # (none with one rank)
             _sync_if_host_backend(self.y, self.group)
-        works = dist.batch_isend_irecv(self.ops) if (self.world > 1 and self.ops) else []
-        self._part(x, mine, 2)
+            works = dist.batch_isend_irecv(self.ops)
+        self._launch(self.local_part, x, mine, 2)
         if self.world > 1 and self.total_cut:
             if self.n_mine:
                 torch.index_select(self.y, 0, self.my_rows, out=self.hv_loc[:self.n_mine])
@@ -222,42 +244,7 @@ class SplitPhaseRowPartitionedSpMV:
         return self.y
 
 
-def hip_local_spmv_parts(handle, device):
-    """
-    (local_part, cut_rows) over a libcsrk handle for SplitPhaseRowPartitionedSpMV: csrk_spmv_device_part on torch's
-    current stream, and the plan's cut rows (csrk_spmv_cut_rows: builds the plan) as an int64 tensor on `device`.
-    """
-    import ctypes as C
-    from ._lib import lib, check
-
-    def run(x, out, part):
-        assert x.dtype == torch.float64 and out.dtype == torch.float64 and out.is_contiguous()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        check(lib.csrk_spmv_device_part(handle, x.data_ptr(), out.data_ptr(), stream, int(part)))
-
-    n = C.c_int64(0)
-    check(lib.csrk_spmv_cut_rows(handle, None, 0, C.byref(n)))
-    rows = torch.zeros(max(n.value, 1), dtype=torch.int32, device=device)
-    if n.value:
-        check(lib.csrk_spmv_cut_rows(handle, rows.data_ptr(), n.value, C.byref(n)))
-    return run, rows[:n.value].to(torch.int64)
-
-
-def hip_local_spmv(handle):
-    """
-    local_spmv callable over a libcsrk handle (csrk_spmv_device on torch's current stream).
-    `handle` is the raw csrk_handle_t (int) of this rank's row range.
-    """
-    from ._lib import lib, check
-
-    def run(x, out):
-        assert x.dtype == torch.float64 and out.dtype == torch.float64 and out.is_contiguous()
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        check(lib.csrk_spmv_device(handle, x.data_ptr(), out.data_ptr(), stream))
-    return run
-
-
-class RowPartitionedSpMM:
+class RowPartitionedSpMM(_RowPartition):
     """
     C = A B, B dense row-major [ncols x k] float64, row-partitioned like RowPartitionedSpMV; C [nrows x k] is complete
     and identical on every rank after step().
@@ -265,61 +252,28 @@ class RowPartitionedSpMM:
     local_spmm(B, out, c0, c1): writes A[r0:r1, :] @ B[:, c0:c1] into `out`, a float64 [r1 - r0 x (c1 - c0)] view on
     `device` whose row stride may exceed its width; asynchronous on the current stream.
 
-    Modes, as in RowPartitionedSpMV:
-      allgather  (default) the local slab is padded to the longest rank's rows, one all_gather_into_tensor moves the
-                 padded slabs, and they are unpadded into C.
-      allgatherv every rank's row slab (of C, or of the block's buffer) is an entry of the output list of one
-                 all_gather: nothing padded.  gloo only takes equal slabs; RCCL also takes unequal ones.
-      allreduce  the other ranks' rows are zeroed and the ranks sum: exact, the slabs being disjoint.
-    col_block=kb: ceil(k / kb) column blocks, each exchanged on a second stream while the next block's product runs on
-    the caller's; None: one block.  The exchange runs whenever a process group is initialised (also with one rank, so
-    that a one-rank job rehearses it); without one, the product writes straight into C.
+    The modes are RowPartitionedSpMV's, on row slabs of C (allgatherv: gloo only takes equal slabs; RCCL also takes
+    unequal ones).  col_block=kb: ceil(k / kb) column blocks, each exchanged on a second stream while the next block's
+    product runs on the caller's; None: one block.  Every block has buffers of its own, so block j + 1's product never
+    writes what block j's collective still reads.  The exchange runs whenever a process group is initialised (also with
+    one rank, so that a one-rank job rehearses it); without one, the product writes straight into C.
     """
 
     def __init__(self, bounds, rank, world, local_spmm, device, k, mode='allgather', col_block=None, group=None):
-        assert len(bounds) == world + 1 and mode in ('allgather', 'allgatherv', 'allreduce')
-        assert int(k) >= 0 and (col_block is None or int(col_block) >= 1)
-        self.bounds = [int(b) for b in bounds]
-        self.rank, self.world, self.mode, self.group = rank, world, mode, group
-        self.local_spmm = local_spmm
+        assert mode in _MODES and int(k) >= 0 and (col_block is None or int(col_block) >= 1)
         self.k = k = int(k)
-        self.nrows = self.bounds[-1]
-        self.r0, self.r1 = self.bounds[rank], self.bounds[rank + 1]
-        self.lens = [self.bounds[g + 1] - self.bounds[g] for g in range(world)]
-        self.device = torch.device(device)
         kb = k if col_block is None else min(int(col_block), max(k, 1))
         self.col_block = col_block
         self.blocks = [(c0, min(c0 + kb, k)) for c0 in range(0, k, max(kb, 1))]
+        super().__init__(bounds, rank, world, group, len(self.blocks))
+        self.mode = mode
+        self.local_spmm = local_spmm
+        self.device = torch.device(device)
         self.exchange = world > 1 or (dist.is_available() and dist.is_initialized())
         self.C = torch.zeros(self.nrows, k, dtype=torch.float64, device=self.device)
-        self.timing = False            # set True to record device events around the local products
-        self._ev = []
-        self._steps = 0
         self.comm = torch.cuda.Stream(self.device) if self.device.type == 'cuda' else None
-        one = len(self.blocks) == 1
-        # per block: (the product's output, what the collective needs); every block has buffers of its own, so block
-        # j + 1's product never writes what block j's collective still reads
-        self.bufs = []
-        if not self.exchange:
-            return
-        if mode == 'allgather':
-            self.maxlen = m = max(self.lens)
-            loc = torch.zeros(m * k, dtype=torch.float64, device=self.device)
-            gath = torch.zeros(world * m * k, dtype=torch.float64, device=self.device)
-            for c0, c1 in self.blocks:
-                w = c1 - c0
-                lj = loc[m * c0:m * c1].view(m, w)
-                gj = gath[world * m * c0:world * m * c1].view(world * m, w)
-                pieces = [(self.bounds[g], self.bounds[g + 1], gj[g * m:g * m + self.lens[g]])
-                          for g in range(world) if self.lens[g]]
-                self.bufs.append((lj[:self.r1 - self.r0], (lj, gj, pieces)))
-        else:
-            # allgatherv / allreduce: a full-height buffer per block (C itself when there is one block)
-            flat = None if one else torch.zeros(self.nrows * k, dtype=torch.float64, device=self.device)
-            for c0, c1 in self.blocks:
-                yj = self.C if one else flat[self.nrows * c0:self.nrows * c1].view(self.nrows, c1 - c0)
-                views = [yj[self.bounds[g]:self.bounds[g + 1]] for g in range(world)]
-                self.bufs.append((views[rank], (yj, views)))
+        self._ex = [_Exchange(self, mode, self.C if len(self.blocks) == 1 else self.C[:, c0:c1])
+                    for c0, c1 in self.blocks] if self.exchange else []
 
     def recv_bytes(self):
         """
@@ -329,81 +283,64 @@ class RowPartitionedSpMM:
         if not self.exchange or self.world == 1:
             return 0
         if self.mode == 'allgather':
-            return (self.world - 1) * self.maxlen * self.k * 8
+            return (self.world - 1) * max(self.lens) * self.k * 8
         if self.mode == 'allgatherv':
             return (self.nrows - (self.r1 - self.r0)) * self.k * 8
         return int(2 * (self.world - 1) * self.nrows * self.k * 8 // self.world)
 
-    def _local(self, B, out, c0, c1):
-        if self.timing and out.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self.local_spmm(B, out, c0, c1)
-            e1.record()
-            self._ev.append((e0, e1))
-        else:
-            self.local_spmm(B, out, c0, c1)
-
-    def compute_ms(self):
-        "mean device time per step of the local products (all blocks) over the steps timed so far (after a synchronize)"
-        if not self._ev or not self._steps:
-            self._ev, self._steps = [], 0
-            return 0.0
-        ms = sum(a.elapsed_time(b) for a, b in self._ev) / self._steps
-        self._ev, self._steps = [], 0
-        return ms
-
-    def _exchange(self, j, out, aux):
-        c0, c1 = self.blocks[j]
-        whole = len(self.blocks) == 1
-        if self.mode == 'allgather':
-            lj, gj, pieces = aux
-            dist.all_gather_into_tensor(gj, lj, group=self.group)
-            if whole and pieces:
-                torch.cat([p for _, _, p in pieces], out=self.C)
-            else:
-                for a, b, p in pieces:
-                    self.C[a:b, c0:c1].copy_(p)
-            return
-        yj, views = aux
-        if self.mode == 'allgatherv':
-            dist.all_gather(views, views[self.rank], group=self.group)
-        else:
-            dist.all_reduce(yj, op=dist.ReduceOp.SUM, group=self.group)
-        if not whole:
-            self.C[:, c0:c1].copy_(yj)
-
     def step(self, B):
         "C = A B, complete on every rank; returns the (reused) C tensor"
-        if self.timing:
-            self._steps += 1
         if not self.exchange:
             for c0, c1 in self.blocks:
-                self._local(B, self.C[self.r0:self.r1, c0:c1], c0, c1)
+                self._launch(self.local_spmm, B, self.C[self.r0:self.r1, c0:c1], c0, c1)
             return self.C
         cur = torch.cuda.current_stream(self.device) if self.comm is not None else None
-        for j, (out, aux) in enumerate(self.bufs):
-            c0, c1 = self.blocks[j]
-            if self.mode == 'allreduce':
-                # zero what the previous step left in the other ranks' rows
-                yj = aux[0]
-                if self.r0 > 0:
-                    yj[:self.r0].zero_()
-                if self.r1 < self.nrows:
-                    yj[self.r1:].zero_()
-            self._local(B, out, c0, c1)
-            _sync_if_host_backend(out, self.group)
+        for (c0, c1), ex in zip(self.blocks, self._ex):
+            ex.prepare()
+            self._launch(self.local_spmm, B, ex.out, c0, c1)
+            _sync_if_host_backend(ex.out, self.group)
             if cur is None:
-                self._exchange(j, out, aux)
+                ex.finish()
                 continue
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            self.comm.wait_event(ready)
+            self.comm.wait_stream(cur)
             with torch.cuda.stream(self.comm):
-                self._exchange(j, out, aux)
+                ex.finish()
         if cur is not None:
             cur.wait_stream(self.comm)
         return self.C
+
+
+def _stream(t):
+    "torch's current stream on t's device, as the hipStream_t libcsrk takes"
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def hip_local_spmv(handle):
+    """
+    local_spmv callable over a libcsrk handle (csrk_spmv_device on torch's current stream).
+    `handle` is the raw csrk_handle_t (int) of this rank's row range.
+    """
+    def run(x, out):
+        assert x.dtype == torch.float64 and out.dtype == torch.float64 and out.is_contiguous()
+        check(lib.csrk_spmv_device(handle, x.data_ptr(), out.data_ptr(), _stream(out)))
+    return run
+
+
+def hip_local_spmv_parts(handle, device):
+    """
+    (local_part, cut_rows) over a libcsrk handle for SplitPhaseRowPartitionedSpMV: csrk_spmv_device_part on torch's
+    current stream, and the plan's cut rows (csrk_spmv_cut_rows: builds the plan) as an int64 tensor on `device`.
+    """
+    def run(x, out, part):
+        assert x.dtype == torch.float64 and out.dtype == torch.float64 and out.is_contiguous()
+        check(lib.csrk_spmv_device_part(handle, x.data_ptr(), out.data_ptr(), _stream(out), int(part)))
+
+    n = C.c_int64(0)
+    check(lib.csrk_spmv_cut_rows(handle, None, 0, C.byref(n)))
+    rows = torch.zeros(max(n.value, 1), dtype=torch.int32, device=device)
+    if n.value:
+        check(lib.csrk_spmv_cut_rows(handle, rows.data_ptr(), n.value, C.byref(n)))
+    return run, rows[:n.value].to(torch.int64)
 
 
 def hip_local_spmm(handle):
@@ -414,8 +351,6 @@ def hip_local_spmm(handle):
     loads and stores (csrk.h), with the same bits.
     `handle` is the raw csrk_handle_t (int) of this rank's row range.
     """
-    import ctypes as C
-    from ._lib import lib, check
     nr, nc, nnz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     p64, vt = C.c_int(0), C.c_int(0)
     check(lib.csrk_info(handle, C.byref(nr), C.byref(nc), C.byref(nnz), C.byref(p64), C.byref(vt)))
@@ -433,6 +368,5 @@ def hip_local_spmm(handle):
         ldb = B.stride(0) if ncols > 1 else max(B.stride(0), B.shape[1])
         ldc = out.stride(0) if nrows > 1 else max(out.stride(0), w)
         assert ldb >= B.shape[1] and ldc >= w
-        stream = torch.cuda.current_stream(out.device).cuda_stream
-        check(lib.csrk_spmm_dense_device(handle, B.data_ptr() + c0 * 8, w, ldb, out.data_ptr(), ldc, stream))
+        check(lib.csrk_spmm_dense_device(handle, B.data_ptr() + c0 * 8, w, ldb, out.data_ptr(), ldc, _stream(out)))
     return run

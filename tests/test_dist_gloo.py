@@ -6,52 +6,33 @@ checks exactly what a multi-GPU run adds: the split points, the padded all-gathe
 all-reduce, and the reassembly.
 """
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from gloo_harness import spawn
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _worker(rank, world, mode, out_dir):
+    from csr_amd import synth
+    from csr_amd.dist import RowPartitionedSpMV
+    from oracle import oracle as O
+    nrows, ncols, nnz = 6000, 5000, 90000
+    shard = synth.powerlaw_csr(nrows, ncols, nnz, device='cpu', rank=rank, world=world)
+    x = synth.dense_vector(ncols, device='cpu')
+    rp, ci, vs = (shard[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
+    n_loc = shard['row_end'] - shard['row_begin']
 
+    def local_spmv(xt, out):
+        out.copy_(torch.from_numpy(O.mult_vec(n_loc, ncols, rp, ci, vs, xt.numpy())))
 
-def _worker(rank, world, port, mode, out_dir):
-    sys.path.insert(0, ROOT)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
-    try:
-        from csr_amd import synth
-        from csr_amd.dist import RowPartitionedSpMV
-        from oracle import oracle as O
-        nrows, ncols, nnz = 6000, 5000, 90000
-        shard = synth.powerlaw_csr(nrows, ncols, nnz, device='cpu', rank=rank, world=world)
-        x = synth.dense_vector(ncols, device='cpu')
-        rp, ci, vs = (shard[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
-        n_loc = shard['row_end'] - shard['row_begin']
-
-        def local_spmv(xt, out):
-            out.copy_(torch.from_numpy(O.mult_vec(n_loc, ncols, rp, ci, vs, xt.numpy())))
-
-        op = RowPartitionedSpMV(shard['bounds'], rank, world, local_spmv, 'cpu', mode=mode)
-        y1 = op.step(x).clone()
-        y2 = op.step(x).clone()          # buffers are reused: a second step must agree
-        assert torch.equal(y1, y2)
-        np.save(os.path.join(out_dir, f'y_{mode}_{rank}.npy'), y1.numpy())
-        np.save(os.path.join(out_dir, f'bounds_{rank}.npy'), np.array(shard['bounds']))
-    finally:
-        dist.destroy_process_group()
+    op = RowPartitionedSpMV(shard['bounds'], rank, world, local_spmv, 'cpu', mode=mode)
+    y1 = op.step(x).clone()
+    y2 = op.step(x).clone()          # buffers are reused: a second step must agree
+    assert torch.equal(y1, y2)
+    np.save(os.path.join(out_dir, f'y_{mode}_{rank}.npy'), y1.numpy())
+    np.save(os.path.join(out_dir, f'bounds_{rank}.npy'), np.array(shard['bounds']))
 
 
 @pytest.mark.parametrize('world', [2, 3])
@@ -59,7 +40,7 @@ def _worker(rank, world, port, mode, out_dir):
 def test_row_partitioned_spmv_gloo(tmp_path, world, mode):
     from csr_amd import synth
     from oracle import oracle as O
-    mp.spawn(_worker, args=(world, _free_port(), mode, str(tmp_path)), nprocs=world, join=True)
+    spawn(_worker, world, mode, str(tmp_path))
     full = synth.powerlaw_csr(6000, 5000, 90000, device='cpu')
     x = synth.dense_vector(5000, device='cpu').numpy()
     ref = O.mult_vec(6000, 5000, full['rowptrs'].numpy(), full['colinds'].numpy(), full['values'].numpy(), x)
@@ -75,41 +56,34 @@ def test_row_partitioned_spmv_gloo(tmp_path, world, mode):
     assert max(per) - min(per) <= int(np.max(np.diff(rp))) + 1
 
 
-def _worker_split(rank, world, port, out_dir):
-    sys.path.insert(0, ROOT)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
-    try:
-        from csr_amd import synth
-        from csr_amd.dist import SplitPhaseRowPartitionedSpMV
-        from oracle import oracle as O
-        nrows, ncols, nnz = 6000, 5000, 90000
-        shard = synth.powerlaw_csr(nrows, ncols, nnz, device='cpu', rank=rank, world=world)
-        x = synth.dense_vector(ncols, device='cpu')
-        rp, ci, vs = (shard[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
-        n_loc = shard['row_end'] - shard['row_begin']
-        lens = np.diff(rp)
-        # the stand-in for the plan's tiers: rows of 40 entries and more (rank 1 of 3 keeps none: an empty list must work)
-        cut = np.flatnonzero(lens >= 40) if not (world == 3 and rank == 1) else np.zeros(0, dtype=np.int64)
-        is_cut = np.zeros(n_loc, dtype=bool)
-        is_cut[cut] = True
+def _worker_split(rank, world, out_dir):
+    from csr_amd import synth
+    from csr_amd.dist import SplitPhaseRowPartitionedSpMV
+    from oracle import oracle as O
+    nrows, ncols, nnz = 6000, 5000, 90000
+    shard = synth.powerlaw_csr(nrows, ncols, nnz, device='cpu', rank=rank, world=world)
+    x = synth.dense_vector(ncols, device='cpu')
+    rp, ci, vs = (shard[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
+    n_loc = shard['row_end'] - shard['row_begin']
+    lens = np.diff(rp)
+    # the stand-in for the plan's tiers: rows of 40 entries and more (rank 1 of 3 keeps none: an empty list must work)
+    cut = np.flatnonzero(lens >= 40) if not (world == 3 and rank == 1) else np.zeros(0, dtype=np.int64)
+    is_cut = np.zeros(n_loc, dtype=bool)
+    is_cut[cut] = True
 
-        def local_part(xt, out, part):
-            full = O.mult_vec(n_loc, ncols, rp, ci, vs, xt.numpy())
-            o = out.numpy()
-            if part == 1:
-                o[:] = np.where(is_cut, 0.0, full)          # the cut rows get 0.0
-            else:
-                o[is_cut] = full[is_cut]                    # ... and are overwritten by part 2
+    def local_part(xt, out, part):
+        full = O.mult_vec(n_loc, ncols, rp, ci, vs, xt.numpy())
+        o = out.numpy()
+        if part == 1:
+            o[:] = np.where(is_cut, 0.0, full)          # the cut rows get 0.0
+        else:
+            o[is_cut] = full[is_cut]                    # ... and are overwritten by part 2
 
-        op = SplitPhaseRowPartitionedSpMV(shard['bounds'], rank, world, local_part, torch.from_numpy(cut.astype(np.int64)), 'cpu')
-        y1 = op.step(x).clone()
-        y2 = op.step(x).clone()
-        assert torch.equal(y1, y2)
-        np.save(os.path.join(out_dir, f'ys_{rank}.npy'), y1.numpy())
-    finally:
-        dist.destroy_process_group()
+    op = SplitPhaseRowPartitionedSpMV(shard['bounds'], rank, world, local_part, torch.from_numpy(cut.astype(np.int64)), 'cpu')
+    y1 = op.step(x).clone()
+    y2 = op.step(x).clone()
+    assert torch.equal(y1, y2)
+    np.save(os.path.join(out_dir, f'ys_{rank}.npy'), y1.numpy())
 
 
 @pytest.mark.parametrize('world', [2, 3])
@@ -117,7 +91,7 @@ def test_split_phase_row_partitioned_spmv_gloo(tmp_path, world):
     "the slice travels while the cut rows are computed, their values follow in a small all-gather: the single-process y"
     from csr_amd import synth
     from oracle import oracle as O
-    mp.spawn(_worker_split, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    spawn(_worker_split, world, str(tmp_path))
     full = synth.powerlaw_csr(6000, 5000, 90000, device='cpu')
     x = synth.dense_vector(5000, device='cpu').numpy()
     ref = O.mult_vec(6000, 5000, full['rowptrs'].numpy(), full['colinds'].numpy(), full['values'].numpy(), x)
@@ -125,39 +99,65 @@ def test_split_phase_row_partitioned_spmv_gloo(tmp_path, world):
         assert np.array_equal(np.load(tmp_path / f'ys_{r}.npy'), ref)
 
 
-def _worker_equal(rank, world, port, out_dir):
-    sys.path.insert(0, ROOT)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
-    try:
-        from csr_amd import synth
-        from csr_amd.dist import RowPartitionedSpMV
-        from oracle import oracle as O
-        full = synth.powerlaw_csr(6000, 5000, 90000, device='cpu')
-        x = synth.dense_vector(5000, device='cpu')
-        rp, ci, vs = (full[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
-        bounds = [6000 * g // world for g in range(world + 1)]      # equal slices: the only kind gloo's all_gather takes
-        a, b = bounds[rank], bounds[rank + 1]
+def _worker_equal(rank, world, out_dir):
+    from csr_amd import synth
+    from csr_amd.dist import RowPartitionedSpMV
+    from oracle import oracle as O
+    full = synth.powerlaw_csr(6000, 5000, 90000, device='cpu')
+    x = synth.dense_vector(5000, device='cpu')
+    rp, ci, vs = (full[k].numpy() for k in ('rowptrs', 'colinds', 'values'))
+    bounds = [6000 * g // world for g in range(world + 1)]      # equal slices: the only kind gloo's all_gather takes
+    a, b = bounds[rank], bounds[rank + 1]
 
-        def local_spmv(xt, out):
-            out.copy_(torch.from_numpy(O.mult_vec(b - a, 5000, rp[a:b + 1] - rp[a], ci[rp[a]:rp[b]], vs[rp[a]:rp[b]], xt.numpy())))
+    def local_spmv(xt, out):
+        out.copy_(torch.from_numpy(O.mult_vec(b - a, 5000, rp[a:b + 1] - rp[a], ci[rp[a]:rp[b]], vs[rp[a]:rp[b]], xt.numpy())))
 
-        op = RowPartitionedSpMV(bounds, rank, world, local_spmv, 'cpu', mode='allgatherv')
-        y1 = op.step(x).clone()
-        assert torch.equal(y1, op.step(x))
-        np.save(os.path.join(out_dir, f'yv_{rank}.npy'), y1.numpy())
-    finally:
-        dist.destroy_process_group()
+    op = RowPartitionedSpMV(bounds, rank, world, local_spmv, 'cpu', mode='allgatherv')
+    y1 = op.step(x).clone()
+    assert torch.equal(y1, op.step(x))
+    np.save(os.path.join(out_dir, f'yv_{rank}.npy'), y1.numpy())
 
 
 def test_allgatherv_mode_gloo(tmp_path):
     "the slices of y as the output list of one all_gather (equal slices here: gloo; RCCL also takes unequal ones)"
     from csr_amd import synth
     from oracle import oracle as O
-    mp.spawn(_worker_equal, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    spawn(_worker_equal, 2, str(tmp_path))
     full = synth.powerlaw_csr(6000, 5000, 90000, device='cpu')
     x = synth.dense_vector(5000, device='cpu').numpy()
     ref = O.mult_vec(6000, 5000, full['rowptrs'].numpy(), full['colinds'].numpy(), full['values'].numpy(), x)
     for r in range(2):
         assert np.array_equal(np.load(tmp_path / f'yv_{r}.npy'), ref)
+
+
+def test_one_rank_without_process_group():
+    """
+    world 1, no process group: RowPartitionedSpMV's step is exactly one local product, written straight into op.y (the
+    single-GPU headline of bench.py times this path); compute_ms() of every operator is 0.0 when no launch was timed
+    (CPU outputs record no events), and stays 0.0 after it reset
+    """
+    from csr_amd.dist import RowPartitionedSpMM, RowPartitionedSpMV, SplitPhaseRowPartitionedSpMV
+    x = torch.ones(3, dtype=torch.float64)
+    calls = []
+
+    def local_spmv(xt, out):
+        calls.append(out)
+        out.fill_(len(calls))
+
+    op = RowPartitionedSpMV([0, 4], 0, 1, local_spmv, 'cpu')
+    assert op.compute_ms() == 0.0
+    op.timing = True
+    for s in range(1, 4):
+        assert op.step(x) is op.y and len(calls) == s and calls[-1] is op.y
+        assert torch.equal(op.y, torch.full((4,), float(s), dtype=torch.float64))
+    assert op.compute_ms() == 0.0 and op.compute_ms() == 0.0
+
+    split = SplitPhaseRowPartitionedSpMV([0, 4], 0, 1, lambda xt, out, part: out.fill_(part),
+                                         torch.zeros(0, dtype=torch.int64), 'cpu')
+    spmm = RowPartitionedSpMM([0, 4], 0, 1, lambda B, out, c0, c1: out.fill_(c0), 'cpu', 5, col_block=2)
+    for o, arg in ((split, x), (spmm, torch.ones(3, 5, dtype=torch.float64))):
+        o.timing = True
+        o.step(arg)
+        assert o.compute_ms() == 0.0 and o.compute_ms() == 0.0
+    assert torch.equal(split.y, torch.full((4,), 2.0, dtype=torch.float64))
+    assert torch.equal(spmm.C, torch.tensor([0.0, 0.0, 2.0, 2.0, 4.0], dtype=torch.float64).expand(4, 5))

@@ -6,27 +6,15 @@ what the distributed form adds: the padded all-gather / the all-gather of slabs 
 columns (k = 37: blocks of 16 and of 5 leave a short last block) and their strided copies into C.
 """
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from gloo_harness import spawn
 
 NROWS, NCOLS, NNZ, K = 3000, 2500, 40000, 37
 BLOCKS = [None, 16, 5]
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _matrix(kind):
@@ -57,33 +45,26 @@ def _bounds(kind, rp, nrows, world, equal):
     return synth.balanced_row_ranges(torch.from_numpy(rp.astype(np.int64)), world)
 
 
-def _worker(rank, world, port, kind, mode, equal, out_dir):
-    sys.path.insert(0, ROOT)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
-    try:
-        from csr_amd.dist import RowPartitionedSpMM
-        from oracle import oracle as O
-        nrows, ncols, rp, ci, vs = _matrix(kind)
-        B = _panel(ncols)
-        bounds = _bounds(kind, rp, nrows, world, equal)
-        a, b = bounds[rank], bounds[rank + 1]
-        lrp = rp[a:b + 1] - rp[a]
-        lci, lvs = ci[rp[a]:rp[b]], vs[rp[a]:rp[b]]
+def _worker(rank, world, kind, mode, equal, out_dir):
+    from csr_amd.dist import RowPartitionedSpMM
+    from oracle import oracle as O
+    nrows, ncols, rp, ci, vs = _matrix(kind)
+    B = _panel(ncols)
+    bounds = _bounds(kind, rp, nrows, world, equal)
+    a, b = bounds[rank], bounds[rank + 1]
+    lrp = rp[a:b + 1] - rp[a]
+    lci, lvs = ci[rp[a]:rp[b]], vs[rp[a]:rp[b]]
 
-        def local_spmm(Bt, out, c0, c1):
-            assert tuple(out.shape) == (b - a, c1 - c0)
-            out.copy_(torch.from_numpy(O.spmm_dense(b - a, lrp, lci, lvs, Bt[:, c0:c1].numpy())))
+    def local_spmm(Bt, out, c0, c1):
+        assert tuple(out.shape) == (b - a, c1 - c0)
+        out.copy_(torch.from_numpy(O.spmm_dense(b - a, lrp, lci, lvs, Bt[:, c0:c1].numpy())))
 
-        for cb in BLOCKS:
-            op = RowPartitionedSpMM(bounds, rank, world, local_spmm, 'cpu', K, mode=mode, col_block=cb)
-            c1 = op.step(B).clone()
-            assert torch.equal(c1, op.step(B))          # buffers are reused: a second step gives the same bytes
-            np.save(os.path.join(out_dir, f'c_{cb}_{rank}.npy'), c1.numpy())
-        np.save(os.path.join(out_dir, f'bounds_{rank}.npy'), np.array(bounds))
-    finally:
-        dist.destroy_process_group()
+    for cb in BLOCKS:
+        op = RowPartitionedSpMM(bounds, rank, world, local_spmm, 'cpu', K, mode=mode, col_block=cb)
+        c1 = op.step(B).clone()
+        assert torch.equal(c1, op.step(B))          # buffers are reused: a second step gives the same bytes
+        np.save(os.path.join(out_dir, f'c_{cb}_{rank}.npy'), c1.numpy())
+    np.save(os.path.join(out_dir, f'bounds_{rank}.npy'), np.array(bounds))
 
 
 def _check(tmp_path, world, kind):
@@ -103,21 +84,21 @@ def _check(tmp_path, world, kind):
 @pytest.mark.parametrize('world', [2, 3])
 @pytest.mark.parametrize('mode', ['allgather', 'allreduce'])
 def test_row_partitioned_spmm_gloo(tmp_path, world, mode):
-    mp.spawn(_worker, args=(world, _free_port(), 'powerlaw', mode, False, str(tmp_path)), nprocs=world, join=True)
+    spawn(_worker, world, 'powerlaw', mode, False, str(tmp_path))
     b = _check(tmp_path, world, 'powerlaw')[0]
     assert b[0] == 0 and b[-1] == NROWS and np.all(np.diff(b) > 0)
 
 
 def test_row_partitioned_spmm_allgatherv_gloo(tmp_path):
     "the slabs themselves as the output list of one all_gather (equal slabs: gloo; RCCL also takes unequal ones)"
-    mp.spawn(_worker, args=(2, _free_port(), 'powerlaw', 'allgatherv', True, str(tmp_path)), nprocs=2, join=True)
+    spawn(_worker, 2, 'powerlaw', 'allgatherv', True, str(tmp_path))
     _check(tmp_path, 2, 'powerlaw')
 
 
 @pytest.mark.parametrize('mode', ['allgather', 'allreduce'])
 def test_row_partitioned_spmm_rank_without_rows(tmp_path, mode):
     "a world larger than the rows that hold the entries: the middle rank owns no rows and still takes part"
-    mp.spawn(_worker, args=(3, _free_port(), 'one_heavy_row', mode, False, str(tmp_path)), nprocs=3, join=True)
+    spawn(_worker, 3, 'one_heavy_row', mode, False, str(tmp_path))
     b = _check(tmp_path, 3, 'one_heavy_row')[0]
     assert b[2] - b[1] == 0 and b[1] - b[0] > 0 and b[3] - b[2] > 0
 

@@ -2060,6 +2060,7 @@ int csrk_spgemm_last_route(int *route)
 
 int csrk_spgemm_ab(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 {
+    t_last_route = 0;      // (a call that fails before spgemm_impl must not report the previous call's route)
     CSRK_REQUIRE(out, "out is NULL");
     *out = 0;
     Matrix *a = from_handle(ah), *b = from_handle(bh);
@@ -2073,6 +2074,7 @@ int csrk_spgemm_ab(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 // A B^T = mult_ab(A, transpose(B)) exactly as the reference does it (multiply.py:54-57)
 int csrk_spgemm_abt(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 {
+    t_last_route = 0;
     CSRK_REQUIRE(out, "out is NULL");
     *out = 0;
     Matrix *a = from_handle(ah), *b = from_handle(bh);

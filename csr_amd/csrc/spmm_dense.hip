@@ -177,7 +177,7 @@ __device__ __forceinline__ void mm_unit(const int32_t *__restrict__ ci, const vo
 // Where a row of the product goes.  Plain (csrk_spmm_dense): row i at C + i * ldc, columns ascending.  As the reference's
 // mult_ab returns a product with a fully populated B (csrk_spgemm_ab's dense route, below): the rows of A without
 // entries have no entries in C (row_base < 0: nothing stored), the others k each at C + row_base[i], columns k - 1 .. 0
-// (rev_k = k: panel column c is stored at k - 1 - c).
+// in the reference's order (rev_k = k: panel column c is stored at k - 1 - c), 0 .. k - 1 in ascending order (rev_k = 0).
 struct SpmmOut {
     const int64_t *row_base;      // nullptr: i * ldc
     int32_t rev_k;                // 0: ascending columns
@@ -869,9 +869,11 @@ static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, doub
 // entry of a row of A discovers the k columns 0 .. k - 1 of its row of B, pushed one by one onto the FRONT of the row's
 // list (multiply.py:79-82), copied out front to back (:94-97) -- every row of C whose row of A holds an entry is
 // k - 1 .. 0, the others are empty -- and the values are the panel's (work[c] += a * b over the row's entries in storage
-// order, :110-122; explicit zeros kept).  One kernel checks B, the dense-panel kernels above write C's values in place
-// (SpmmOut), C's index arrays are filled beside them.  Anything else -- a row of B short of a column, or in another
-// order; float32 values on BOTH operands, whose products the reference rounds to float32 -- takes the general product.
+// order, :110-122; explicit zeros kept).  Under csrk_spgemm_set_order(0) / CSRK_SPGEMM_ORDER=ascending the rows are
+// 0 .. k - 1 instead, as the general product's are: the same sums, stored in the other order.  One kernel checks B, the
+// dense-panel kernels above write C's values in place (SpmmOut), C's index arrays are filled beside them.  Anything
+// else -- a row of B short of a column, or in another order; float32 values on BOTH operands, whose products the
+// reference rounds to float32 -- takes the general product.
 template <class P>
 __global__ __launch_bounds__(256) void dense_b_check_kernel(const P *__restrict__ rp, const int32_t *__restrict__ ci,
                                                            int32_t nrows, int32_t k, int32_t *__restrict__ bad)
@@ -901,10 +903,11 @@ __global__ void dense_c_rows_kernel(const int64_t *__restrict__ rank, int32_t nr
     if (i < nrows) row_base[i] = rank[i + 1] > rank[i] ? rank[i] * k : -1;
 }
 
-__global__ __launch_bounds__(256) void dense_c_cols_kernel(int32_t *__restrict__ ci, int64_t n, int32_t k)
+// the columns of C's rows: k - 1 .. 0 (the reference's order) or 0 .. k - 1 (ascending)
+__global__ __launch_bounds__(256) void dense_c_cols_kernel(int32_t *__restrict__ ci, int64_t n, int32_t k, bool reference_order)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) __builtin_nontemporal_store(k - 1 - (int32_t)(i % k), ci + i);
+    if (i < n) __builtin_nontemporal_store(reference_order ? k - 1 - (int32_t)(i % k) : (int32_t)(i % k), ci + i);
 }
 
 __global__ void dense_widen_kernel(const float *__restrict__ in, double *__restrict__ out, int64_t n)
@@ -912,6 +915,8 @@ __global__ void dense_widen_kernel(const float *__restrict__ in, double *__restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (double)in[i];
 }
+
+bool spgemm_reference_order_wanted();      // spgemm_order.hip
 
 // *taken = false: B is not a row-major panel (or the route is switched off): the caller runs the general product
 int spgemm_dense_b(Matrix *a, Matrix *b, Matrix **out, bool *taken)
@@ -964,12 +969,13 @@ int spgemm_dense_b(Matrix *a, Matrix *b, Matrix **out, bool *taken)
                   "multiply row blocks of A instead", (long long)c_nnz);
         return CSRK_ERR_OVERFLOW;
     }
+    const bool ref_order = spgemm_reference_order_wanted();      // (read once: C's columns and the stores of its values agree)
     Matrix *c = nullptr;
     CSRK_TRY(new_matrix(nr, k, c_nnz, 0, CSRK_VAL_F64, &c));
     dense_c_rows_kernel<<<ga, 256>>>(rank.as<int64_t>(), nr, k, (int32_t *)c->d_rowptrs, row_base.as<int64_t>());
     int rc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
     if (rc == CSRK_OK && c_nnz > 0) {
-        dense_c_cols_kernel<<<(unsigned)ceil_div(c_nnz, 256), 256>>>(c->d_colinds, c_nnz, k);
+        dense_c_cols_kernel<<<(unsigned)ceil_div(c_nnz, 256), 256>>>(c->d_colinds, c_nnz, k, ref_order);
         rc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
     }
     DevBuf wide;      // a float32 panel under float64 values of A: widened (exactly) once
@@ -982,7 +988,7 @@ int spgemm_dense_b(Matrix *a, Matrix *b, Matrix **out, bool *taken)
             panel = wide.as<double>();
         }
     }
-    if (rc == CSRK_OK && c_nnz > 0) rc = spmm_device(a, panel, k, k, (double *)c->d_values, k, nullptr, SpmmOut{row_base.as<int64_t>(), k});
+    if (rc == CSRK_OK && c_nnz > 0) rc = spmm_device(a, panel, k, k, (double *)c->d_values, k, nullptr, SpmmOut{row_base.as<int64_t>(), ref_order ? k : 0});
     // (row_base, the widened panel and C's arrays are recycled in default-stream order: the launches above are on it)
     if (rc == CSRK_OK && hipDeviceSynchronize() != hipSuccess) rc = CSRK_ERR_HIP;
     if (rc != CSRK_OK) {

@@ -620,8 +620,8 @@ def set_spgemm_order(order):
     """
     Column order inside the rows mult_ab / mult_abt return: 'reference' (default) -- reverse order of first discovery,
     what csr/kernels/numba/multiply.py:79-82, 94-97 emit --, 'ascending' (the product kernels' own: no ordering pass) or
-    None (follow CSRK_SPGEMM_ORDER: "ascending", else the reference's).  Process-wide.  The values are the same bits
-    either way.
+    None (follow CSRK_SPGEMM_ORDER: "ascending", else the reference's).  Process-wide, and followed by every route: the
+    dense-panel route (a fully populated B, spgemm_last_route) too.  The values are the same bits either way.
     """
     code = {None: -1, 'ascending': 0, 'reference': 1}[order]
     check(lib.csrk_spgemm_set_order(code))

@@ -701,7 +701,7 @@ def _panel_csr(B, cols=None, vals=None, ptr64=False):
     return CSR(n, k, n * k, rp, cols, vals, _cast=False)
 
 
-def test_mult_ab_with_a_dense_b_golden(golden):
+def test_mult_ab_with_a_dense_b_golden(golden, reference_order):
     """
     BASELINE configs[2] through the reference's OWN entry point: K.mult_ab(A, CSR(B)) with B fully populated
     (csr/csr.py:524-567 -> csr/kernels/numba/multiply.py:13-38).  The library recognises the row-major panel on the
@@ -736,7 +736,7 @@ def test_mult_ab_with_a_dense_b_golden(golden):
 
 
 @pytest.mark.parametrize('k,dtype,ptr64', [(64, np.float64, False), (7, np.float32, False), (130, np.float64, True), (1, np.float64, False)])
-def test_mult_ab_with_a_dense_b_vs_oracle(k, dtype, ptr64, monkeypatch):
+def test_mult_ab_with_a_dense_b_vs_oracle(k, dtype, ptr64, monkeypatch, reference_order):
     """
     The same route on a power-law A with rows far beyond one segment (and, forced, the heavy-row kernels), against the
     pinned oracle's orc_mult_ab on the same two CSR operands: rowptrs and colinds bit for bit, values bit for bit on the
@@ -777,7 +777,7 @@ def test_mult_ab_with_a_dense_b_vs_oracle(k, dtype, ptr64, monkeypatch):
     assert P.nnz == int(keep.sum()) and np.array_equal(P.colinds, ci[keep]) and np.array_equal(P.values, C.values[keep])
 
 
-def test_mult_ab_dense_route_declines(monkeypatch):
+def test_mult_ab_dense_route_declines(monkeypatch, reference_order):
     "what is NOT a row-major panel takes the general product: a row short of one column, float32 on both operands, the switch"
     from oracle import oracle as O
     from csr_amd import CSR

@@ -615,6 +615,64 @@ def test_spmv_float32_vector_on_the_device_and_a_stream(vals):
         K.release_handle(h)
 
 
+@pytest.mark.parametrize('vals', ['f4', 'f8'])
+def test_spmv_device_entries_with_offset_buffers(vals, monkeypatch):
+    """
+    csrk_spmv_device, csrk_spmv_device_part (part 1 then part 2, as the split-phase operator issues them) and
+    csrk_spmv_f32x_device with x and y views at element offset 1 of larger tensors: x 8-byte (float64) or 4-byte (float32)
+    aligned, never 16-byte, and y as a row range of a rank's slice is.  The kernels load x in 8- and 16-byte pairs declared
+    for 4-byte alignment (spmv_plan.h): every call -- the first, plan-less one and the planned ones -- equals the same
+    call on aligned buffers bit for bit, and nothing outside y's view is written.
+    """
+    import ctypes as C
+    import torch
+    from csr_amd import CSR
+    from csr_amd._lib import lib, check
+    from csr_amd.kernels import hip as K
+    monkeypatch.setenv('CSRK_HANDLE_CACHE', '0')              # a fresh handle (no plan) per run
+    rng = np.random.default_rng(21)
+    lens = np.minimum((rng.pareto(0.8, 30000) * 4).astype(np.int64), 20000)
+    m = _random_csr(rng, 30000, 600000, lens, dtype=np.float32 if vals == 'f4' else np.float64, sort=True)
+    A = CSR(m.nrows, m.ncols, m.nnz, m.rowptrs, m.colinds, m.values, _cast=False)
+    x64 = rng.uniform(-1, 1, size=m.ncols)
+    dev = torch.device('cuda', 0)
+    st = torch.cuda.Stream(device=dev)
+
+    def run(entry, x, offset):
+        xb = torch.full((m.ncols + 2 * offset,), float('nan'), dtype=torch.float32 if entry == 'f32x' else torch.float64,
+                        device=dev)
+        xv = xb[offset:offset + m.ncols]
+        xv.copy_(torch.from_numpy(x))
+        yb = torch.full((m.nrows + 2 * offset,), float('nan'), dtype=torch.float64, device=dev)
+        yv = yb[offset:offset + m.nrows]
+        assert xv.data_ptr() % 16 == (xv.element_size() * offset) % 16 and yv.data_ptr() % 16 == 8 * offset
+        h = K.to_handle(A)
+        out = []
+        try:
+            torch.cuda.synchronize()
+            s = C.c_void_p(st.cuda_stream)
+            for _ in range(3):
+                if entry == 'f32x':
+                    check(lib.csrk_spmv_f32x_device(K._live(h), xv.data_ptr(), yv.data_ptr(), s))
+                elif entry == 'part':
+                    check(lib.csrk_spmv_device_part(K._live(h), xv.data_ptr(), yv.data_ptr(), s, 1))
+                    check(lib.csrk_spmv_device_part(K._live(h), xv.data_ptr(), yv.data_ptr(), s, 2))
+                else:
+                    check(lib.csrk_spmv_device(K._live(h), xv.data_ptr(), yv.data_ptr(), s))
+                st.synchronize()
+                out.append(yb.cpu().numpy())
+        finally:
+            K.release_handle(h)
+        return out
+
+    for entry, x in (('device', x64), ('part', x64), ('f32x', x64.astype(np.float32))):
+        aligned, shifted = run(entry, x, 0), run(entry, x, 1)
+        for i, (ya, yb_) in enumerate(zip(aligned, shifted)):
+            assert not np.isnan(ya).any(), (entry, i)
+            assert np.isnan(yb_[0]) and np.isnan(yb_[-1]), (entry, i)
+            assert np.array_equal(ya.view(np.int64), yb_[1:-1].view(np.int64)), (entry, i)
+
+
 def test_float32_matrix_keeps_float32_streams(split_mode):
     """
     A float32 matrix's plan stores float32 values in the tier-0 and light streams (6 and 8 bytes per entry instead of 10 and

@@ -322,6 +322,32 @@ class CSR:
                 ys.append(K.mult_vec(h, v))
         return ys[0] if len(ys) == 1 else np.concatenate(ys)
 
+    def sddmm(self, U, V, *, scale=False):
+        """
+        Sampled dense-dense product on this pattern: a new CSR with the same shape, row pointers and column order whose
+        value at each stored entry (i, j) is dot(U[i, :], V[j, :]), times the entry's value with scale=True (1.0 for a
+        structure-only matrix).  U [nrows x k] and V [ncols x k] are both float32 or both float64; the values are float64.
+        The structure is copied from the host arrays; only the values come back from the device.  Above K.max_nnz the
+        row blocks' values are concatenated in row order.  Not a reference entry point.
+        """
+        U, V = np.asarray(U), np.asarray(V)
+        if U.ndim != 2 or V.ndim != 2:
+            raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
+        if U.dtype != V.dtype or U.dtype not in (np.float32, np.float64):
+            raise ValueError(f'U and V must both be float32 or both float64, not {U.dtype} and {V.dtype}')
+        if U.shape[0] != self.nrows or V.shape[0] != self.ncols or U.shape[1] != V.shape[1] or U.shape[1] == 0:
+            raise ValueError(f'panels of shapes {U.shape} and {V.shape} do not fit a {self.nrows} x {self.ncols} '
+                             'matrix (expected (nrows, k) and (ncols, k), k >= 1)')
+        K, fn = self._ext('sddmm')
+        vs = []
+        r0 = 0
+        for blk in self._row_blocks(K.max_nnz):
+            with releasing(K.to_handle(blk), K) as h:
+                vs.append(fn(h, U[r0:r0 + blk.nrows], V, scale))
+            r0 += blk.nrows
+        vals = vs[0] if len(vs) == 1 else np.concatenate(vs)
+        return CSR(self.nrows, self.ncols, self.nnz, self.rowptrs.copy(), self.colinds.copy(), vals, _cast=False)
+
     def _row_blocks(self, limit):
         "the matrix itself when it fits the kernel's max_nnz, else its _shard_rows blocks"
         return [self] if self.nnz <= limit else self._shard_rows(limit)

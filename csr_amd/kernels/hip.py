@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -613,6 +613,48 @@ def mult_dense(h, B):
     k = B.shape[1]
     out = _out((h.nrows, k), np.float64)
     _call(lib.csrk_spmm_dense, _live(h), ptr(B), k, k, ptr(out), k)
+    return out
+
+
+_PANEL_CODES = {np.dtype('f4'): _lib.VAL_F32, np.dtype('f8'): _lib.VAL_F64}
+
+
+def _panel(P, rows, name):
+    "a 2-D float32 / float64 panel of `rows` rows as (array, ld): a row-major view with unit column stride keeps its row stride"
+    if P.ndim != 2:
+        raise ValueError(f'{name} must be 2-D, not of shape {P.shape}')
+    if P.dtype not in _PANEL_CODES:
+        raise ValueError(f'{name} must be float32 or float64, not {P.dtype}')
+    if P.shape[0] != rows:
+        raise ValueError(f'{name} has {P.shape[0]} rows, expected {rows}')
+    es = P.dtype.itemsize
+    if P.strides[1] == es and P.strides[0] % es == 0 and P.strides[0] >= P.shape[1] * es:
+        return P, P.strides[0] // es
+    P = np.ascontiguousarray(P)
+    return P, P.shape[1]
+
+
+def sddmm(h, U, V, scale=False):
+    """
+    Sampled dense-dense product: for every stored entry (i, j) of the handle's matrix, in its storage order,
+    dot(U[i, :], V[j, :]) -- times the entry's value with scale=True (1.0 for a structure-only matrix) -- as a fresh
+    float64[nnz].  U [nrows x k] and V [ncols x k] are both float32 or both float64; the sums are float64 in a fixed order
+    (include/csrk.h).  Not a reference entry point.
+    """
+    U, V = np.asarray(U), np.asarray(V)
+    if U.ndim != 2 or V.ndim != 2:
+        raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
+    if U.dtype != V.dtype:
+        raise ValueError(f'U and V must have the same dtype, not {U.dtype} and {V.dtype}')
+    if U.shape[1] != V.shape[1]:
+        raise ValueError(f'U and V have {U.shape[1]} and {V.shape[1]} columns')
+    if U.shape[1] == 0:
+        raise ValueError('panels have no columns (k = 0)')
+    U, ldu = _panel(U, h.nrows, 'U')
+    V, ldv = _panel(V, h.ncols, 'V')
+    k = U.shape[1]
+    out = _out(h.nnz, np.float64)
+    _call(lib.csrk_sddmm, _live(h), ptr(U), ldu, ptr(V), ldv, k, _PANEL_CODES[U.dtype], int(bool(scale)), ptr(out))
     return out
 
 

@@ -231,6 +231,33 @@ CSRK_API int csrk_spmm_dense_device(csrk_handle_t a, const double *d_B, int32_t 
  * [4] column ranges, [5] their entries, [6] column tiles, [7] segments of the other rows, [8] of which partial (split rows). */
 CSRK_API int csrk_spmm_plan_stats(csrk_handle_t a, int64_t *out, int n);
 
+/* ---- sampled dense-dense product (SDDMM): one value per stored entry ---------------------
+ * Not a reference entry point (the reference's mult_ab is sparse x sparse only); the transpose-dual of
+ * csrk_spmm_dense.  U is dense row-major [nrows x k], V dense row-major [ncols x k], both float32 or both float64
+ * (panel_type CSRK_VAL_F32 / CSRK_VAL_F64); ldu / ldv >= k in elements.  For every stored entry e = (i, j), in the
+ * handle's storage order (unsorted and repeated columns are just more entries):
+ *   out[e] = dot(U[i, :], V[j, :])                        scale = 0
+ *   out[e] = values[e] * dot(U[i, :], V[j, :])            scale = 1 (float32 values widened; structure-only: 1.0, as above)
+ * out is float64 whatever the panel type.  Order of addition, fixed by k and the panel type alone (not by the entry's
+ * position, its row's length, the pointer width, the strides, the alignment, the stream or the launch, so an entry gets
+ * the same bits whatever else the matrix holds): 16 partial sums, partial l over its columns below k in ascending order
+ * (in each 64-column chunk c: float64 64 c + {2 l, 2 l + 1, 32 + 2 l, 33 + 2 l}, float32 64 c + {4 l .. 4 l + 3}),
+ * each step one fused multiply-add from +0.0 (float32 panels: the product of the
+ * widened operands is exact, so one rounding per step); then the 16 partials added by the fixed tree of distances
+ * 1, 2, 4, 8 (csrc/sddmm.hip); then the value multiplied in once.  Accuracy: within (k / 16 + 4) ulp-scale roundings of
+ * sum_t |u_t v_t| (times |value|), far inside 1e-12 of it for any k a panel holds.  NaN and Inf propagate as IEEE says.
+ * Alignment: U and V need their element size; when both are 16-B aligned and ldu, ldv are multiples of 16 B the kernel
+ * takes 16-B loads, else 8-B (float64) or 4-B (float32) ones -- the same bits either way.
+ * nnz = 0 or nrows = 0: CSRK_OK, nothing launched.  CSRK_ERR_INVALID for k < 1, ldu < k, ldv < k, an unknown panel_type,
+ * a scale other than 0 / 1, or a NULL U, V or out when nnz > 0.
+ * Host form: host panels in, out[nnz] float64 in host memory (the panels cross packed; synchronous). */
+CSRK_API int csrk_sddmm(csrk_handle_t s, const void *U, int64_t ldu, const void *V, int64_t ldv,
+                        int32_t k, int panel_type, int scale, double *out);
+/* Device form: d_U, d_V, d_out in HBM (e.g. torch tensors' data_ptr()), launched on `stream` (NULL = the default
+ * stream); nothing is allocated and the host is not synchronised. */
+CSRK_API int csrk_sddmm_device(csrk_handle_t s, const void *d_U, int64_t ldu, const void *d_V, int64_t ldv,
+                               int32_t k, int panel_type, int scale, double *d_out, void *stream);
+
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).
  * Bit-exact with the reference's stable counting sort: output rowptrs keep the input

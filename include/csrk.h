@@ -124,6 +124,22 @@ CSRK_API int csrk_device_ptrs(csrk_handle_t h, void **d_rowptrs, void **d_colind
  * entries, y receives nrows float64 entries (every entry is written; empty rows get 0).
  * Structure-only matrices multiply with implicit 1.0 (csr/csr.py:254-262).            */
 CSRK_API int csrk_spmv(csrk_handle_t h, const double *x, double *y);
+/* Special values, for every product (mult_vec, mult_ab / _abt, the dense-panel SpMM, SDDMM), as the reference computes them
+ * (tests/test_gpu_special_values.py pins each point):
+ *   - NaN and +-Inf propagate as IEEE says: which outputs are NaN, +Inf or -Inf is the reference's.  An explicit 0.0 or -0.0
+ *     value times an infinite or NaN operand gives NaN: no path skips an explicit zero.
+ *   - A sum starts at +0.0, like the reference's accumulators: a row whose products are all -0.0, or cancel exactly, is +0.0.
+ *     (SDDMM: its dot starts at +0.0 and is then multiplied by the value, so a negative value times a +0.0 dot is -0.0.)
+ *   - float32 values times float32 x (csrk_spmv_f32x*, and mult_ab with float32 values on both operands) is a float32
+ *     product: rounded once, +-Inf above FLT_MAX, subnormal (not flushed) below FLT_MIN.  Every other float32 input -- values
+ *     against float64 x, float32-valued SpMM, SDDMM's float32 panels -- is widened exactly, subnormals included, and its
+ *     products are float64.
+ *   - An output depends only on the inputs the reference's loop reads into it: a NaN or Inf in an x entry, a B / U / V row
+ *     or a panel column that no product of that output uses changes nothing, not a single bit.
+ *   - Data movement (transpose, order_columns, pick_rows, from_coo, filter_zeros) copies values bit for bit, NaN payloads and
+ *     -0.0 included; filter_zeros drops +0.0 and -0.0 and keeps every NaN.
+ * Deliberate difference from the reference: the sign and payload of a NaN a product creates are not specified (the
+ * reference's x86 loop gives the negative default NaN, the GPU the positive one); only its position is. */
 /* The same with x given as float32 (host pointers).  Numba types the reference's loop by its operands
  * (csr/kernels/numba/__init__.py:55-67): float32 values times float32 x is a float32 product -- one rounding -- added to the
  * float64 accumulator; with float64 or absent values x is widened and the product is float64 (= csrk_spmv). */

@@ -9,7 +9,8 @@ feeds it seeded inputs, and stores inputs + the reference's outputs.  The fixtur
 data only; neither this script nor the fixtures contain reference source.  Nothing on the
 GPU box needs /root/reference: tests read the committed .npz files.
 
-Run:  python oracle/gen/gen_golden.py        (writes tests/golden/)
+Run:  python oracle/gen/gen_golden.py              (writes every fixture under tests/golden/)
+      python oracle/gen/gen_golden.py special ...  (writes only the fixtures named, e.g. special.npz)
 
 Input distributions restate csr/test_utils.py:30-101 (`csrs`, `mm_pairs`): shapes 1..80
 (mm: 1..100), density <= 0.5, unique COO coordinates, values in +-1e3 of dtype f4/f8 with
@@ -330,16 +331,276 @@ def gen_spmm_dense(n=12):
     np.savez_compressed(os.path.join(OUT, 'spmm_dense.npz'), **d)
 
 
+def save_stable(path, d):
+    """
+    np.savez_compressed with fixed zip member timestamps: the same arrays give the same bytes on every run (numpy stamps
+    members with the current time).
+    """
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_DEFLATED) as z:
+        for k, a in d.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def _special_x(rng, ncols):
+    """
+    x for the special-value cases: finite values in +-4 and, at disjoint columns, NaN, +Inf, -Inf, +0.0, -0.0, exact ones,
+    +-1e25 (float32 products with 1e20 overflow, float64 ones do not) and +-1e-20 / 1e-160 (subnormal products).
+    Returns x and a dict kind -> columns.
+    """
+    x = rng.uniform(-4.0, 4.0, size=ncols)
+    kinds = ('nan', 'pinf', 'ninf', 'pz', 'nz', 'one', 'huge', 'tiny32', 'tiny64')
+    cols = rng.permutation(ncols)[:4 * len(kinds)].reshape(len(kinds), 4)
+    at = dict(zip(kinds, (np.sort(c) for c in cols)))
+    x[at['nan']] = np.nan
+    x[at['pinf']] = np.inf
+    x[at['ninf']] = -np.inf
+    x[at['pz']] = 0.0
+    x[at['nz']] = -0.0
+    x[at['one']] = 1.0
+    x[at['huge']] = [1e25, -1e25, 1e25, 3e25]
+    x[at['tiny32']] = [1e-20, -1e-20, 3e-21, 1e-19]
+    x[at['tiny64']] = [1e-160, -1e-160, 3e-161, 1e-159]
+    return x, at
+
+
+def _special_rows(rng, nrows, ncols, at, dt):
+    """
+    One CSR (row by row, struct built directly: nothing filtered) whose rows cycle through the patterns the kernels get
+    wrong: random rows with NaN / +-Inf / +-0.0 values, one-entry rows whose product is -0.0, long rows whose products are
+    all -0.0, exact cancellation, +Inf and -Inf in one row, explicit +-0.0 values against non-finite x, float32-overflowing
+    and subnormal products, empty rows.
+    """
+    f4 = dt == 'f4'
+    rows_c, rows_v = [], []
+    for i in range(nrows):
+        kind = i % 11
+        if kind == 0 or kind == 10:                 # random row, a few special values
+            n = int(rng.integers(1, max(2, ncols // 6)))
+            c = rng.choice(ncols, size=n, replace=False)
+            v = rng.uniform(-4.0, 4.0, size=n)
+            r = rng.random(n)
+            v[r < 0.08] = np.nan
+            v[(r >= 0.08) & (r < 0.14)] = np.inf
+            v[(r >= 0.14) & (r < 0.20)] = -np.inf
+            v[(r >= 0.20) & (r < 0.26)] = 0.0
+            v[(r >= 0.26) & (r < 0.32)] = -0.0
+        elif kind == 1:                             # one entry, product -0.0
+            if rng.random() < 0.5:
+                c, v = [rng.choice(at['pz'])], [-float(rng.uniform(0.5, 3))]
+            else:
+                c, v = [rng.choice(at['nz'])], [float(rng.uniform(0.5, 3))]
+        elif kind == 2:                             # long row, every product -0.0
+            n = int(rng.integers(8, 40))
+            c = rng.choice(np.concatenate([at['pz'], at['nz']]), size=n)
+            v = rng.uniform(0.5, 3.0, size=n)
+            v = np.where(np.isin(c, at['pz']), -v, v)
+            v[::5] = np.where(np.isin(c[::5], at['pz']), -0.0, 0.0)   # explicit zeros of the right sign too
+        elif kind == 3:                             # exact cancellation on x == 1
+            c = rng.choice(at['one'], size=4)
+            v = np.array([3.0, -5.0, 2.0, 0.0]) * float(rng.choice([1, 0.25, 8]))
+        elif kind == 4:                             # +Inf and -Inf products in one row
+            c = [rng.choice(at['pinf']), rng.choice(at['ninf']), rng.choice(at['one'])]
+            v = [float(rng.uniform(0.5, 2)), float(rng.uniform(0.5, 2)), 1.5]
+        elif kind == 5:                             # explicit +-0.0 against NaN / +-Inf x
+            c = [rng.choice(at['nan' if i % 3 == 0 else 'pinf' if i % 3 == 1 else 'ninf'])]
+            v = [0.0 if rng.random() < 0.5 else -0.0]
+        elif kind == 6:                             # non-finite values against finite x
+            c = rng.choice(at['one'], size=2, replace=False)
+            v = [(np.nan, np.inf, -np.inf)[i % 3], 1.0]
+        elif kind == 7:                             # empty
+            c, v = [], []
+        elif kind == 8:                             # float32 overflow: 1e20 * 1e25 (float64: 1e45)
+            c = [rng.choice(at['huge'])]
+            v = [1e20 if f4 else 1e120]
+        else:                                       # subnormal products
+            if f4:
+                c, v = [rng.choice(at['tiny32'])], [float(rng.choice([1e-20, -3e-19, 7e-21]))]
+            else:
+                c, v = [rng.choice(at['tiny64'])], [float(rng.choice([1e-160, -3e-159, 7e-161]))]
+        rows_c.append(np.asarray(c, dtype=np.int32))
+        rows_v.append(np.asarray(v, dtype=np.float64))
+    rp = np.zeros(nrows + 1, dtype=np.int32)
+    rp[1:] = np.cumsum([len(c) for c in rows_c])
+    ci = np.concatenate(rows_c).astype(np.int32) if nrows else np.zeros(0, np.int32)
+    vs = np.concatenate(rows_v) if nrows else np.zeros(0)
+    if dt is not None:
+        with np.errstate(all='ignore'):
+            vs = vs.astype(dt)
+    return CSR(nrows, ncols, int(rp[-1]), rp, ci, None if dt is None else vs)
+
+
+def _special_mm(rng, r, mid, k, dta, dtb):
+    """
+    A [r x mid] and B [mid x k] for the sparse products: random sparse rows with NaN / +-Inf / +-0.0 values in both,
+    and planted rows -- in A, rows that pick up a B row of -0.0 values (all products -0.0), two B rows that cancel
+    exactly, +Inf and -Inf rows of B, one-entry rows against a subnormal or float32-overflowing row of B.
+    """
+    def rnd(nr, nc, dens):
+        rows_c, rows_v = [], []
+        for _ in range(nr):
+            n = int(rng.binomial(nc, dens))
+            c = np.sort(rng.choice(nc, size=n, replace=False))
+            v = rng.uniform(-4.0, 4.0, size=n)
+            q = rng.random(n)
+            v[q < 0.03] = np.nan
+            v[(q >= 0.03) & (q < 0.06)] = np.inf
+            v[(q >= 0.06) & (q < 0.09)] = -np.inf
+            v[(q >= 0.09) & (q < 0.13)] = 0.0
+            v[(q >= 0.13) & (q < 0.17)] = -0.0
+            rows_c.append(c.astype(np.int32))
+            rows_v.append(v)
+        return rows_c, rows_v
+
+    ac, av = rnd(r, mid, 0.12)
+    bc, bv = rnd(mid, k, 0.2)
+    # B rows 0..5 are planted: 0 all -0.0 / +0.0 mixed so that (+a) * row = -0.0 products, 1 and 2 equal (cancellation),
+    # 3 all +Inf, 4 all -Inf, 5 tiny (subnormal products with tiny A values) / huge (float32 overflow)
+    f4 = dta == 'f4' and dtb == 'f4'
+    full = np.sort(rng.choice(k, size=max(1, k // 3), replace=False)).astype(np.int32)
+    bc[0], bv[0] = full, -np.zeros(len(full))
+    bc[1], bv[1] = full, rng.integers(-3, 4, size=len(full)).astype(np.float64)
+    bc[2], bv[2] = full.copy(), bv[1].copy()
+    bc[3], bv[3] = full, np.full(len(full), np.inf)
+    bc[4], bv[4] = full, np.full(len(full), -np.inf)
+    bc[5], bv[5] = full, np.full(len(full), 1e-20 if f4 else 1e-160) * rng.choice([1.0, -3.0], size=len(full))
+    for i in range(r):
+        kind = i % 7
+        if kind == 1:
+            ac[i], av[i] = np.array([0], np.int32), np.array([2.5])             # every product -0.0
+        elif kind == 2:
+            ac[i], av[i] = np.array([1, 2], np.int32), np.array([1.5, -1.5])    # exact cancellation
+        elif kind == 3:
+            ac[i], av[i] = np.array([3, 4], np.int32), np.array([1.0, 2.0])     # +Inf + -Inf
+        elif kind == 4:
+            ac[i], av[i] = np.array([5], np.int32), np.array([1e-20 if f4 else 1e-160])   # subnormal products
+        elif kind == 5 and f4:
+            ac[i], av[i] = np.array([6], np.int32), np.array([1e20])            # float32 overflow against B row 6
+    if f4:
+        bc[6], bv[6] = full, np.full(len(full), 1e25)
+
+    def build(nr, nc, cs, vs, dt):
+        rp = np.zeros(nr + 1, dtype=np.int32)
+        rp[1:] = np.cumsum([len(c) for c in cs])
+        with np.errstate(all='ignore'):
+            v = np.concatenate(vs).astype(dt)
+        return CSR(nr, nc, int(rp[-1]), rp, np.concatenate(cs).astype(np.int32), v)
+    return build(r, mid, ac, av, dta), build(mid, k, bc, bv, dtb)
+
+
+def _nan_payloads(rng, n):
+    "quiet NaNs of both signs with distinct payloads, as float64"
+    bits = (np.uint64(0x7ff8000000000000) | rng.integers(1, 1 << 40, size=n).astype(np.uint64))
+    bits[rng.random(n) < 0.5] |= np.uint64(1 << 63)
+    return bits.view(np.float64)
+
+
+def gen_special():
+    """
+    NaN, +-Inf, signed zeros and the float32 range through the reference (tests/test_oracle_golden.py pins the oracle on
+    it; tests/test_gpu_special_values.py feeds the library the same inputs).  Cases:
+      mv{c}   mult_vec with float64 and float32 x; values f8 / f4 / structure only
+      mm{c}   mult_ab and mult_abt as raw kernel arrays (explicit zeros kept), CSR.multiply (zeros filtered)
+      dn{c}   mult_ab with a fully populated B (the dense route's input), raw arrays
+      dm{c}   data movement on float64 values holding NaNs with distinct payloads and -0.0: transpose, sort_rows,
+              pick_rows, _filter_zeros, from_coo
+    """
+    rng = np.random.default_rng(20261016)
+    d = {}
+    n_mv = 9
+    d['n_mv'] = np.array(n_mv)
+    for c in range(n_mv):
+        dt = ('f8', 'f4', None)[c % 3]
+        nrows, ncols = int(rng.integers(40, 101)), int(rng.integers(40, 101))
+        x, at = _special_x(rng, ncols)
+        m = _special_rows(rng, nrows, ncols, at, dt)
+        put(d, f'mv{c}_', m)
+        d[f'mv{c}_x64'] = x
+        with np.errstate(all='ignore'):
+            x32 = x.astype(np.float32)
+            d[f'mv{c}_x32'] = x32
+            d[f'mv{c}_y64'] = K.mult_vec(K.to_handle(m), x)
+            d[f'mv{c}_y32'] = K.mult_vec(K.to_handle(m), x32)
+    n_mm = 6
+    d['n_mm'] = np.array(n_mm)
+    for c in range(n_mm):
+        dta, dtb = (('f8', 'f8'), ('f4', 'f4'), ('f4', 'f8'))[c % 3]
+        r, mid, k = int(rng.integers(20, 61)), int(rng.integers(10, 61)), int(rng.integers(8, 61))
+        A, B = _special_mm(rng, r, mid, k, dta, dtb)
+        put(d, f'mm{c}_a_', A)
+        put(d, f'mm{c}_b_', B)
+        with np.errstate(all='ignore'):
+            put(d, f'mm{c}_raw_', K.mult_ab(K.to_handle(A), K.to_handle(B)))
+            Bt = B.transpose()
+            if dtb == 'f4':                           # keep B^T float32 (transpose() widens)
+                Bt = CSR(Bt.nrows, Bt.ncols, Bt.nnz, Bt.rowptrs, Bt.colinds, Bt.values.astype(np.float32))
+            put(d, f'mm{c}_bt_', Bt)
+            put(d, f'mm{c}_rawt_', K.mult_abt(K.to_handle(A), K.to_handle(Bt)))
+            put(d, f'mm{c}_ab_', A.multiply(B))
+    n_dn = 3
+    d['n_dn'] = np.array(n_dn)
+    for c in range(n_dn):
+        k = (1, 7, 64)[c]
+        dt = ('f8', 'f4', 'f8')[c]
+        nrows, ncols = int(rng.integers(40, 61)), int(rng.integers(40, 61))
+        x, at = _special_x(rng, ncols)
+        A = _special_rows(rng, nrows, ncols, at, dt)
+        # the panel: row j of B is x[j] times a random positive factor in each column (so the rows' classes follow x)
+        B = x[:, None] * rng.uniform(0.5, 2.0, size=(ncols, k))
+        B[at['tiny32'] if dt == 'f4' else at['tiny64'], :] = x[at['tiny32'] if dt == 'f4' else at['tiny64'], None]
+        Bc = CSR(ncols, k, ncols * k, np.arange(ncols + 1, dtype=np.int32) * k,
+                 np.tile(np.arange(k, dtype=np.int32), ncols), B.reshape(-1).copy())
+        put(d, f'dn{c}_a_', A)
+        d[f'dn{c}_B'] = B
+        with np.errstate(all='ignore'):
+            put(d, f'dn{c}_raw_', K.mult_ab(K.to_handle(A), K.to_handle(Bc)))
+    n_dm = 4
+    d['n_dm'] = np.array(n_dm)
+    for c in range(n_dm):
+        nrows, ncols = int(rng.integers(10, 101)), int(rng.integers(10, 101))
+        nnz = int(rng.integers(nrows, 4 * nrows + 1))
+        rows = rng.integers(0, nrows, size=nnz).astype(np.int32)
+        cols = rng.integers(0, ncols, size=nnz).astype(np.int32)      # duplicates, unsorted
+        vals = rng.uniform(-4.0, 4.0, size=nnz)
+        q = rng.random(nnz)
+        vals[q < 0.2] = _nan_payloads(rng, int(np.sum(q < 0.2)))
+        vals[(q >= 0.2) & (q < 0.3)] = -0.0
+        vals[(q >= 0.3) & (q < 0.35)] = 0.0
+        vals[(q >= 0.35) & (q < 0.4)] = np.inf
+        vals[(q >= 0.4) & (q < 0.45)] = -np.inf
+        d[f'dm{c}_coo_rows'], d[f'dm{c}_coo_cols'], d[f'dm{c}_coo_vals'] = rows, cols, vals
+        m = CSR.from_coo(rows, cols, vals.copy(), (nrows, ncols))
+        put(d, f'dm{c}_', m)
+        put(d, f'dm{c}_t_', m.transpose())
+        s = CSR(m.nrows, m.ncols, m.nnz, m.rowptrs.copy(), m.colinds.copy(), m.values.copy())
+        s.sort_rows()
+        put(d, f'dm{c}_sorted_', s)
+        pick = rng.integers(0, nrows, size=int(rng.integers(1, 2 * nrows))).astype(np.int32)
+        d[f'dm{c}_pick_rows'] = pick
+        put(d, f'dm{c}_pick_', m.pick_rows(pick))
+        f = CSR(m.nrows, m.ncols, m.nnz, m.rowptrs.copy(), m.colinds.copy(), m.values.copy())
+        f._filter_zeros()
+        put(d, f'dm{c}_fz_', f)
+    save_stable(os.path.join(OUT, 'special.npz'), d)
+
+
+GENERATORS = {'kat': gen_kat, 'spmv': gen_spmv, 'cfg1_spmv': gen_cfg1, 'transpose': gen_transpose, 'rows': gen_rows,
+              'spgemm': gen_spgemm, 'shard': gen_shard, 'pick': gen_pick, 'coo': gen_coo, 'spmm_dense': gen_spmm_dense,
+              'special': gen_special}
+
+
 if __name__ == '__main__':
-    gen_kat()
-    gen_spmv()
-    gen_cfg1()
-    gen_transpose()
-    gen_rows()
-    gen_spgemm()
-    gen_shard()
-    gen_pick()
-    gen_coo()
-    gen_spmm_dense()
-    for f in sorted(os.listdir(OUT)):
+    names = sys.argv[1:] or list(GENERATORS)
+    unknown = [n for n in names if n not in GENERATORS]
+    if unknown:
+        sys.exit(f'unknown fixture(s) {unknown}; known: {sorted(GENERATORS)}')
+    for name in names:
+        GENERATORS[name]()
+        f = name + '.npz'
         print(f, os.path.getsize(os.path.join(OUT, f)))

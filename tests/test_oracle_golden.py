@@ -308,3 +308,80 @@ def test_row_parallel_variant_is_bit_identical_to_the_sequential_port():
         assert np.array_equal(O.mult_vec_rows_parallel(30000, 20000, rp, ci, vs, x, nthr), ref)
     assert np.array_equal(O.mult_vec_rows_parallel(30000, 20000, rp, ci, None, x, 4),
                           O.mult_vec(30000, 20000, rp, ci, None, x))
+
+
+def test_special_values_golden(golden):
+    """
+    The oracle on NaN, +-Inf, signed zeros and the float32 range (oracle/gen/gen_golden.py gen_special: the reference run on
+    the inputs tests/test_gpu_special_values.py feeds the library).  Products: NaN at the same positions, every other value
+    bit for bit -- the sign of every zero and infinity included.  Data movement: every bit, NaN payloads included.
+    """
+    from special_values import kind, raw_bits_equal, same_bits
+    g = golden('special')
+    y_kinds = set()
+    for c in range(int(g['n_mv'])):
+        m = Mat(g, f'mv{c}_')
+        for xk in ('x64', 'x32'):
+            x = g[f'mv{c}_{xk}']
+            with np.errstate(all='ignore'):
+                y = O.mult_vec(m.nrows, m.ncols, m.rowptrs, m.colinds, m.values, x)
+            want = g[f'mv{c}_y' + xk[1:]]
+            same_bits(y, want, f'mult_vec case {c} {xk}')
+            y_kinds |= set(kind(want).tolist())
+            assert not np.any((want == 0) & np.signbit(want)), 'the reference never sums to -0.0'
+        if m.values is not None and m.values.dtype == np.float32:
+            # float32 products overflow where float64 ones do not, and float32 subnormal products survive
+            y32, y64 = g[f'mv{c}_y32'], g[f'mv{c}_y64']
+            assert np.any(np.isposinf(y32) & np.isfinite(y64))
+            assert np.any((np.abs(y32) < np.finfo(np.float32).tiny) & (y32 != 0))
+        elif m.values is not None:
+            assert np.any((np.abs(g[f'mv{c}_y64']) < np.finfo(np.float64).tiny) & (g[f'mv{c}_y64'] != 0))
+    assert y_kinds == {0, 1, 2, 3, 5}
+    mm_kinds = set()
+    for c in range(int(g['n_mm'])):
+        A, B, Bt = Mat(g, f'mm{c}_a_'), Mat(g, f'mm{c}_b_'), Mat(g, f'mm{c}_bt_')
+        raw, rawt, ab = Mat(g, f'mm{c}_raw_'), Mat(g, f'mm{c}_rawt_'), Mat(g, f'mm{c}_ab_')
+        with np.errstate(all='ignore'):
+            nr, nc, crp, cci, cvs = O.mult_ab(A.tup(), B.tup())
+            assert np.array_equal(crp, raw.rowptrs) and np.array_equal(cci, raw.colinds), c
+            same_bits(cvs, raw.values, f'mult_ab case {c}')
+            frp, fci, fvs = O.filter_zeros(nr, crp, cci, cvs)
+            assert np.array_equal(frp, ab.rowptrs) and np.array_equal(fci, ab.colinds), c
+            same_bits(fvs, ab.values, f'multiply case {c}')
+            tnr, tnc, trp, tci, tvs = O.transpose(Bt.nrows, Bt.ncols, Bt.rowptrs, Bt.colinds, Bt.values)
+            _, _, rp2, ci2, vs2 = O.mult_ab(A.tup(), (tnr, tnc, trp, tci, tvs))
+        assert np.array_equal(rp2, rawt.rowptrs) and np.array_equal(ci2, rawt.colinds), c
+        same_bits(vs2, rawt.values, f'mult_abt case {c}')
+        mm_kinds |= set(kind(raw.values).tolist())
+        assert not np.any((raw.values == 0) & np.signbit(raw.values))
+        if A.values.dtype == B.values.dtype == np.float32:
+            assert np.any(np.isposinf(raw.values)) and np.any((np.abs(raw.values) < np.finfo(np.float32).tiny) &
+                                                               (raw.values != 0))
+    assert mm_kinds == {0, 1, 2, 3, 5}
+    for c in range(int(g['n_dn'])):
+        a, B, raw = Mat(g, f'dn{c}_a_'), g[f'dn{c}_B'], Mat(g, f'dn{c}_raw_')
+        k = B.shape[1]
+        with np.errstate(all='ignore'):
+            _, _, rp, ci, vs = O.mult_ab(a.tup(), (a.ncols, k, np.arange(a.ncols + 1, dtype=np.int32) * k,
+                                                   np.tile(np.arange(k, dtype=np.int32), a.ncols), B.reshape(-1)))
+        assert np.array_equal(rp, raw.rowptrs) and np.array_equal(ci, raw.colinds), c
+        same_bits(vs, raw.values, f'dense-B mult_ab case {c}')
+        assert {0, 1, 2, 3} <= set(kind(raw.values).tolist())
+    for c in range(int(g['n_dm'])):
+        m = Mat(g, f'dm{c}_')
+        assert np.isnan(m.values).sum() > 3 and np.any((m.values == 0) & np.signbit(m.values))
+        rp, ci, vs = O.from_coo(m.nrows, g[f'dm{c}_coo_rows'], g[f'dm{c}_coo_cols'], g[f'dm{c}_coo_vals'])
+        assert np.array_equal(rp, m.rowptrs) and np.array_equal(ci, m.colinds) and raw_bits_equal(vs, m.values)
+        t = Mat(g, f'dm{c}_t_')
+        _, _, brp, bci, bvs = O.transpose(*m.tup())
+        assert np.array_equal(brp, t.rowptrs) and np.array_equal(bci, t.colinds) and raw_bits_equal(bvs, t.values)
+        s = Mat(g, f'dm{c}_sorted_')
+        sci, svs = O.sort_rows(m.nrows, m.rowptrs, m.colinds, m.values)
+        assert np.array_equal(sci, s.colinds) and raw_bits_equal(svs, s.values)
+        p = Mat(g, f'dm{c}_pick_')
+        prp, pci, pvs = O.pick_rows(m.rowptrs, m.colinds, m.values, g[f'dm{c}_pick_rows'])
+        assert np.array_equal(prp, p.rowptrs) and np.array_equal(pci, p.colinds) and raw_bits_equal(pvs, p.values)
+        f = Mat(g, f'dm{c}_fz_')
+        frp, fci, fvs = O.filter_zeros(m.nrows, m.rowptrs, m.colinds, m.values)
+        assert np.array_equal(frp, f.rowptrs) and np.array_equal(fci, f.colinds) and raw_bits_equal(fvs, f.values)
+        assert not np.any(f.values == 0) and np.isnan(f.values).sum() == np.isnan(m.values).sum()

@@ -22,6 +22,13 @@ INTC = np.iinfo(np.intc)
 _log = logging.getLogger(__name__)
 
 
+def _topk_check(K, k, min_value, order):
+    "argument errors of topk_rows / multiply_topk, raised before any device work (the kernel's own checker when it has one)"
+    chk = getattr(K, 'topk_args', None)
+    if chk is not None:
+        chk(k, min_value, order)
+
+
 class CSR:
     """
     Compressed sparse row matrix (host arrays), drop-in for the reference's `csr.CSR` on the
@@ -347,6 +354,51 @@ class CSR:
             r0 += blk.nrows
         vals = vs[0] if len(vs) == 1 else np.concatenate(vs)
         return CSR(self.nrows, self.ncols, self.nnz, self.rowptrs.copy(), self.colinds.copy(), vals, _cast=False)
+
+    def topk_rows(self, k, *, min_value=None, order='descending'):
+        """
+        Each row's k largest entries that are not below min_value (None: no threshold) as a new CSR of the same shape:
+        best first (order='descending') or in the order they had in the row (order='storage').  NaN ranks above +Inf,
+        -0.0 ties with +0.0, ties go to the entry stored earlier; indices and values are copied bit for bit and the values
+        keep their dtype (include/csrk.h).  Runs on the device, per row block above K.max_nnz.  Not a reference entry point.
+        """
+        K, fn = self._ext('topk_rows')
+        _topk_check(K, k, min_value, order)
+        if self._values is None:
+            raise ValueError('matrix has no values')
+
+        def top(A):
+            with releasing(K.to_handle(A), K) as h:
+                with releasing(fn(h, k, min_value, order), K) as t_h:
+                    return K.from_handle(t_h)
+
+        blocks = [top(blk) for blk in self._row_blocks(K.max_nnz)]
+        return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
+
+    def multiply_topk(self, other, k, *, transpose=False, min_value=None, order='descending'):
+        """
+        self.multiply(other, transpose).topk_rows(k, min_value=min_value, order=order), array for array, with the product
+        left on the device: per row block to_handle -> mult_ab / mult_abt -> filter_zeros -> topk_rows -> from_handle, so
+        only the kept entries cross PCIe (item-kNN: each row's k most similar neighbours above a minimum similarity).
+        """
+        if transpose:
+            assert self.ncols == other.ncols
+        else:
+            assert self.ncols == other.nrows
+        K, fn = self._ext('topk_rows')
+        _topk_check(K, k, min_value, order)
+        _, dev_filter = self._ext('filter_zeros')
+
+        def mul(A, b_h):
+            with releasing(K.to_handle(A), K) as a_h:
+                with releasing(K.mult_abt(a_h, b_h) if transpose else K.mult_ab(a_h, b_h), K) as c_h:
+                    with releasing(dev_filter(c_h), K) as f_h:
+                        with releasing(fn(f_h, k, min_value, order), K) as t_h:
+                            return K.from_handle(t_h)
+
+        with releasing(K.to_handle(other), K) as b_h:
+            blocks = [mul(blk, b_h) for blk in self._row_blocks(K.max_nnz)]
+        return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
 
     def _row_blocks(self, limit):
         "the matrix itself when it fits the kernel's max_nnz, else its _shard_rows blocks"

@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -590,6 +590,44 @@ def filter_zeros(h):
     out = handle_t(0)
     _call(lib.csrk_filter_zeros, _live(h), C.byref(out))
     return _wrap(out.value)
+
+
+_TOPK_ORDERS = {'descending': _lib.TOPK_BY_VALUE, 'storage': _lib.TOPK_STORAGE}
+
+
+def topk_args(k, min_value, order):
+    "(k, min_value, order code) as the library takes them; ValueError for anything it would refuse"
+    import numbers
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise ValueError(f'k must be an integer, not {k!r}')
+    if k < 1:
+        raise ValueError(f'k must be at least 1, not {k}')
+    mv = -np.inf if min_value is None else float(min_value)
+    if mv != mv:
+        raise ValueError('min_value is NaN')
+    if order not in _TOPK_ORDERS:
+        raise ValueError(f"order must be 'descending' or 'storage', not {order!r}")
+    return min(int(k), int(max_nnz)), mv, _TOPK_ORDERS[order]
+
+
+def topk_rows(h, k, min_value=None, order='descending'):
+    """
+    Row top-k on the device: NEW handle whose rows hold each row's k largest entries that are not below min_value (None:
+    no threshold), best first (order='descending') or in the order they had in the row (order='storage').  NaN ranks
+    above +Inf, -0.0 ties with +0.0, ties go to the entry stored earlier; indices and values are copied bit for bit
+    (include/csrk.h).  Not a reference entry point.
+    """
+    k, mv, code = topk_args(k, min_value, order)
+    out = handle_t(0)
+    _call(lib.csrk_topk_rows, _live(h), k, mv, code, C.byref(out))
+    return _wrap(out.value)
+
+
+def topk_limits():
+    "(longest row ranked by one wavefront, winners a large-class workgroup orders in LDS, its threads, longest medium row)"
+    out = (C.c_int64 * 4)()
+    check(lib.csrk_topk_limits(out, 4))
+    return tuple(out)
 
 
 def values_of(h):

@@ -136,8 +136,8 @@ CSRK_API int csrk_spmv(csrk_handle_t h, const double *x, double *y);
  *     products are float64.
  *   - An output depends only on the inputs the reference's loop reads into it: a NaN or Inf in an x entry, a B / U / V row
  *     or a panel column that no product of that output uses changes nothing, not a single bit.
- *   - Data movement (transpose, order_columns, pick_rows, from_coo, filter_zeros) copies values bit for bit, NaN payloads and
- *     -0.0 included; filter_zeros drops +0.0 and -0.0 and keeps every NaN.
+ *   - Data movement (transpose, order_columns, pick_rows, from_coo, filter_zeros, topk_rows) copies values bit for bit, NaN
+ *     payloads and -0.0 included; filter_zeros drops +0.0 and -0.0 and keeps every NaN; topk_rows ranks every NaN above +Inf.
  * Deliberate difference from the reference: the sign and payload of a NaN a product creates are not specified (the
  * reference's x86 loop gives the negative default NaN, the GPU the positive one); only its position is. */
 /* The same with x given as float32 (host pointers).  Numba types the reference's loop by its operands
@@ -324,6 +324,36 @@ CSRK_API int csrk_pick_rows(csrk_handle_t h, const int32_t *rows, int64_t n_rows
  * csr/_struct.py:61-76.  Returns a NEW handle without the entries whose value is
  * exactly 0.0 (NaN is kept).  Requires float64 values.                                  */
 CSRK_API int csrk_filter_zeros(csrk_handle_t h, csrk_handle_t *out);
+
+/* ---- row top-k: keep each row's k largest entries ------------------------------------------
+ * Not a reference entry point: the step a caller of mult_abt (item-kNN: each row's N most similar neighbours above a
+ * minimum similarity) or of SDDMM (each user's N best candidates) takes next, on the device, so that only the kept entries
+ * cross PCIe.  Returns a NEW handle of h's shape whose row i holds the kept entries of row i of h:
+ *   1. An entry PASSES unless value < min_value: NaN passes, -0.0 passes min_value = 0.0; min_value = -INFINITY is no
+ *      threshold.
+ *   2. Of a row's passing entries the first k in this total order are kept: larger value first; NaN (any sign, any
+ *      payload) ranks above +Inf and all NaNs tie; -0.0 and +0.0 tie; ties go to the entry stored earlier in the row
+ *      (the order torch.topk / a reversed np.sort give to values, made a function of the input by the tie rule).  A row
+ *      with fewer than k passing entries keeps them all.
+ *   3. order = CSRK_TOPK_BY_VALUE: the kept entries are written in that rank order, best first.  order = CSRK_TOPK_STORAGE:
+ *      the same entries in the order they had in the input row (a column-sorted matrix stays column-sorted).
+ *   4. Column indices and values are copied bit for bit (NaN payloads, -0.0, float32 subnormals); values keep their dtype.
+ *      Unsorted and repeated columns are just more entries.
+ *   5. Row pointers are int32 unless the result holds more than 2^31 - 1 entries, whatever the input's pointer width (the
+ *      layout rule of csr/csr.py:88-93, as csrk_pick_rows).
+ *   6. h is not modified and keeps its plans.  CSRK_ERR_INVALID for k < 1, a NaN min_value, an unknown order, or a
+ *      structure-only h (no values to rank: the refusal of csrk_unit_rows).  nrows = 0 or nnz = 0: CSRK_OK, an empty result,
+ *      nothing launched.  k may exceed every row length (then only rule 1 filters, and `order` still applies).
+ *   7. The result depends on (h, k, min_value, order) only: not on launch geometry, repeated calls, the pointer width or what
+ *      else the matrix holds (csrc/topk.hip: ranks and slots are counted, never appended in arrival order).
+ * A row of more than 2^31 - 1 entries is CSRK_ERR_UNSUPPORTED. */
+enum { CSRK_TOPK_BY_VALUE = 0, CSRK_TOPK_STORAGE = 1 };
+CSRK_API int csrk_topk_rows(csrk_handle_t h, int64_t k, double min_value, int order, csrk_handle_t *out);
+/* Diagnostics: the row classes of csrk_topk_rows: out[0] = the longest row one wavefront ranks, [1] = the candidates /
+ * winners a large-class workgroup holds in LDS (more winners than that in by-value order are ordered in device memory),
+ * [2] = its threads, [3] = the longest row of the medium class (a smaller workgroup, the whole row in LDS);  n <= 4.
+ * No device is touched. */
+CSRK_API int csrk_topk_limits(int64_t *out, int n);
 
 #ifdef __cplusplus
 }

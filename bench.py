@@ -3,7 +3,13 @@
 Headline benchmark: fp64 SpMV (the reference's mult_vec, csr/kernels/numba/__init__.py:55-67)
 on a 10M x 10M power-law CSR with nnz = 2e8, through the libcsrk C ABI on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing more: it generates the matrix, builds the plan, warms up, times
+the K steps, writes --dump-outputs and prints the result line.  `--full` adds everything else the benchmark measures or
+checks, after the timed steps: `cpu_baseline` with the full-size `parity` check, `roofline.without_a_plan` and the
+`secondary` block (26 s instead of 3-4 for the whole run on one GPU); `--no-cpu-baseline` and `--no-secondary` leave one of them out of
+a full run.
 
 N = 1 runs in-process; for N > 1 the driver launches one rank per GPU
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`) -- or, started plainly as
@@ -31,7 +37,7 @@ One JSON line is printed by rank 0:
              `hbm_gbs_end_to_end` is 2.60 GB / step time;
              peak = 8000 GB/s (HBM3E spec); traffic = per-launch HBM bytes from the committed
              rocprofv3 PMC summary (profiles/), or null;
-  cpu_baseline  the oracle's sequential restatement of the reference loop (oracle/csr_oracle.c,
+  cpu_baseline  (--full) the oracle's sequential restatement of the reference loop (oracle/csr_oracle.c,
              kind "port", 1 core) timed on this host on the same matrix, plus a full-size
              parity check of the GPU result against it.
 """
@@ -64,9 +70,12 @@ def parse():
     ap.add_argument('--force-dist', action='store_true',
                     help='run the N > 1 code path (process group on RCCL, exchange candidates, completeness checks) whatever N is: '
                          'with --gpus 1 it is the one-rank rehearsal of the multi-GPU run (tests/test_gpu_fullsize.py)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check what the headline figure does not need: the CPU baseline '
+                         'with the full-size parity check, the product without a plan and the `secondary` block')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline and the parity check')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='N = 1: skip the `secondary` block (SpMM configs[2], transpose + A B^T configs[4], unit_rows on the '
+                    help='--full, N = 1: skip the `secondary` block (SpMM configs[2], transpose + A B^T configs[4], unit_rows on the '
                          'headline matrix: bench_secondary.py), which adds ~30 s after the SpMV has been timed')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='CPU baseline time budget')
     ap.add_argument('--secondary-seconds', type=float, default=240.0, help='N = 1: time limit of the secondary block (a child process)')
@@ -520,6 +529,7 @@ def main():
         'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
         'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64',
         'data': 'synthetic',
+        'full': bool(args.full),      # False: the blocks of --full (cpu_baseline, parity, roofline.without_a_plan, secondary) are absent
         'config': {'workload': workload, 'nrows': nrows, 'ncols': ncols, 'nnz': nnz,
                    'row_degree': f'power-law alpha={args.alpha}, max {int(min(1_000_000, ncols // 8))}',
                    'columns': 'Zipf(1.0) popularity over a permuted column space, distinct+sorted per row',
@@ -569,7 +579,7 @@ def main():
             torch.cuda.synchronize()
             out['multi_gpu']['y_equals_plain_product_bitwise'] = bool(torch.equal(y.view(torch.int64), y_plain.view(torch.int64)))
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O       # the checker / baseline, never the thing measured above
         rp_h, ci_h, vs_h = rp.cpu().numpy(), ci.cpu().numpy(), vs.cpu().numpy()
         x_h = x.cpu().numpy()
@@ -634,7 +644,7 @@ def main():
     for hc in op_handles:
         check(lib.csrk_free(hc))
     check(lib.csrk_free(h))
-    if world == 1 and not distd:
+    if args.full and world == 1 and not distd:
         # What a caller WITHOUT a kept handle gets (the reference makes one per product, csr/csr.py:580-583): the first
         # product on a fresh handle runs the plan-less merge-path kernel over the CSR arrays as they are.  Timed here on a
         # second handle over the same resident arrays (kernels already loaded), outside the timed region.
@@ -667,7 +677,7 @@ def main():
             'plan_build_call_ms_from_the_pool': round(plan2_ms, 2),
             'planned_products_to_amortise_it_from_the_pool': None if pl_ms <= ms_per_step else
             int(np.ceil(plan2_ms / (pl_ms - ms_per_step)))}
-    if world == 1 and not distd and not args.no_secondary and args.scale == 1.0:
+    if args.full and world == 1 and not distd and not args.no_secondary and args.scale == 1.0:
         # the other BASELINE configs, AFTER the SpMV has been timed and checked (nothing above depends on this):
         # each entry carries ms, algorithmic bytes, frac of 8 TB/s, a parity flag and the oracle's time on a stated sample
         # (a Python error anywhere in here must not cost the line that has been timed and verified above)

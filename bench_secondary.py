@@ -2,8 +2,8 @@
 The other BASELINE.json configurations, measured the way bench.py measures the headline SpMV: through the libcsrk
 C ABI with inputs resident in HBM, each with its algorithmic bytes, the fraction of the 8 TB/s
 roofline, a parity flag against the CPU oracle, and the oracle timed on a stated sample as `cpu_baseline` (kind
-"port", 1 core).  bench.py puts the dicts these functions return into the `secondary` block of its JSON line
-(`--no-secondary` skips it); tools/bench_configs.py prints the same dicts one per line for profiles/rNN_configs.json.
+"port", 1 core).  `bench.py --full` puts the dicts these functions return into the `secondary` block of its JSON line
+(`--no-secondary` leaves it out); tools/bench_configs.py prints the same dicts one per line for profiles/rNN_configs.json.
 
   spmm       configs[2]: dense-panel SpMM, A 2M x 2M nnz 5e7 (power-law) x B 2M x 64 f64 (csrk_spmm_dense_device;
              reference: mult_ab with a fully populated B, csr/kernels/numba/multiply.py:13-38, 110-122)

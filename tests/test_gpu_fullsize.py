@@ -302,6 +302,35 @@ def test_bench_one_rank_on_rccl(collective):
         assert mg['exchange'] == collective
 
 
+@pytest.mark.parametrize('full', [False, True])
+def test_bench_full_option_gates_everything_but_the_headline(full):
+    """
+    A plain `python bench.py --gpus 1 --steps K --warmup W` prints the headline line and nothing that takes a run of its
+    own; `--full` adds the CPU baseline with its parity check and the product without a plan (the `secondary` block runs at
+    the full size only, so it is not started at this scale).  The headline fields are there either way.
+    """
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'BENCH_TEST_SHARE_GPU')}
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--scale', '0.05']
+    cmd += ['--full', '--cpu-seconds', '0.5'] if full else []
+    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    assert d['metric'] == 'spmv_gflops' and d['unit'] == 'GFLOP/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['value'] > 0 and d['ms_per_step'] > 0
+    assert d['full'] is full and d['setup_check']['ok'] is True and d['roofline']['all_kernels']
+    assert 'secondary' not in d
+    if full:
+        assert d['cpu_baseline']['value'] > 0 and d['parity']['ok'] is True
+        assert d['roofline']['without_a_plan']['ms'] > 0
+    else:
+        assert 'cpu_baseline' not in d and 'parity' not in d and 'without_a_plan' not in d['roofline']
+
+
 def test_bench_refuses_more_ranks_than_gpus():
     "`python bench.py --gpus 8` on a box with fewer GPUs: a clear message and a non-zero exit, before anything is launched"
     import os

@@ -508,53 +508,14 @@ __global__ __launch_bounds__(PT) void spmv_panel_kernel(
 #undef PANEL_LOAD_TILE
 }
 
-// a lane's eight values of a tile: float64 four 16-B loads, float32 (a float32 matrix's stream) two, widened on use
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <class SV> struct AccVals;
-template <> struct AccVals<double> {
-    f64x2_t v[4];
-    __device__ __forceinline__ void load(const double *tile, int lane)
-    {
-        const f64x2_t *vp = (const f64x2_t *)tile;
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = __builtin_nontemporal_load(vp + q * WAVE + lane);
-    }
-    __device__ __forceinline__ void get(double (&a)[ACC_K]) const
-    {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            a[2 * q] = v[q].x;
-            a[2 * q + 1] = v[q].y;
-        }
-    }
-};
-template <> struct AccVals<float> {
-    f32x4_t v[2];
-    __device__ __forceinline__ void load(const float *tile, int lane)
-    {
-        const f32x4_t *vp = (const f32x4_t *)tile;
-#pragma unroll
-        for (int q = 0; q < 2; q++) v[q] = __builtin_nontemporal_load(vp + q * WAVE + lane);
-    }
-    __device__ __forceinline__ void get(double (&a)[ACC_K]) const
-    {
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            a[4 * q] = (double)v[q].x;
-            a[4 * q + 1] = (double)v[q].y;
-            a[4 * q + 2] = (double)v[q].z;
-            a[4 * q + 3] = (double)v[q].w;
-        }
-    }
-};
-
 template <int CB, int PT, bool R32 = false, class SV = double, class XT = double>
 __global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pvals, const uint16_t *__restrict__ pidx,
                                                      const int32_t *__restrict__ tile_row0,
                                                      const XT *__restrict__ x, int32_t ncols,
                                                      const AccSeg *__restrict__ segs, const int32_t *__restrict__ wg_seg,
-                                                     int32_t H, double *__restrict__ partial)
+                                                     int32_t H, double *__restrict__ partial, int32_t fx_g)
 {
+    // fx_g: the grid exponent of a fix56 stream's values (SV = fix56::Packed; the other streams ignore it)
     extern __shared__ __align__(16) unsigned char acc_smem[];
     double *s_x = (double *)acc_smem;                     // CB + 2 (slot CB = 0.0 for padding entries)
     double *s_acc = s_x + CB + 2;                         // Hpad
@@ -622,7 +583,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pva
             const uint32_t e[ACC_K] = {ix.x & 0xffffu, ix.x >> 16, ix.y & 0xffffu, ix.y >> 16,
                                        ix.z & 0xffffu, ix.z >> 16, ix.w & 0xffffu, ix.w >> 16};
             double a[ACC_K];
-            v.get(a);
+            v.get(a, fx_g);
             double xv[ACC_K];
 #pragma unroll
             for (int j = 0; j < ACC_K; j++) xv[j] = s_x[e[j] & ACC_COL_MASK];
@@ -1307,7 +1268,11 @@ int spmv_kernel_attributes()
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, double, float>,
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, double, float>,
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, float, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, float, float>})
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, float, float>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed, float>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed, float>})
         CSRK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
@@ -1442,14 +1407,14 @@ static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipSt
         if (do_heavy && p->n_heavy && !p->acc.empty()) {        // tier 0, accumulator form
             KernelTimer kh(p, s, 1);
             for (AccPanel *ap : p->acc) {
-                if (ap->f32)
-                    spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, float, XT><<<(unsigned)ap->n_wg, ACC_THREADS, ap->lds, s>>>(
-                        ap->vals.as<float>(), ap->idx.as<uint16_t>(), ap->tile_row0.as<int32_t>(), d_x, m->ncols,
-                        ap->segs.as<AccSeg>(), ap->wg_seg.as<int32_t>(), ap->nrow, ap->partial.as<double>());
-                else
-                    spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, double, XT><<<(unsigned)ap->n_wg, ACC_THREADS, ap->lds, s>>>(
-                        ap->vals.as<double>(), ap->idx.as<uint16_t>(), ap->tile_row0.as<int32_t>(), d_x, m->ncols,
-                        ap->segs.as<AccSeg>(), ap->wg_seg.as<int32_t>(), ap->nrow, ap->partial.as<double>());
+#define ACC_LAUNCH(SV)                                                                                                 \
+    spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, SV, XT><<<(unsigned)ap->n_wg, ACC_THREADS, ap->lds, s>>>(                \
+        ap->vals.as<SV>(), ap->idx.as<uint16_t>(), ap->tile_row0.as<int32_t>(), d_x, m->ncols, ap->segs.as<AccSeg>(),  \
+        ap->wg_seg.as<int32_t>(), ap->nrow, ap->partial.as<double>(), ap->fx_g)
+                if (ap->f32) ACC_LAUNCH(float);
+                else if (ap->fix56) ACC_LAUNCH(fix56::Packed);
+                else ACC_LAUNCH(double);
+#undef ACC_LAUNCH
                 CSRK_LAUNCH_CHECK();
             }
             kh.stop();

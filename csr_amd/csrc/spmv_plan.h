@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "wave.h"
+#include "fix56.h"
 
 #include <vector>
 
@@ -80,6 +81,10 @@ struct AccPanel {
     DevBuf row_list, vals, idx, tile_row0, segs, wg_seg, partial;      // idx: 16-bit words (column, row step)
     DevBuf z;              // double[nrow]: the rows' sums when the reduce rides in the pair kernel's launch (PanelRider)
     bool f32 = false;      // vals holds float32 (a float32 matrix: 6 B per entry instead of 10; widening them in the kernel is exact)
+    // vals holds fix56 tiles (fix56.h: the group's float64 values lie on the grid 2^fx_g; 9 B per entry instead of 10, decoded
+    // exactly): chosen per group at plan time, checked there entry by entry against the source, CSRK_SPMV_FIX56=0 forbids it
+    bool fix56 = false;
+    int32_t fx_g = 0;
 };
 
 // A light stream (see "short rows: the light stream"): a private tiled copy of a set of rows ("runs") plus
@@ -299,6 +304,78 @@ template <class SV> __host__ __device__ __forceinline__ int acc_slot_of(int e)
 {
     return sizeof(SV) == 8 ? acc_val_slot(e) : acc_idx_slot(e);
 }
+
+// a lane's eight values of a tile: float64 four 16-B loads, float32 (a float32 matrix's stream) two, widened on use; get(a, g): g is
+// the grid exponent of a fix56 tile (the other forms ignore it)
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+template <class SV> struct AccVals;
+template <> struct AccVals<double> {
+    f64x2_t v[4];
+    __device__ __forceinline__ void load(const double *tile, int lane)
+    {
+        const f64x2_t *vp = (const f64x2_t *)tile;
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = __builtin_nontemporal_load(vp + q * WAVE + lane);
+    }
+    __device__ __forceinline__ void get(double (&a)[ACC_K], int32_t = 0) const
+    {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            a[2 * q] = v[q].x;
+            a[2 * q + 1] = v[q].y;
+        }
+    }
+};
+template <> struct AccVals<float> {
+    f32x4_t v[2];
+    __device__ __forceinline__ void load(const float *tile, int lane)
+    {
+        const f32x4_t *vp = (const f32x4_t *)tile;
+#pragma unroll
+        for (int q = 0; q < 2; q++) v[q] = __builtin_nontemporal_load(vp + q * WAVE + lane);
+    }
+    __device__ __forceinline__ void get(double (&a)[ACC_K], int32_t = 0) const
+    {
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            a[4 * q] = (double)v[q].x;
+            a[4 * q + 1] = (double)v[q].y;
+            a[4 * q + 2] = (double)v[q].z;
+            a[4 * q + 3] = (double)v[q].w;
+        }
+    }
+};
+// float64 values on one binary grid in 7 bytes (fix56.h): per tile a 32-bit plane (a lane's eight words: two 16-B loads), a
+// 16-bit plane (one 16-B load) and an 8-bit plane (one 8-B load) -- as many load instructions as the float64 tile, 3584 B
+// instead of 4096.  get(): word j = {0, byte j of the 8-bit plane, half j of the 16-bit plane} by one v_perm_b32 (as LS_RND24
+// assembles its index words), then fix56::decode -- and-or, one v_add_f64 against 2^(52 + g), the sign xor-ed in: exact, so
+// what the kernel multiplies is bit for bit what the float64 tile holds.
+static_assert(fix56::TILE == ACC_TILE, "fix56 tiles are the streams' tiles");
+template <> struct AccVals<fix56::Packed> {
+    u32x4_t lo[2], mid;
+    u32x2_t hi;
+    __device__ __forceinline__ void load(const fix56::Packed *tile, int lane)
+    {
+        const unsigned char *tp = (const unsigned char *)tile;
+#pragma unroll
+        for (int q = 0; q < 2; q++) lo[q] = __builtin_nontemporal_load((const u32x4_t *)tp + q * WAVE + lane);
+        mid = __builtin_nontemporal_load((const u32x4_t *)(tp + fix56::MID_OFF) + lane);
+        hi = __builtin_nontemporal_load((const u32x2_t *)(tp + fix56::HI_OFF) + lane);
+    }
+    __device__ __forceinline__ void get(double (&a)[ACC_K], int32_t g) const
+    {
+        const uint32_t l[ACC_K] = {lo[0].x, lo[0].y, lo[0].z, lo[0].w, lo[1].x, lo[1].y, lo[1].z, lo[1].w};
+        const uint32_t m[4] = {mid.x, mid.y, mid.z, mid.w}, h[2] = {hi.x, hi.y};
+        const uint32_t ebits = fix56::ebits_of(g);
+        const double magic = fix56::magic_of(g);
+#pragma unroll
+        for (int j = 0; j < ACC_K; j++) {
+            const uint32_t w = __builtin_amdgcn_perm(h[j >> 2], m[j >> 1],
+                                                     0x0c000000u | ((4u + (j & 3)) << 16) | ((2u * (j & 1) + 1u) << 8) | (2u * (j & 1)));
+            a[j] = fix56::decode(l[j], w, ebits, magic);
+        }
+    }
+};
 
 // The merge-path tile kernel spends ~600 vector instructions per wavefront-tile on index arithmetic (clamped
 // 64-bit addresses, merge coordinates, the cut table) and four dependent memory round trips per 2048-item

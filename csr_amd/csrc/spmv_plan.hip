@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 #include <ctime>
+#include <type_traits>
 
 namespace csrk {
 // tile_row[t] = number of row ends consumed before merge-path diagonal d = min(t*ITEMS, nrows+nnz).
@@ -599,13 +600,65 @@ __device__ __forceinline__ int64_t acc_phys_tile(int64_t t, const int64_t *__res
     return (t - wg_t0[w]) * n_wg + w;
 }
 
+// The grid test of a group's values (fix56.h): bad flag, lowest and highest set bit over the entries of the listed rows, into
+// out[0..2] (preset to 0, INT32_MAX, INT32_MIN).  blockIdx.x = the row, whose entries gridDim.y workgroups share.
+template <class P>
+__global__ __launch_bounds__(256) void acc_range_kernel(const P *__restrict__ rp, const double *__restrict__ vs,
+                                                       const int32_t *__restrict__ rows, int32_t *__restrict__ out)
+{
+    const int32_t row = rows[blockIdx.x];
+    const int64_t k1 = (int64_t)rp[row + 1];
+    fix56::Range r;
+    for (int64_t k = (int64_t)rp[row] + blockIdx.y * 256 + threadIdx.x; k < k1; k += (int64_t)gridDim.y * 256) fix56::fold(r, vs[k]);
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        fix56::Range o;
+        o.bad = __shfl_xor(r.bad, off, WAVE);
+        o.lo = __shfl_xor(r.lo, off, WAVE);
+        o.hi = __shfl_xor(r.hi, off, WAVE);
+        fix56::merge(r, o);
+    }
+    // a wavefront's atomics only where they would change the result so far (a stale look costs an atomic, never the result):
+    // unconditional, the headline matrix's 250 k wavefronts queued 19 ms on these three words
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        const volatile int32_t *seen = out;
+        if (r.bad && !seen[0]) atomicOr(out, 1);
+        if (r.lo < seen[1]) atomicMin(out + 1, r.lo);
+        if (r.hi > seen[2]) atomicMax(out + 2, r.hi);
+    }
+}
+
+// One value of tier 0's stream: stored by the fill kernels -- or, VERIFY (fix56 tiles only), read back from the finished tile
+// by the routine the product kernel uses (AccVals: the loads of lane el / 8, its decode) and compared with the source bit for
+// bit.
+template <class SV, bool VERIFY>
+__device__ __forceinline__ void acc_put(SV *__restrict__ pvals, int64_t pt, int el, double v, int32_t fx_g,
+                                        int32_t *__restrict__ mismatch)
+{
+    if constexpr (!std::is_same<SV, fix56::Packed>::value) {
+        pvals[pt * ACC_TILE + acc_slot_of<SV>(el)] = (SV)v;
+    } else if constexpr (!VERIFY) {
+        fix56::put((unsigned char *)(pvals + pt * ACC_TILE), el, fix56::encode(v, fx_g));
+    } else {
+        AccVals<SV> t;
+        t.load(pvals + pt * ACC_TILE, el >> 3);
+        double a[ACC_K];
+        t.get(a, fx_g);
+        double d = a[0];
+#pragma unroll
+        for (int j = 1; j < ACC_K; j++) d = (el & 7) == j ? a[j] : d;
+        if (fix56::bits_of(d) != fix56::bits_of(v)) *mismatch = 1;
+    }
+}
+
 // One wavefront per 64 consecutive (block, heavy row) pairs of ONE block: their slots are one contiguous range of the
 // block's logical stream, walked 64 slots at a time -- a slot finds its pair by bisection in the wavefront's own table of
 // pair starts, a padding slot (the first ones of a pair whose row lies more than ACC_MAXSTEP rows after the previous one)
 // writes (0.0, zero slot, step 7), the others copy the pair's entries -- so the stream is written by consecutive lanes and
 // every lane works.  (A thread per pair walking its 3.6 entries one after the other wrote and read 64 scattered lines
 // per instruction: 6.9 ms of the headline matrix's plan, its largest item; this form 2.7.)
-template <class P, int VT, class SV>
+// VERIFY: the same walk writes nothing and checks the values of a finished fix56 stream instead (acc_put).
+template <class P, int VT, class SV, bool VERIFY = false>
 __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp, const int32_t *__restrict__ ci,
                                                       const void *__restrict__ vs, const int32_t *__restrict__ heavy_row,
                                                       int32_t n_heavy, int32_t n_blocks, int32_t cb,
@@ -613,7 +666,8 @@ __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp,
                                                       const int32_t *__restrict__ pstart, const int32_t *__restrict__ gap,
                                                       SV *__restrict__ pvals, uint16_t *__restrict__ pidx,
                                                       int32_t *__restrict__ tile_row0, const int64_t *__restrict__ wg_t0,
-                                                      int32_t n_wg, int32_t waves_per_block)
+                                                      int32_t n_wg, int32_t waves_per_block, int32_t fx_g,
+                                                      int32_t *__restrict__ mismatch)
 {
     __shared__ int32_t s_start[256 / WAVE][WAVE];
     const int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
@@ -656,14 +710,16 @@ __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp,
         const int el = (int)(L % ACC_TILE);
         const int64_t pt = acc_phys_tile(t, wg_t0, n_wg);
         if (at < npad_p) {                           // padding entry k = at + 1 stands on heavy row c - g + 7k
-            pvals[pt * ACC_TILE + acc_slot_of<SV>(el)] = (SV)0.0;
+            acc_put<SV, VERIFY>(pvals, pt, el, 0.0, fx_g, mismatch);
+            if (VERIFY) continue;
             pidx[pt * ACC_TILE + el] = (uint16_t)((uint32_t)cb | ((el ? (uint32_t)ACC_MAXSTEP : 0u) << ACC_ROW_SHIFT));
             if (el == 0) tile_row0[t] = c0 + p - g_p + ACC_MAXSTEP * (at + 1);
         } else {
             const int64_t k = lo_p + (at - npad_p);
             // the pair's first entry: the step from the previous row (or the last padding entry) to this row
             const uint32_t step_in = at == npad_p ? (uint32_t)(g_p - ACC_MAXSTEP * npad_p) : 0u;
-            pvals[pt * ACC_TILE + acc_slot_of<SV>(el)] = (SV)ValLoad<VT>::at(vs, k);
+            acc_put<SV, VERIFY>(pvals, pt, el, ValLoad<VT>::at(vs, k), fx_g, mismatch);
+            if (VERIFY) continue;
             pidx[pt * ACC_TILE + el] = (uint16_t)((uint32_t)(ci[k] - b * cb) | ((el ? step_in : 0u) << ACC_ROW_SHIFT));
             if (el == 0) tile_row0[t] = c0 + p;
         }
@@ -672,10 +728,11 @@ __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp,
 
 // one workgroup per block: pads the block's last tile with (0.0, column slot ACC_CB (a zero in LDS), step 0 = the
 // block's last heavy row) -- a padding entry adds 0.0 * 0.0 to an accumulator
-template <class SV>
+template <class SV, bool VERIFY = false>
 __global__ __launch_bounds__(256) void acc_pad_kernel(const int64_t *__restrict__ off, int32_t n_heavy, int32_t n_blocks,
                                                      const int64_t *__restrict__ blk_tile0, SV *__restrict__ pvals,
-                                                     uint16_t *__restrict__ pidx, const int64_t *__restrict__ wg_t0, int32_t n_wg)
+                                                     uint16_t *__restrict__ pidx, const int64_t *__restrict__ wg_t0, int32_t n_wg,
+                                                     int32_t fx_g, int32_t *__restrict__ mismatch)
 {
     const int32_t b = blockIdx.x;
     if (b >= n_blocks) return;
@@ -684,8 +741,8 @@ __global__ __launch_bounds__(256) void acc_pad_kernel(const int64_t *__restrict_
     for (int64_t L = L0 + threadIdx.x; L < L1; L += blockDim.x) {      // (the tail of the block's last tile: one tile)
         const int64_t pt = acc_phys_tile(L / ACC_TILE, wg_t0, n_wg);
         const int el = (int)(L % ACC_TILE);
-        pvals[pt * ACC_TILE + acc_slot_of<SV>(el)] = (SV)0.0;
-        pidx[pt * ACC_TILE + el] = (uint16_t)ACC_CB;
+        acc_put<SV, VERIFY>(pvals, pt, el, 0.0, fx_g, mismatch);
+        if (!VERIFY) pidx[pt * ACC_TILE + el] = (uint16_t)ACC_CB;
     }
 }
 
@@ -1030,25 +1087,68 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     CSRK_TRY(stage_h2d(d_wg_t0.p, wg_t0.data(), (size_t)(n_wg + 1) * 8, s));
     // a float32 matrix keeps float32 values in the stream (6 B per entry; widened in the kernel, exactly)
     ap->f32 = VT == CSRK_VAL_F32;
-    CSRK_TRY(ap->vals.alloc((size_t)n_phys * ACC_TILE * (ap->f32 ? 4 : 8)));
+    // float64 values that lie on one binary grid are kept in 7 bytes (fix56.h: 9 B per entry; decoded exactly).  One switch for
+    // the whole group: the grid test over its values, and CSRK_SPMV_FIX56=0 forbids the form (tests, measurements)
+    DevBuf fx;      // int32[4]: the grid test's bad flag, lowest and highest set bit; the verification's mismatch flag
+    CSRK_TRY(fx.alloc(16));
+    if (VT == CSRK_VAL_F64 && n > 0) {
+        const char *env = getenv("CSRK_SPMV_FIX56");
+        if (!(env && env[0] == '0')) {
+            int32_t h[4] = {0, INT32_MAX, INT32_MIN, 0};
+            CSRK_TRY(stage_h2d(fx.p, h, sizeof h, s));
+            acc_range_kernel<P><<<dim3((unsigned)n, 16), 256, 0, s>>>(rp, (const double *)m->d_values, ap->row_list.as<int32_t>(),
+                                                                     fx.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            CSRK_TRY(stage_d2h(h, fx.p, sizeof h, s));
+            CSRK_HIP(hipStreamSynchronize(s));
+            fix56::Range r;
+            r.bad = h[0];
+            r.lo = h[1];
+            r.hi = h[2];
+            ap->fix56 = fix56::packable(r, ap->fx_g);
+            tr.lap("  tier 0: value grid test");
+        }
+    }
     CSRK_TRY(ap->idx.alloc((size_t)n_phys * ACC_TILE * 2));
     CSRK_TRY(ap->tile_row0.alloc((size_t)(n_tiles ? n_tiles : 1) * 4));
     const int32_t fill_waves = (int32_t)ceil_div(n, WAVE);      // wavefronts per block: 64 pairs each
-#define ACC_FILL(SV)                                                                                                   \
+#define ACC_FILL(SV, VERIFY)                                                                                           \
     do {                                                                                                               \
-        acc_fill_kernel<P, VT, SV><<<(unsigned)ceil_div((int64_t)nb * fill_waves * WAVE, 256), 256, 0, s>>>(           \
+        acc_fill_kernel<P, VT, SV, VERIFY><<<(unsigned)ceil_div((int64_t)nb * fill_waves * WAVE, 256), 256, 0, s>>>(   \
             rp, m->d_colinds, m->d_values, ap->row_list.as<int32_t>(), n, nb, ACC_CB, off.as<int64_t>(),               \
             bends.as<int64_t>(), pstart.as<int32_t>(), gap.as<int32_t>(), ap->vals.as<SV>(), ap->idx.as<uint16_t>(),   \
-            ap->tile_row0.as<int32_t>(), d_wg_t0.as<int64_t>(), (int32_t)n_wg, fill_waves);                            \
+            ap->tile_row0.as<int32_t>(), d_wg_t0.as<int64_t>(), (int32_t)n_wg, fill_waves, ap->fx_g,                   \
+            fx.as<int32_t>() + 3);                                                                                     \
         CSRK_LAUNCH_CHECK();                                                                                           \
-        acc_pad_kernel<SV><<<(unsigned)nb, 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>(), ap->vals.as<SV>(), \
-                                                        ap->idx.as<uint16_t>(), d_wg_t0.as<int64_t>(), (int32_t)n_wg); \
+        acc_pad_kernel<SV, VERIFY><<<(unsigned)nb, 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>(),         \
+                                                                ap->vals.as<SV>(), ap->idx.as<uint16_t>(),             \
+                                                                d_wg_t0.as<int64_t>(), (int32_t)n_wg, ap->fx_g,        \
+                                                                fx.as<int32_t>() + 3);                                 \
         CSRK_LAUNCH_CHECK();                                                                                           \
     } while (0)
-    if (ap->f32) ACC_FILL(float);
-    else ACC_FILL(double);
+    if (ap->fix56) {
+        CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::TILE_BYTES));
+        ACC_FILL(fix56::Packed, false);
+        tr.lap("  tier 0: fill (fix56)");
+        // the library's own proof of "exact", on every plan: every stored entry decoded as the product decodes it, against
+        // the source; a single mismatch and the group is rebuilt raw
+        int32_t mismatch = 1;
+        ACC_FILL(fix56::Packed, true);
+        CSRK_TRY(stage_d2h(&mismatch, fx.as<int32_t>() + 3, 4, s));
+        CSRK_HIP(hipStreamSynchronize(s));
+        tr.lap("  tier 0: verify (fix56)");
+        if (mismatch) {
+            ap->fix56 = false;
+            ap->fx_g = 0;
+        }
+    }
+    if (!ap->fix56) {
+        CSRK_TRY(ap->vals.alloc((size_t)n_phys * ACC_TILE * (ap->f32 ? 4 : 8)));
+        if (ap->f32) ACC_FILL(float, false);
+        else ACC_FILL(double, false);
+        tr.lap("  tier 0: fill");
+    }
 #undef ACC_FILL
-    tr.lap("  tier 0: fill");
     std::vector<AccSeg> segs;
     std::vector<int32_t> wg_seg((size_t)n_wg + 1);
     int32_t b = 0;

@@ -15,6 +15,7 @@ ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_OVERFLOW = -1, -2, -3, -4
 VAL_NONE, VAL_F32, VAL_F64 = 0, 1, 2
 SPMV_AUTO, SPMV_MERGE, SPMV_VECTOR, SPMV_SCALAR = 0, 1, 2, 3
 TOPK_BY_VALUE, TOPK_STORAGE = 0, 1
+COMBINE_ADD, COMBINE_MUL, COMBINE_KEEP, COMBINE_DROP = 0, 1, 2, 3
 
 
 class CsrkError(RuntimeError):
@@ -101,6 +102,8 @@ SIGNATURES = {
     'csrk_pick_rows': (_int, [handle_t, C.c_void_p, C.c_int64, C.c_int, C.POINTER(handle_t)]),
     'csrk_topk_rows': (_int, [handle_t, _i64, C.c_double, _int, C.POINTER(handle_t)]),
     'csrk_topk_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_combine': (_int, [handle_t, handle_t, _int, C.c_double, C.c_double, C.POINTER(handle_t)]),
+    'csrk_combine_limits': (_int, [C.POINTER(_i64), _int]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

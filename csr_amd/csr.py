@@ -375,11 +375,72 @@ class CSR:
         blocks = [top(blk) for blk in self._row_blocks(K.max_nnz)]
         return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
 
-    def multiply_topk(self, other, k, *, transpose=False, min_value=None, order='descending'):
+    # ---- two matrices entry by entry -----------------------------------------------------------
+    def _combine(self, other, op, alpha=1.0, beta=1.0):
+        """
+        to_handle x 2 -> combine -> from_handle.  Above K.max_nnz both operands are cut at the same row boundaries (the
+        union of their own _shard_cuts, so that every block fits for both) and the blocks' results are stacked.
+        """
+        K, fn = self._ext('combine')
+        chk = getattr(K, 'combine_args', None)
+        if chk is not None:
+            chk(self, other, op, alpha, beta)
+        if (self.nrows, self.ncols) != (other.nrows, other.ncols):
+            raise ValueError(f'operands of different shapes: {self.nrows} x {self.ncols} and {other.nrows} x {other.ncols}')
+
+        def comb(A, B):
+            with releasing(K.to_handle(A), K) as a_h:
+                if B is A:                           # one device copy serves both sides
+                    with releasing(fn(a_h, a_h, op, alpha, beta), K) as c_h:
+                        return K.from_handle(c_h)
+                with releasing(K.to_handle(B), K) as b_h:
+                    with releasing(fn(a_h, b_h, op, alpha, beta), K) as c_h:
+                        return K.from_handle(c_h)
+
+        if max(self.nnz, other.nnz) <= K.max_nnz:
+            return comb(self, other)
+        cuts = sorted(set(self._shard_cuts(K.max_nnz)) | set(other._shard_cuts(K.max_nnz)))
+        blocks = [comb(self.subset_rows(a, b), other.subset_rows(a, b)) for a, b in zip(cuts[:-1], cuts[1:])]
+        return CSR._assemble_shards(blocks)
+
+    def add(self, other, alpha=1.0, beta=1.0):
+        """
+        alpha * self + beta * other over the union of the two patterns, as a new CSR with float64 values and rows ascending
+        in column.  Both matrices must be canonical (every row strictly ascending in column: sort_rows sorts; the library
+        refuses anything else with CsrkError).  Every product and the sum are rounded on their own, float32 values are
+        widened exactly, a structure-only operand counts as 1.0, and an exact-zero sum stays stored (include/csrk.h,
+        csrk_combine).  Runs on the device.  Not a reference entry point.
+        """
+        return self._combine(other, 'add', alpha, beta)
+
+    def subtract(self, other):
+        "self - other: add(other, 1.0, -1.0)"
+        return self._combine(other, 'add', 1.0, -1.0)
+
+    def multiply_entries(self, other):
+        "the entry-wise product over the intersection of the two patterns (float64; both matrices canonical, as for add)"
+        return self._combine(other, 'multiply')
+
+    def keep_entries(self, other):
+        """
+        The entries of self whose (row, column) `other` stores, in self's storage order, indices and values bit for bit
+        (a structure-only self stays structure-only).  Only `other` must be canonical: self may be unsorted and repeat
+        columns (a product in the reference's column order is).  other's values are not read.
+        """
+        return self._combine(other, 'keep')
+
+    def drop_entries(self, other):
+        "the entries of self whose (row, column) `other` does NOT store; otherwise as keep_entries"
+        return self._combine(other, 'drop')
+
+    def multiply_topk(self, other, k, *, transpose=False, min_value=None, order='descending', exclude=None):
         """
         self.multiply(other, transpose).topk_rows(k, min_value=min_value, order=order), array for array, with the product
         left on the device: per row block to_handle -> mult_ab / mult_abt -> filter_zeros -> topk_rows -> from_handle, so
         only the kept entries cross PCIe (item-kNN: each row's k most similar neighbours above a minimum similarity).
+        exclude: a canonical CSR of the product's shape whose stored positions are removed from the product before the
+        top-k (a recommender's seen items) -- drop_entries on the device between filter_zeros and topk_rows; its device copy
+        is made once and pick_rows takes the rows of each block.
         """
         if transpose:
             assert self.ncols == other.ncols
@@ -388,6 +449,8 @@ class CSR:
         K, fn = self._ext('topk_rows')
         _topk_check(K, k, min_value, order)
         _, dev_filter = self._ext('filter_zeros')
+        if exclude is not None:
+            return self._multiply_topk_excluding(other, k, transpose, min_value, order, exclude)
 
         def mul(A, b_h):
             with releasing(K.to_handle(A), K) as a_h:
@@ -399,6 +462,36 @@ class CSR:
         with releasing(K.to_handle(other), K) as b_h:
             blocks = [mul(blk, b_h) for blk in self._row_blocks(K.max_nnz)]
         return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
+
+    def _multiply_topk_excluding(self, other, k, transpose, min_value, order, exclude):
+        "multiply_topk with `exclude`: product -> filter_zeros -> combine(.., 'drop') -> topk_rows, all on the device"
+        K, fn = self._ext('topk_rows')
+        _, dev_filter = self._ext('filter_zeros')
+        _, comb = self._ext('combine')
+        _, pick = self._ext('pick_rows')
+        shape = (self.nrows, other.nrows if transpose else other.ncols)
+        if (exclude.nrows, exclude.ncols) != shape:
+            raise ValueError(f'exclude is {exclude.nrows} x {exclude.ncols}, the product {shape[0]} x {shape[1]}')
+
+        def mul(A, b_h, x_h):
+            with releasing(K.to_handle(A), K) as a_h:
+                with releasing(K.mult_abt(a_h, b_h) if transpose else K.mult_ab(a_h, b_h), K) as c_h:
+                    with releasing(dev_filter(c_h), K) as f_h:
+                        with releasing(comb(f_h, x_h, 'drop'), K) as d_h:
+                            with releasing(fn(d_h, k, min_value, order), K) as t_h:
+                                return K.from_handle(t_h)
+
+        blocks = self._row_blocks(K.max_nnz)
+        with releasing(K.to_handle(other), K) as b_h:
+            with releasing(K.to_handle(exclude), K) as x_h:
+                if len(blocks) == 1:
+                    return mul(self, b_h, x_h)
+                out, r0 = [], 0
+                for blk in blocks:
+                    with releasing(pick(x_h, np.arange(r0, r0 + blk.nrows, dtype=np.int32), False), K) as xb_h:
+                        out.append(mul(blk, b_h, xb_h))
+                    r0 += blk.nrows
+        return CSR._assemble_shards(out)
 
     def _row_blocks(self, limit):
         "the matrix itself when it fits the kernel's max_nnz, else its _shard_rows blocks"
@@ -425,6 +518,11 @@ class CSR:
         last row boundary that keeps it within the target; a single row larger than the target cannot be placed.
         Pinned by tests/golden/shard.npz (the reference's own cuts).
         """
+        cuts = self._shard_cuts(tgt_nnz)
+        return [self.subset_rows(a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+
+    def _shard_cuts(self, tgt_nnz):
+        "the row boundaries of _shard_rows: [0, ..., nrows]"
         assert tgt_nnz > 0
         ptr = self.rowptrs.astype(np.int64)
         cuts = [0]
@@ -441,7 +539,7 @@ class CSR:
             _log.debug('%s: row block [%d, %d) holds %d entries', self, first, nxt, int(ptr[nxt]) - int(ptr[first]))
             cuts.append(nxt)
         cuts.append(self.nrows)
-        return [self.subset_rows(a, b) for a, b in zip(cuts[:-1], cuts[1:])]
+        return cuts
 
     @classmethod
     def _assemble_shards(cls, shards):

@@ -125,6 +125,8 @@ struct Matrix {
     SpmmPlan *spmm_plan = nullptr;
     int dense_panel = -1;          // as the right operand of mult_ab: 1 = fully populated, rows 0 .. ncols - 1 ascending (its values ARE a row-major
                                    // panel), 0 = not, -1 = not looked at yet (spgemm_dense_b; reset with the plans by the in-place operations)
+    int canonical = -1;            // every row strictly ascending in column: 1, 0 (noncanonical_row: the first row that is not), -1 = not looked
+    int32_t noncanonical_row = -1; // at yet (csrk_combine; reset like dense_panel: order_columns rewrites the columns)
     // A launch was issued on a caller's stream: the caching allocator recycles blocks in default-stream order only,
     // and a non-blocking stream is not ordered with the default one, so the handle's memory (arrays, plans, scratch)
     // goes back to the pool only after the device has drained (csrk_free, plan invalidation, scratch growth).

@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows, combine.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -211,6 +211,11 @@ def _call(fn, *args):
     operations (order_columns, unit_rows, center_rows) are never retried -- a second pass over a half-updated matrix
     would report success with wrong norms.
     """
+    check(_call_rc(fn, *args))
+
+
+def _call_rc(fn, *args):
+    "_call without the check: the status comes back (a caller that raises its refusals its own way: combine)"
     rc = fn(*args)
     if rc == _lib.ERR_HIP:
         with _cache_lock:
@@ -219,7 +224,7 @@ def _call(fn, *args):
             flush_handle_cache()
             check(lib.csrk_trim_cache())
             rc = fn(*args)
-    check(rc)
+    return rc
 
 
 # ---- result arrays -----------------------------------------------------------------------------------------
@@ -627,6 +632,51 @@ def topk_limits():
     "(longest row ranked by one wavefront, winners a large-class workgroup orders in LDS, its threads, longest medium row)"
     out = (C.c_int64 * 4)()
     check(lib.csrk_topk_limits(out, 4))
+    return tuple(out)
+
+
+_COMBINE_OPS = {'add': _lib.COMBINE_ADD, 'multiply': _lib.COMBINE_MUL, 'keep': _lib.COMBINE_KEEP, 'drop': _lib.COMBINE_DROP}
+
+
+def combine_args(a, b, op, alpha=1.0, beta=1.0):
+    """
+    (op code, alpha, beta) as the library takes them; ValueError for an unknown op, a non-real alpha or beta, or operands
+    (handles or CSRs: anything with nrows and ncols) of different shapes
+    """
+    import numbers
+    if not isinstance(op, str) or op not in _COMBINE_OPS:
+        raise ValueError(f"op must be 'add', 'multiply', 'keep' or 'drop', not {op!r}")
+    for name, v in (('alpha', alpha), ('beta', beta)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f'{name} must be a real number, not {v!r}')
+    if (a.nrows, a.ncols) != (b.nrows, b.ncols):
+        raise ValueError(f'operands of different shapes: {a.nrows} x {a.ncols} and {b.nrows} x {b.ncols}')
+    return _COMBINE_OPS[op], float(alpha), float(beta)
+
+
+def combine(a_h, b_h, op, alpha=1.0, beta=1.0):
+    """
+    Two matrices entry by entry on the device: NEW handle of A's shape (include/csrk.h, csrk_combine).
+      'add'       alpha A + beta B over the union of the patterns    (float64; each product and the sum rounded on its own)
+      'multiply'  a b over the intersection                          (float64)
+      'keep'      the entries of A whose position B stores           (A's storage order, indices and values bit for bit)
+      'drop'      the entries of A whose position B does not store   (the same)
+    'add' and 'multiply' need both operands canonical (every row strictly ascending in column), 'keep' and 'drop' only
+    B: A may be unsorted and repeat columns.  The library refuses a non-canonical operand with CsrkError (its message
+    names the operand and a row); order_columns sorts.  a_h may be b_h.  Not a reference entry point.
+    """
+    code, al, be = combine_args(a_h, b_h, op, alpha, beta)
+    out = handle_t(0)
+    rc = _call_rc(lib.csrk_combine, _live(a_h), _live(b_h), code, al, be, C.byref(out))
+    if rc != _lib.OK:
+        raise _lib.CsrkError(rc, _lib.last_error())
+    return _wrap(out.value)
+
+
+def combine_limits():
+    "(entries a wavefront takes per step, entries a workgroup takes per step, largest len_a + len_b of the wavefront class)"
+    out = (C.c_int64 * 3)()
+    check(lib.csrk_combine_limits(out, 3))
     return tuple(out)
 
 

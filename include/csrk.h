@@ -355,6 +355,43 @@ CSRK_API int csrk_topk_rows(csrk_handle_t h, int64_t k, double min_value, int or
  * No device is touched. */
 CSRK_API int csrk_topk_limits(int64_t *out, int n);
 
+/* ---- combine: two matrices entry by entry -> a new one -------------------------------------------
+ * Not a reference entry point: what a caller does between the kernels above -- drop the (user, item) pairs already seen
+ * from a product before csrk_topk_rows, a residual or a blend of two matrices (alpha A + beta B), a weighting (A o B),
+ * A + A^T.  Returns a NEW handle of A's shape.  CANONICAL below means: every row strictly ascending in column (sorted,
+ * no column twice); csrk_order_columns sorts.
+ *   1. A and B have the same nrows and ncols.  a == b is allowed.  Neither is modified; both keep their plans.  The
+ *      operands may differ in pointer width and in value type.
+ *   2. op = CSRK_COMBINE_ADD (the union of the patterns; A and B canonical): rows strictly ascending, float64 values --
+ *      an entry of both round(round(alpha a) + round(beta b)), of A alone round(alpha a), of B alone round(beta b).  Each
+ *      multiply and the add is rounded on its own (no fused multiply-add); float32 values are widened exactly first; a
+ *      structure-only operand counts as 1.0 everywhere (csrk_sddmm's rule).  alpha and beta get no special cases: an
+ *      exact-zero result stays stored (csrk_filter_zeros removes it), NaN and Inf behave as IEEE says (0 * Inf is NaN).
+ *   3. op = CSRK_COMBINE_MUL (the intersection; A and B canonical; alpha, beta ignored): the columns both rows hold,
+ *      ascending, float64 round(a b), operands widened as in 2.
+ *   4. op = CSRK_COMBINE_KEEP / CSRK_COMBINE_DROP (a mask; only B canonical; alpha, beta ignored): the entries of A whose
+ *      column is (KEEP) / is not (DROP) stored in the same row of B, in A's storage order -- A may be unsorted and may
+ *      repeat columns (a product in the reference's column order is).  Column indices and values are copied bit for bit
+ *      in A's value type (NaN payloads, -0.0, float32 subnormals); a structure-only A gives a structure-only result.
+ *      B's values are never read.
+ *   5. Row pointers are int32 unless the result holds more than 2^31 - 1 entries, whatever the inputs' widths (the rule
+ *      of csrk_pick_rows).
+ *   6. CSRK_ERR_INVALID: a NULL out, an unknown op, different shapes, or an operand that has to be canonical and is not
+ *      (the message names the operand and the first such row).  The rows are looked at on the device, once per handle:
+ *      the answer is remembered and dropped by whatever rewrites the handle's columns (csrk_order_columns).
+ *      CSRK_ERR_UNSUPPORTED: a row of more than 2^31 - 1 entries.  nrows = 0, or both operands without entries: CSRK_OK,
+ *      an empty result, nothing launched.
+ *   7. The result depends on (A, B, op, alpha, beta) only: not on launch geometry, the pointer widths or repeated calls
+ *      (csrc/combine.hip: every slot is counted, never appended in arrival order; no float atomics).  A NaN the
+ *      arithmetic of ADD / MUL creates or passes on has no specified sign or payload, only its position.
+ * Column indices are compared and copied, never used as addresses. */
+enum { CSRK_COMBINE_ADD = 0, CSRK_COMBINE_MUL = 1, CSRK_COMBINE_KEEP = 2, CSRK_COMBINE_DROP = 3 };
+CSRK_API int csrk_combine(csrk_handle_t a, csrk_handle_t b, int op, double alpha, double beta, csrk_handle_t *out);
+/* Diagnostics: the row classes of csrk_combine, ascending: out[0] = the entries of a row one wavefront takes per step,
+ * [1] = the entries a workgroup takes per step (its threads), [2] = the largest len_a + len_b of the wavefront class (longer
+ * rows get a workgroup each);  n <= 3.  No device is touched. */
+CSRK_API int csrk_combine_limits(int64_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

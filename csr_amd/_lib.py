@@ -16,6 +16,7 @@ VAL_NONE, VAL_F32, VAL_F64 = 0, 1, 2
 SPMV_AUTO, SPMV_MERGE, SPMV_VECTOR, SPMV_SCALAR = 0, 1, 2, 3
 TOPK_BY_VALUE, TOPK_STORAGE = 0, 1
 COMBINE_ADD, COMBINE_MUL, COMBINE_KEEP, COMBINE_DROP = 0, 1, 2, 3
+DUP_SUM, DUP_FIRST, DUP_LAST, DUP_MAX, DUP_MIN = 0, 1, 2, 3, 4
 
 
 class CsrkError(RuntimeError):
@@ -104,6 +105,9 @@ SIGNATURES = {
     'csrk_topk_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_combine': (_int, [handle_t, handle_t, _int, C.c_double, C.c_double, C.POINTER(handle_t)]),
     'csrk_combine_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_coalesce': (_int, [handle_t, _int, C.POINTER(handle_t)]),
+    'csrk_coalesce_last_route': (_int, [C.POINTER(_int)]),
+    'csrk_is_canonical': (_int, [handle_t, C.POINTER(_int), C.POINTER(_i32)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

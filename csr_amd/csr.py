@@ -29,6 +29,15 @@ def _topk_check(K, k, min_value, order):
         chk(k, min_value, order)
 
 
+def _coalesce_check(K, duplicates):
+    "the argument error of coalesce / from_coo(duplicates=), raised before any device work"
+    chk = getattr(K, 'coalesce_args', None)
+    if chk is not None:
+        chk(duplicates)
+    elif duplicates not in ('sum', 'first', 'last', 'max', 'min'):
+        raise ValueError(f"duplicates must be 'sum', 'first', 'last', 'max' or 'min', not {duplicates!r}")
+
+
 class CSR:
     """
     Compressed sparse row matrix (host arrays), drop-in for the reference's `csr.CSR` on the
@@ -103,12 +112,16 @@ class CSR:
         return cls(nrows, ncols, nnz, rps, np.zeros(nnz, dtype=np.intc), vs)
 
     @classmethod
-    def from_coo(cls, rows, cols, vals, shape=None):
+    def from_coo(cls, rows, cols, vals, shape=None, *, duplicates=None):
         """
         csr/csr.py:138-169 -> csr/structure.py:11-67: stable counting sort of the COO entries
         by row (entries of a row keep their input order).  Host-side ingest, not on the hot
         path (out of scope); done with a stable NumPy argsort.
+        duplicates=None keeps every repeated (row, col) pair, as the reference does; 'sum', 'first', 'last', 'max' or
+        'min' hands the ingested matrix to coalesce() (on the device), whose result is canonical.
         """
+        if duplicates is not None:
+            _coalesce_check(get_kernel(), duplicates)
         rows = np.asarray(rows)
         cols = np.asarray(cols)
         assert np.min(rows, initial=0) >= 0 and np.min(cols, initial=0) >= 0
@@ -124,7 +137,8 @@ class CSR:
         order = np.argsort(rows, kind='stable')
         rps = np.zeros(nrows + 1, dtype=np.int64)
         np.cumsum(np.bincount(rows, minlength=nrows), out=rps[1:])
-        return cls(nrows, ncols, nnz, rps, cols[order], None if vals is None else np.asarray(vals)[order])
+        m = cls(nrows, ncols, nnz, rps, cols[order], None if vals is None else np.asarray(vals)[order])
+        return m if duplicates is None else m.coalesce(duplicates)
 
     @classmethod
     def from_scipy(cls, mat, copy=True):
@@ -406,8 +420,8 @@ class CSR:
     def add(self, other, alpha=1.0, beta=1.0):
         """
         alpha * self + beta * other over the union of the two patterns, as a new CSR with float64 values and rows ascending
-        in column.  Both matrices must be canonical (every row strictly ascending in column: sort_rows sorts; the library
-        refuses anything else with CsrkError).  Every product and the sum are rounded on their own, float32 values are
+        in column.  Both matrices must be canonical (every row strictly ascending in column: sort_rows sorts, coalesce
+        sorts and merges repeated columns; the library refuses anything else with CsrkError).  Every product and the sum are rounded on their own, float32 values are
         widened exactly, a structure-only operand counts as 1.0, and an exact-zero sum stays stored (include/csrk.h,
         csrk_combine).  Runs on the device.  Not a reference entry point.
         """
@@ -432,6 +446,50 @@ class CSR:
     def drop_entries(self, other):
         "the entries of self whose (row, column) `other` does NOT store; otherwise as keep_entries"
         return self._combine(other, 'drop')
+
+    # ---- the canonical form ---------------------------------------------------------------------
+    def coalesce(self, duplicates='sum'):
+        """
+        The canonical form as a new CSR: every row strictly ascending in column, one entry per distinct (row, column).  The
+        entries of a row that share a column are merged in their storage order: 'sum' adds them left to right (each add
+        rounded in the values' dtype; an exact zero stays stored), 'first' / 'last' keep the one stored first / last,
+        'max' / 'min' the earliest stored of the largest / the latest stored of the smallest in topk_rows' order (NaN above
+        +Inf, -0.0 ties with +0.0); all but 'sum' copy the value bit for bit.  Values keep their dtype, a structure-only
+        matrix stays structure-only (include/csrk.h, csrk_coalesce).  What add, multiply_entries and the masks ask of
+        their operands.  Runs on the device, per row block above K.max_nnz (a group never leaves its row).  Not a reference
+        entry point.
+        """
+        K, fn = self._ext('coalesce')
+        _coalesce_check(K, duplicates)
+
+        def co(A):
+            with releasing(K.to_handle(A), K) as h:
+                with releasing(fn(h, duplicates), K) as c_h:
+                    return K.from_handle(c_h)
+
+        blocks = [co(blk) for blk in self._row_blocks(K.max_nnz)]
+        return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
+
+    def sum_duplicates(self):
+        "coalesce('sum'), under SciPy's name for it (a new matrix: self is not changed)"
+        return self.coalesce('sum')
+
+    def is_canonical(self, *, with_row=False):
+        """
+        Is every row strictly ascending in column (sorted, no column twice)?  Asked on the device.  with_row=True returns
+        (answer, the first row that is not -- None when canonical).
+        """
+        K, fn = self._ext('is_canonical')
+        r0 = 0
+        ok, row = True, None
+        for blk in self._row_blocks(K.max_nnz):
+            with releasing(K.to_handle(blk), K) as h:
+                ok, row = fn(h)
+            if not ok:
+                row += r0
+                break
+            r0 += blk.nrows
+        return (ok, row) if with_row else ok
 
     def multiply_topk(self, other, k, *, transpose=False, min_value=None, order='descending', exclude=None):
         """

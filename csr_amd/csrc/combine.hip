@@ -226,55 +226,6 @@ __global__ __launch_bounds__(256) void combine_ptr_kernel(const int64_t *__restr
     if (i <= nr) orp[i] = (PO)off[i];
 }
 
-// ---- canonical rows ------------------------------------------------------------------------------------------------------
-// One thread per entry: an entry that is not above its predecessor is fine only where it starts a row (one binary search of
-// the row pointers, taken by those entries alone).  Only a flag comes back: the lowest offending row.
-template <class P>
-__global__ __launch_bounds__(256) void combine_canon_kernel(const P *__restrict__ rp, const int32_t *__restrict__ ci, int32_t nrows,
-                                                           int64_t nnz, int32_t *__restrict__ bad_row)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
-    if (e >= nnz) return;
-    if (ci[e - 1] < ci[e]) return;
-    int64_t lo = 0, hi = (int64_t)nrows - 1;          // the last row that starts at or before e: the row that holds it
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if ((int64_t)rp[mid] <= e)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    if ((int64_t)rp[lo] != e) atomicMin(bad_row, (int32_t)lo);
-}
-
-// Is every row strictly ascending in column?  Remembered by the handle (Matrix::canonical; invalidate_plans drops it
-// when order_columns rewrites the columns).  Caller holds m->mu.
-static int ensure_canonical(Matrix *m, const char *name)
-{
-    if (m->canonical < 0) {
-        int32_t row = INT32_MAX;
-        if (m->nnz > 1) {
-            DevBuf bad;
-            CSRK_TRY(bad.alloc(4));
-            CSRK_HIP(hipMemcpy(bad.p, &row, 4, hipMemcpyHostToDevice));
-            const unsigned grid = (unsigned)ceil_div(m->nnz - 1, 256);
-            if (m->ptr64)
-                combine_canon_kernel<int64_t><<<grid, 256>>>((const int64_t *)m->d_rowptrs, m->d_colinds, m->nrows, m->nnz, bad.as<int32_t>());
-            else
-                combine_canon_kernel<int32_t><<<grid, 256>>>((const int32_t *)m->d_rowptrs, m->d_colinds, m->nrows, m->nnz, bad.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            CSRK_HIP(hipMemcpy(&row, bad.p, 4, hipMemcpyDeviceToHost));      // (waits for the kernel: `bad` may go back to the pool)
-        }
-        m->canonical = row == INT32_MAX ? 1 : 0;
-        m->noncanonical_row = row == INT32_MAX ? -1 : row;
-    }
-    CSRK_REQUIRE(m->canonical == 1,
-                 "combine: operand %s is not canonical: row %d is not strictly ascending in column (csrk_order_columns "
-                 "sorts; repeated columns have to be merged by the caller)",
-                 name, m->noncanonical_row);
-    return CSRK_OK;
-}
-
 static int empty_result(int32_t nrows, int32_t ncols, int vt, Matrix **out)
 {
     Matrix *t = nullptr;

@@ -127,6 +127,7 @@ struct Matrix {
                                    // panel), 0 = not, -1 = not looked at yet (spgemm_dense_b; reset with the plans by the in-place operations)
     int canonical = -1;            // every row strictly ascending in column: 1, 0 (noncanonical_row: the first row that is not), -1 = not looked
     int32_t noncanonical_row = -1; // at yet (csrk_combine; reset like dense_panel: order_columns rewrites the columns)
+    int nondescending = -1;        // no entry below its predecessor in the row (repeats allowed): 1, 0, -1; from the same look (csrk_coalesce)
     // A launch was issued on a caller's stream: the caching allocator recycles blocks in default-stream order only,
     // and a non-blocking stream is not ordered with the default one, so the handle's memory (arrays, plans, scratch)
     // goes back to the pool only after the device has drained (csrk_free, plan invalidation, scratch growth).
@@ -149,6 +150,11 @@ int64_t spmm_plan_bytes(const SpmmPlan *p);
 void invalidate_plans(Matrix *m);
 // Wait for every stream of the device if a caller's stream ever launched on this handle (before its memory is recycled).
 void drain_user_streams(Matrix *m);
+
+// Is every row strictly ascending in column?  One look on the device answers it and "is every row non-descending" together;
+// the handle remembers both (Matrix::canonical, noncanonical_row, nondescending) until invalidate_plans.  Caller holds m->mu.
+int look_at_rows(Matrix *m);                              // coalesce.hip
+int ensure_canonical(Matrix *m, const char *name);        // CSRK_ERR_INVALID (csrk_combine's refusal) unless canonical
 
 // Create an owning matrix with freshly allocated (uninitialised) device arrays.
 int new_matrix(int32_t nrows, int32_t ncols, int64_t nnz, int ptr64, int val_type, Matrix **out);

@@ -260,6 +260,7 @@ void invalidate_plans(Matrix *m)
 {
     m->dense_panel = -1;      // (order_columns may have made the rows ascending, or not)
     m->canonical = -1;        // (the same for csrk_combine's look at the rows)
+    m->nondescending = -1;
     if (!m->spmv_plan && !m->spmm_plan) return;
     (void)hipDeviceSynchronize();
     if (m->spmm_plan) {                 // may hold a view into the SpMV plan: goes first

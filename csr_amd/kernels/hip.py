@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows, combine.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows, combine, coalesce, is_canonical.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -663,7 +663,7 @@ def combine(a_h, b_h, op, alpha=1.0, beta=1.0):
       'drop'      the entries of A whose position B does not store   (the same)
     'add' and 'multiply' need both operands canonical (every row strictly ascending in column), 'keep' and 'drop' only
     B: A may be unsorted and repeat columns.  The library refuses a non-canonical operand with CsrkError (its message
-    names the operand and a row); order_columns sorts.  a_h may be b_h.  Not a reference entry point.
+    names the operand and a row); order_columns sorts, coalesce sorts and merges.  a_h may be b_h.  Not a reference entry point.
     """
     code, al, be = combine_args(a_h, b_h, op, alpha, beta)
     out = handle_t(0)
@@ -678,6 +678,51 @@ def combine_limits():
     out = (C.c_int64 * 3)()
     check(lib.csrk_combine_limits(out, 3))
     return tuple(out)
+
+
+_DUPLICATES = {'sum': _lib.DUP_SUM, 'first': _lib.DUP_FIRST, 'last': _lib.DUP_LAST, 'max': _lib.DUP_MAX, 'min': _lib.DUP_MIN}
+
+
+def coalesce_args(duplicates):
+    "the dup code as the library takes it; ValueError for anything but 'sum', 'first', 'last', 'max', 'min'"
+    if not isinstance(duplicates, str) or duplicates not in _DUPLICATES:
+        raise ValueError(f"duplicates must be 'sum', 'first', 'last', 'max' or 'min', not {duplicates!r}")
+    return _DUPLICATES[duplicates]
+
+
+def coalesce(h, duplicates='sum'):
+    """
+    The canonical form of the handle's matrix on the device: NEW handle of the same shape, every row strictly ascending in
+    column, one entry per distinct (row, column) (include/csrk.h, csrk_coalesce).  The entries of a row that share a column
+    become, in their storage order:
+      'sum'    ((v0 + v1) + v2) + ...   each add rounded in the values' dtype; an exact zero stays stored
+      'first'  v0                       'last'  the one stored last              (bit for bit)
+      'max'    the earliest stored of the largest      'min'  the latest stored of the smallest      (bit for bit; NaN
+               ranks above +Inf, -0.0 ties with +0.0: topk_rows' order)
+    Values keep their dtype; a structure-only matrix stays structure-only.  h is not modified.  The result may go straight
+    into combine.  Not a reference entry point.
+    """
+    code = coalesce_args(duplicates)
+    out = handle_t(0)
+    _call(lib.csrk_coalesce, _live(h), code, C.byref(out))
+    return _wrap(out.value)
+
+
+def coalesce_last_route():
+    "what this thread's last coalesce did: 0 copied a canonical matrix, 1 merged without sorting, 2 sorted and merged"
+    r = C.c_int(0)
+    check(lib.csrk_coalesce_last_route(C.byref(r)))
+    return r.value
+
+
+def is_canonical(h):
+    """
+    (True, None) when every row of the handle's matrix is strictly ascending in column, else (False, the first row that
+    is not).  Looked at on the device once per handle; combine and coalesce use the same answer.
+    """
+    ok, row = C.c_int(0), C.c_int32(-1)
+    _call(lib.csrk_is_canonical, _live(h), C.byref(ok), C.byref(row))
+    return (True, None) if ok.value else (False, row.value)
 
 
 def values_of(h):

@@ -392,6 +392,49 @@ CSRK_API int csrk_combine(csrk_handle_t a, csrk_handle_t b, int op, double alpha
  * rows get a workgroup each);  n <= 3.  No device is touched. */
 CSRK_API int csrk_combine_limits(int64_t *out, int n);
 
+/* ---- coalesce: the canonical form of any matrix --------------------------------------------------
+ * Not a reference entry point: what csrk_combine asks of its operands and nothing above supplies.  csrk_from_coo keeps every
+ * repeated (row, column) pair (a re-rated item in a ratings log) and csrk_order_columns only sorts; csrk_coalesce merges.
+ *   1. The result is a NEW handle of h's shape: every row strictly ascending in column, one entry per distinct
+ *      (row, column) that h stores.  h is not modified and keeps its plans.  The result is known to be canonical: a
+ *      following csrk_combine or csrk_is_canonical does not look at its rows again.
+ *   2. A GROUP is the set of entries of one row with one column; its members v0 .. v(m-1) are taken in h's storage order,
+ *      earlier in the row first.  A group never crosses a row boundary: the last entry of row r and the first of the next
+ *      non-empty row stay two entries when their columns agree.  `dup` says what a group becomes:
+ *        CSRK_DUP_SUM    ((v0 + v1) + v2) + ..., left to right, every add rounded in the values' dtype (float32 values: float32
+ *                        adds).  The sum does not start at +0.0: a group of one is copied bit for bit and -0.0 + -0.0 stays
+ *                        -0.0.  An exact-zero sum stays stored (csrk_filter_zeros removes it).  A NaN that an add creates or
+ *                        passes on has its position specified, not its sign or payload (csrk_combine's rule 7).
+ *        CSRK_DUP_FIRST  v0, copied bit for bit.       CSRK_DUP_LAST  v(m-1), copied bit for bit.
+ *        CSRK_DUP_MAX / CSRK_DUP_MIN   the first / the last member in the total order of csrk_topk_rows (rule 2): larger
+ *                        first, NaN above +Inf and all NaNs tied, -0.0 and +0.0 tied, tied members in storage order.  So MAX
+ *                        takes the EARLIEST stored of the largest members and MIN the LATEST stored of the smallest; MIN is
+ *                        a NaN only when every member is one.  The value is copied bit for bit.
+ *      Bit for bit holds for -0.0, subnormals and quiet-NaN payloads in both dtypes; a signalling float32 NaN may come back
+ *      quieted when the entries had to be sorted (as from csrk_order_columns).  Values keep their dtype; a structure-only h
+ *      gives a structure-only result (dup must still be valid).
+ *   3. Row pointers are int32 unless the result holds more than 2^31 - 1 entries, whatever h's width (csrk_pick_rows' rule).
+ *   4. Three routes, the same arrays from each for the same matrix (csrk_coalesce_last_route):
+ *        0  h is canonical: the result is a device copy.
+ *        1  h's rows are non-descending in column, only repeats are present: the groups are merged without any sort.
+ *        2  the entries are sorted by column within rows, stably, then merged.
+ *      Which one applies is found by one look at the rows on the device, remembered by the handle like csrk_combine's.
+ *   5. The result depends on (h, dup) only: not on launch geometry, the pointer width or repeated calls (csrc/coalesce.hip:
+ *      every slot is counted, a group is folded by one thread in storage order; no float atomics, nothing appended in
+ *      arrival order).
+ *   6. CSRK_ERR_INVALID: a NULL out, an unknown dup, a bad handle; *out is 0 on any failure.  nrows = 0 or nnz = 0: CSRK_OK,
+ *      an empty result, nothing launched.
+ * Column indices are compared and copied, never used as addresses. */
+enum { CSRK_DUP_SUM = 0, CSRK_DUP_FIRST = 1, CSRK_DUP_LAST = 2, CSRK_DUP_MAX = 3, CSRK_DUP_MIN = 4 };
+CSRK_API int csrk_coalesce(csrk_handle_t h, int dup, csrk_handle_t *out);
+/* The route the calling thread's last csrk_coalesce took: 0 copied, 1 merged without sorting, 2 sorted and merged; 0 after
+ * a failed call.  No device is touched. */
+CSRK_API int csrk_coalesce_last_route(int *route);
+/* Is every row of h strictly ascending in column?  *canonical = 1 or 0; *first_bad_row (may be NULL) = the first row that
+ * is not, -1 when canonical.  The rows are looked at on the device once per handle: the answer is remembered (it is the one
+ * csrk_combine and csrk_coalesce use) and dropped by whatever rewrites the handle's columns (csrk_order_columns). */
+CSRK_API int csrk_is_canonical(csrk_handle_t h, int *canonical, int32_t *first_bad_row);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,9 @@ SIGNATURES = {
     'csrk_spmm_plan_stats': (_int, [handle_t, _vp, _int]),
     'csrk_sddmm': (_int, [handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _vp]),
     'csrk_sddmm_device': (_int, [handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _vp, _vp]),
+    'csrk_gram_rows': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _vp, _vp]),
+    'csrk_gram_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _vp, _vp, _vp]),
+    'csrk_gram_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

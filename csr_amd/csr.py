@@ -369,6 +369,27 @@ class CSR:
         vals = vs[0] if len(vs) == 1 else np.concatenate(vs)
         return CSR(self.nrows, self.ncols, self.nnz, self.rowptrs.copy(), self.colinds.copy(), vals, _cast=False)
 
+    def gram_rows(self, V, *, weighted=False, rows=None, base=None, max_bytes=4 << 30):
+        """
+        One k x k Gram matrix per row, float64 [n, k, k]: for each row i of rows = (begin, end) (None: all rows), base plus
+        the sum over the row's stored columns j of w V[j, :]^T V[j, :], with w = 1 or (weighted=True) the entry's value --
+        the left-hand side of the normal equations of alternating least squares (mult_dense gives the right-hand side).  V
+        [ncols x k] is float32 or float64; base is None or float64 [k, k] (its lower triangle is read; lambda I for a
+        ridge).  Every block is exactly symmetric and every element a fixed chain of one rounded multiply and one fused
+        multiply-add per entry, in storage order (include/csrk.h).  A request whose result would exceed max_bytes is
+        refused with ValueError: ask for row ranges.  Not a reference entry point.
+        """
+        K, fn = self._ext('gram_rows')
+        V, _, k, _, rb, re_, base = K.gram_args(self, V, rows, base)
+        per_row = k * k * 8
+        if (re_ - rb) * per_row > max_bytes:
+            raise ValueError(f'{re_ - rb} rows of {k} x {k} float64 are {(re_ - rb) * per_row} bytes, above max_bytes = '
+                             f'{max_bytes}: at most {max(int(max_bytes) // per_row, 0)} rows fit, ask for rows=(begin, end) ranges')
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            return fn(h, V, weighted, (rb, re_), base)
+
     def topk_rows(self, k, *, min_value=None, order='descending'):
         """
         Each row's k largest entries that are not below min_value (None: no threshold) as a new CSR of the same shape:

@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm, topk_rows, combine, coalesce, is_canonical.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, topk_rows, combine, coalesce, is_canonical.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -788,6 +788,63 @@ def sddmm(h, U, V, scale=False):
     k = U.shape[1]
     out = _out(h.nnz, np.float64)
     _call(lib.csrk_sddmm, _live(h), ptr(U), ldu, ptr(V), ldv, k, _PANEL_CODES[U.dtype], int(bool(scale)), ptr(out))
+    return out
+
+
+def gram_limits():
+    "(largest k, entries staged per step, largest k of the 16-lane class, of the wavefront class, of the one-tile workgroup class)"
+    out = (C.c_int64 * 5)()
+    check(lib.csrk_gram_limits(out, 5))
+    return tuple(out)
+
+
+def gram_args(h, V, rows=None, base=None):
+    """
+    (V, ldv, k, panel code, row_begin, row_end, base) as the library takes them; ValueError for anything it would refuse
+    as invalid.  h is anything with nrows and ncols (a handle or a CSR); no library call is made.
+    """
+    import numbers
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError(f'V must be 2-D, not of shape {V.shape}')
+    if V.dtype not in _PANEL_CODES:
+        raise ValueError(f'V must be float32 or float64, not {V.dtype}')
+    if V.shape[1] == 0:
+        raise ValueError('V has no columns (k = 0)')
+    V, ldv = _panel(V, h.ncols, 'V')
+    k = V.shape[1]
+    if rows is None:
+        rb, re_ = 0, int(h.nrows)
+    else:
+        try:
+            rb, re_ = rows
+        except (TypeError, ValueError):
+            raise ValueError(f'rows must be (begin, end), not {rows!r}') from None
+        for v in (rb, re_):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f'rows must be two integers, not {rows!r}')
+        rb, re_ = int(rb), int(re_)
+        if not 0 <= rb <= re_ <= h.nrows:
+            raise ValueError(f'rows ({rb}, {re_}) is not a range within the {h.nrows} rows')
+    if base is not None:
+        base = np.asarray(base)
+        if base.dtype != np.float64 or base.shape != (k, k):
+            raise ValueError(f'base must be float64 of shape ({k}, {k}), not {base.dtype} of shape {base.shape}')
+        base = np.ascontiguousarray(base)
+    return V, ldv, k, _PANEL_CODES[V.dtype], rb, re_, base
+
+
+def gram_rows(h, V, scale=False, rows=None, base=None):
+    """
+    One k x k Gram matrix per row: for each row i of rows = (begin, end) (None: all rows), base + the sum over the row's
+    stored entries (i, j), in storage order, of w V[j, :]^T V[j, :], w = 1 or, with scale=True, the entry's value (1.0 for a
+    structure-only matrix) -- as a fresh float64 [end - begin, k, k], exactly symmetric.  V [ncols x k] is float32 or
+    float64; base is None or float64 [k, k] of which the lower triangle is read.  Each element is one serial chain of a
+    rounded multiply and a fused multiply-add per entry (include/csrk.h, csrk_gram_rows).  Not a reference entry point.
+    """
+    V, ldv, k, code, rb, re_, base = gram_args(h, V, rows, base)
+    out = _out((re_ - rb, k, k), np.float64)
+    _call(lib.csrk_gram_rows, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), ptr(base), ptr(out))
     return out
 
 

@@ -274,6 +274,53 @@ CSRK_API int csrk_sddmm(csrk_handle_t s, const void *U, int64_t ldu, const void 
 CSRK_API int csrk_sddmm_device(csrk_handle_t s, const void *d_U, int64_t ldu, const void *d_V, int64_t ldv,
                                int32_t k, int panel_type, int scale, double *d_out, void *stream);
 
+/* ---- per-row Gram matrices: one k x k block per row ------------------------------------------
+ * Not a reference entry point: the left-hand side of the normal equations of alternating least squares,
+ * (sum_j w_ij v_j v_j^T + lambda I) u_i = sum_j c_ij v_j over row i's stored columns j; the right-hand side is
+ * csrk_spmm_dense, the solve is the caller's.  The gather of csrk_sddmm (a row of V per stored entry), reduced across a
+ * row's entries into a dense block.  out is float64, packed: out[(i - row_begin) * k * k + p * k + q] for rows
+ * row_begin <= i < row_end.
+ *   1. Operands.  V is dense row-major [ncols x k], float32 or float64 (panel_type CSRK_VAL_F32 / CSRK_VAL_F64), ldv >= k in
+ *      elements.  scale = 0: w = 1 for every entry.  scale = 1: w = values[e], float32 values widened exactly, 1.0 for a
+ *      structure-only matrix (csrk_sddmm's rule).  base is NULL or a k x k float64 matrix, packed row-major, of which
+ *      only the lower triangle (p >= q) is read.
+ *   2. Fixed arithmetic, per element.  For each row i and each p >= q the accumulator G[p][q] starts at base[p][q], or at
+ *      +0.0 when base is NULL.  Then, for the row's entries in storage order, j the entry's column, one step each:
+ *          t = round(w * V[j][p]);   G[p][q] = fma(t, V[j][q], G[p][q])
+ *      one rounded multiply and one fused multiply-add (scale = 0: t is V[j][p] itself; float32 panel elements are
+ *      widened exactly first).  Then G[q][p] = G[p][q]: the block is exactly symmetric.  Unsorted and repeated columns
+ *      are just more entries.  An empty row gives base mirrored, or all +0.0 when base is NULL.
+ *   3. An element depends on its row's entries, V's rows at those columns, k, the panel type, scale and base only: not on
+ *      the row range asked for, the pointer width, ldv, the alignment, the stream, the launch geometry or repeated calls.
+ *      (csrc/gram.hip: parallel over rows and over the k (k + 1) / 2 elements, never over a row's entries; no float
+ *      atomics, no split sums.)
+ *   4. Special values.  NaN and +-Inf propagate as IEEE says; an explicit 0.0 or -0.0 weight or V element times an
+ *      infinite or NaN operand gives NaN: no path skips a zero.  A row is changed only by NaN / Inf in V rows that it
+ *      references.  A created NaN has its position specified, not its sign or payload (csrk_combine's rule 7).
+ *   5. Alignment.  V needs its element size; base and out 8 B.  When V is 16-B aligned and ldv and k are whole numbers of
+ *      16-B pieces the kernel takes 16-B loads, else element loads -- the same bits either way.
+ *   6. Offsets into out are 64-bit: (row_end - row_begin) * k * k may exceed 2^31.  The caller chooses the row range so
+ *      that the output fits (2 10^6 rows at k = 64 would be 65 GB).
+ *   7. CSRK_ERR_INVALID: k < 1, ldv < k, an unknown panel_type, a scale other than 0 / 1, row_begin < 0, row_end > nrows,
+ *      row_begin > row_end, or a NULL out (or a NULL V when the matrix stores entries) when there is something to write.
+ *      CSRK_ERR_UNSUPPORTED: k above csrk_gram_limits' out[0] (at least 128).  row_begin == row_end: CSRK_OK, nothing
+ *      launched.  out is not written by a refused call.  h is not modified and keeps its plans.
+ *   8. Limits (csrk_gram_limits, below): out[0] = the largest k; [1] = the entries of a row staged through LDS per step;
+ *      then the k classes, ascending: [2] = the largest k at which 16 lanes take a row, [3] = the largest k at which a
+ *      wavefront takes a row, [4] = the largest k at which a workgroup takes a row with one 4 x 4 tile per thread (above
+ *      it, up to three).  By rule 3 no class changes a bit of the result.
+ * Column indices address V: they must lie in [0, ncols), as for csrk_sddmm.
+ * Host form: host pointers in and out (the panel crosses packed; synchronous). */
+CSRK_API int csrk_gram_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *V, int64_t ldv,
+                            int32_t k, int panel_type, int scale, const double *base, double *out);
+/* Device form: d_V, d_base, d_out in HBM, launched on `stream` (NULL = the default stream); nothing is allocated and the
+ * host is not synchronised. */
+CSRK_API int csrk_gram_rows_device(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *d_V, int64_t ldv,
+                                   int32_t k, int panel_type, int scale, const double *d_base, double *d_out,
+                                   void *stream);
+/* Diagnostics: the five limits of rule 8 above, in its order;  n <= 5.  No device is touched. */
+CSRK_API int csrk_gram_limits(int64_t *out, int n);
+
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).
  * Bit-exact with the reference's stable counting sort: output rowptrs keep the input

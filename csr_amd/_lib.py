@@ -17,6 +17,7 @@ SPMV_AUTO, SPMV_MERGE, SPMV_VECTOR, SPMV_SCALAR = 0, 1, 2, 3
 TOPK_BY_VALUE, TOPK_STORAGE = 0, 1
 COMBINE_ADD, COMBINE_MUL, COMBINE_KEEP, COMBINE_DROP = 0, 1, 2, 3
 DUP_SUM, DUP_FIRST, DUP_LAST, DUP_MAX, DUP_MIN = 0, 1, 2, 3, 4
+ALS_RHS_ONES, ALS_RHS_VALUES, ALS_RHS_ONE_PLUS = 0, 1, 2
 
 
 class CsrkError(RuntimeError):
@@ -93,6 +94,12 @@ SIGNATURES = {
     'csrk_gram_rows': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _vp, _vp]),
     'csrk_gram_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _vp, _vp, _vp]),
     'csrk_gram_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_solve_blocks': (_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'csrk_solve_blocks_device': (_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'csrk_als_rows': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, _vp, _i64, _vp]),
+    'csrk_als_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, _vp, _i64, _vp,
+                                    _vp]),
+    'csrk_als_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

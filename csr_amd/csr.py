@@ -390,6 +390,35 @@ class CSR:
         with releasing(K.to_handle(self), K) as h:
             return fn(h, V, weighted, (rb, re_), base)
 
+    def als_rows(self, V, *, weighted=False, rhs='values', base=None, reg_per_entry=0.0, rows=None, return_info=False):
+        """
+        One half-step of alternating least squares, float64 [n, k]: for each row i of rows = (begin, end) (None: all rows)
+        the solution u_i of
+            (base + sum_j w_ij V[j, :]^T V[j, :] + reg_per_entry * n_i * I) u_i = sum_j c_ij V[j, :]
+        over the row's n_i stored columns j, with w = 1 or (weighted=True) the entry's value and c = the value
+        (rhs='values'), 1 ('ones') or 1 + the value ('one_plus_values': implicit feedback with values stored as
+        confidence - 1).  Explicit ALS: weighted=False, rhs='values', a ridge in base or reg_per_entry.  Implicit ALS:
+        weighted=True, rhs='one_plus_values', base = V^T V + lambda I.  The k x k block is gram_rows' block bit for bit,
+        but it is built and factorised (LDL^T, no pivoting, a fixed order of fused multiply-adds) on the chip and never
+        stored, so the result is small whatever k and no max_bytes is needed (include/csrk.h, csrk_als_rows).  A row
+        whose system has a pivot that is not positive (an empty row without base, an indefinite base) raises ValueError
+        naming the first such row; with return_info=True nothing is raised and (U, info) comes back, info[i] = 0 or
+        1 + the first bad pivot of row i.  Not a reference entry point.
+        """
+        K, fn = self._ext('als_rows')
+        _, _, _, _, rb, re_, base, _, lam_n = K.als_args(self, V, rhs, base, reg_per_entry, rows)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            U, info = fn(h, V, weighted, rhs, base, lam_n, (rb, re_))
+        if return_info:
+            return U, info
+        bad = np.flatnonzero(info)
+        if len(bad):
+            raise ValueError(f'{len(bad)} of {re_ - rb} rows have a system that is not positive definite; the first is row '
+                             f'{rb + int(bad[0])}, at pivot {int(info[bad[0]]) - 1} (return_info=True returns the codes)')
+        return U
+
     def topk_rows(self, k, *, min_value=None, order='descending'):
         """
         Each row's k largest entries that are not below min_value (None: no threshold) as a new CSR of the same shape:

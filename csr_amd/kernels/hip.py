@@ -7,7 +7,8 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, topk_rows, combine, coalesce, is_canonical.
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
+is_canonical.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -846,6 +847,70 @@ def gram_rows(h, V, scale=False, rows=None, base=None):
     out = _out((re_ - rb, k, k), np.float64)
     _call(lib.csrk_gram_rows, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), ptr(base), ptr(out))
     return out
+
+
+def als_limits():
+    "(largest k, entries staged per step, largest k of the 16-lane class, of the wavefront class, of the one-tile workgroup class)"
+    out = (C.c_int64 * 5)()
+    check(lib.csrk_als_limits(out, 5))
+    return tuple(out)
+
+
+_RHS_CODES = {'ones': _lib.ALS_RHS_ONES, 'values': _lib.ALS_RHS_VALUES, 'one_plus_values': _lib.ALS_RHS_ONE_PLUS}
+
+
+def solve_args(G, b):
+    "(G, b, n, k) as the library takes them; ValueError for anything it would refuse as invalid.  No library call is made."
+    G, b = np.asarray(G), np.asarray(b)
+    if G.ndim != 3 or G.shape[1] != G.shape[2] or G.dtype != np.float64:
+        raise ValueError(f'G must be float64 of shape (n, k, k), not {G.dtype} of shape {G.shape}')
+    n, k = G.shape[0], G.shape[1]
+    if k == 0:
+        raise ValueError('the systems have no unknowns (k = 0)')
+    if b.dtype != np.float64 or b.shape != (n, k):
+        raise ValueError(f'b must be float64 of shape ({n}, {k}), not {b.dtype} of shape {b.shape}')
+    return np.ascontiguousarray(G), np.ascontiguousarray(b), n, k
+
+
+def solve_blocks(G, b):
+    """
+    Solve n symmetric k x k systems G[s] x[s] = b[s]: (x float64 [n, k], info int32 [n]).  Only the lower triangle of each
+    G[s] is read.  An LDL^T factorisation without pivoting in a fixed order of fused multiply-adds (include/csrk.h, rule
+    S): the same bits whatever the launch.  info[s] is 0, or j + 1 for the first pivot j that is not positive (x[s] is then
+    Inf / NaN or meaningless).  Not a reference entry point.
+    """
+    G, b, n, k = solve_args(G, b)
+    x, info = _out((n, k), np.float64), np.zeros(n, np.int32)
+    check(lib.csrk_solve_blocks(n, k, ptr(G), ptr(b), k, ptr(x), k, ptr(info)))
+    return x, info
+
+
+def als_args(h, V, rhs='values', base=None, lam_n=0.0, rows=None):
+    "gram_args' tuple + (rhs code, lam_n); ValueError for anything the library would refuse as invalid.  No library call."
+    import numbers
+    args = gram_args(h, V, rows, base)
+    if not isinstance(rhs, str) or rhs not in _RHS_CODES:
+        raise ValueError(f'rhs must be one of {sorted(_RHS_CODES)}, not {rhs!r}')
+    if isinstance(lam_n, bool) or not isinstance(lam_n, numbers.Real):
+        raise ValueError(f'the per-entry ridge must be one real number, not {lam_n!r}')
+    return args + (_RHS_CODES[rhs], float(lam_n))
+
+
+def als_rows(h, V, scale=False, rhs='values', base=None, lam_n=0.0, rows=None):
+    """
+    One ALS half-step: for each row i of rows = (begin, end) (None: all rows) solve
+        (base + sum_e w_e v_j v_j^T + lam_n n_i I) u_i = sum_e c_e v_j
+    over the row's n_i stored entries e = (i, j) in storage order, v_j = V[j, :]: (U float64 [end - begin, k], info int32).
+    w is 1 or (scale=True) the entry's value; c is 1 (rhs='ones'), the value ('values') or 1 + the value
+    ('one_plus_values'); a structure-only matrix counts every value as 1.0.  The block is csrk_gram_rows', built and
+    factorised in registers and never written; the solve is solve_blocks' (include/csrk.h, rules A and S).  info[i] is 0, or
+    j + 1 for the first pivot j of row i that is not positive.  Not a reference entry point.
+    """
+    V, ldv, k, code, rb, re_, base, rcode, lam_n = als_args(h, V, rhs, base, lam_n, rows)
+    out, info = _out((re_ - rb, k), np.float64), np.zeros(re_ - rb, np.int32)
+    _call(lib.csrk_als_rows, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), rcode, ptr(base), lam_n, ptr(out), k,
+          ptr(info))
+    return out, info
 
 
 def set_spgemm_order(order):

@@ -321,6 +321,75 @@ CSRK_API int csrk_gram_rows_device(csrk_handle_t h, int32_t row_begin, int32_t r
 /* Diagnostics: the five limits of rule 8 above, in its order;  n <= 5.  No device is touched. */
 CSRK_API int csrk_gram_limits(int64_t *out, int n);
 
+/* ---- the ALS half-step: solve each row's normal equations ----------------------------------------
+ * Not reference entry points.  csrk_solve_blocks solves n packed symmetric k x k systems; csrk_als_rows builds each row's
+ * system (csrk_gram_rows' block, a ridge, the right-hand side) in one pass over the row's entries and solves it on the
+ * chip: k float64 per row are written, the k x k block never is.  Both run one device routine (csrc/als.hip), so
+ * csrk_als_rows equals csrk_gram_rows + the ridge + csrk_solve_blocks bit for bit.  All arithmetic is float64;
+ * fma(-a, b, c) is round(c - a b), one rounding.
+ *
+ * S. The solve.  Per system: G (k x k, packed row-major, ONLY THE LOWER TRIANGLE p >= q IS READ) and b[k] in, x[k] and an
+ *    info word out.  An LDL^T factorisation with a fixed order of operations:
+ *        for j = 0 .. k-1:
+ *            for i = j .. k-1:
+ *                a = G[i][j];   for t = 0 .. j-1 (ascending):  a = fma(-L[i][t], C[j][t], a);   C[i][j] = a
+ *            d_j = C[j][j];   r_j = 1.0 / d_j                       (one correctly rounded division per column)
+ *            for i = j+1 .. k-1:  L[i][j] = round(C[i][j] * r_j)
+ *        forward:  for i = 0 .. k-1:   z_i = b[i];  for t = 0 .. i-1 ascending:    z_i = fma(-L[i][t], z_t, z_i)
+ *        scale:    y_i = round(z_i * r_i)
+ *        back:     for i = k-1 .. 0:   x_i = y_i;   for t = k-1 .. i+1 descending: x_i = fma(-L[t][i], x_t, x_i)
+ *   S1. No pivoting, no square root, no special case.  A zero, negative or NaN pivot goes through IEEE arithmetic and the
+ *       system's x becomes Inf or NaN; info = j + 1 for the first j where d_j > 0 is false, 0 when every pivot is positive.
+ *   S2. Every element of C, L, z and x is one serial chain in the order above.  Parallelism is over systems and over
+ *       elements, never inside a chain; no float atomics, no split sums.  The result depends on (G's lower triangle, b, k)
+ *       only: not on the launch geometry, the k class, ldb, ldx, the alignment, the stream or repeated calls.
+ *   S3. csrk_solve_blocks: G is n * k * k float64, system s at G + s k k; b[s * ldb + p], x[s * ldx + p], ldb, ldx >= k in
+ *       elements; info is int32[n] or NULL.  x may not overlap G or b.  CSRK_ERR_INVALID: n < 0, k < 1, ldb < k, ldx < k,
+ *       or a NULL G, b or x when n > 0.  CSRK_ERR_UNSUPPORTED: k above csrk_als_limits' out[0] (at least 128).  n = 0:
+ *       CSRK_OK, nothing launched.  A refused call writes neither x nor info.
+ *
+ * A. The fused row.  For row i of [row_begin, row_end), its entries e = (i, j) in storage order, n_i of them:
+ *   A1. Block.  G is exactly csrk_gram_rows' rule 2, with the same V, panel_type, scale, base and lower triangle.
+ *   A2. Ridge.  After the chain, for each p: G[p][p] = fma(lam_n, (double)n_i, G[p][p]).  lam_n is one double for every row;
+ *       0.0 leaves finite values as they are.  lam_n * n_i is the count-weighted ridge of explicit ALS; base carries
+ *       lambda I and, for implicit feedback, V^T V.
+ *   A3. Right-hand side.  b[p] starts at +0.0 and takes one step per entry, in storage order:
+ *           b[p] = fma(c_e, V[j][p], b[p])
+ *       with c_e by rhs_mode: CSRK_ALS_RHS_ONES 1.0; CSRK_ALS_RHS_VALUES the entry's value, float32 widened exactly, 1.0 for
+ *       a structure-only matrix (csrk_sddmm's rule); CSRK_ALS_RHS_ONE_PLUS round(1.0 + that value) (values stored as
+ *       confidence - 1).
+ *   A4. Solve and output.  Rule S on (G, b); out[(i - row_begin) * ldo + p] = x[p], ldo >= k in elements, so the caller
+ *       may write straight into a wider factor panel (the other columns of out are not touched); info[i - row_begin] is
+ *       int32, and info may be NULL.
+ *   A5. Empty rows solve base x = 0: x is +0.0 everywhere when base is positive definite (info 0).  With base NULL the
+ *       first pivot is +0.0: info is 1 and every x is NaN.
+ *   A6. The rest is csrk_gram_rows': unsorted and repeated columns are just more entries; NaN and Inf reach only the rows
+ *       that reference them; V is read in 16-B pieces when its pointer, ldv and k allow, else by element -- the same bits;
+ *       offsets are 64-bit; h is not modified and keeps its plans; the device form allocates nothing and never
+ *       synchronises the host; a refused call writes neither out nor info.
+ *   A7. CSRK_ERR_INVALID: every refusal of csrk_gram_rows (its rule 7), ldo < k, an unknown rhs_mode, a NULL out when
+ *       there are rows.  CSRK_ERR_UNSUPPORTED: k above csrk_als_limits' out[0] (at least 128).  row_begin == row_end:
+ *       CSRK_OK, nothing launched.
+ *   Limits (csrk_als_limits): out[0] = the largest k; [1] = the entries of a row staged through LDS per step; then the k
+ *   classes, ascending: [2] = the largest k at which 16 lanes take a system, [3] = a wavefront, [4] = a workgroup with one
+ *   4 x 4 tile per thread (above it, up to three).  By S2 no class changes a bit.
+ * Host forms: host pointers in and out (panels cross packed; synchronous). */
+enum { CSRK_ALS_RHS_ONES = 0, CSRK_ALS_RHS_VALUES = 1, CSRK_ALS_RHS_ONE_PLUS = 2 };
+CSRK_API int csrk_solve_blocks(int64_t n, int32_t k, const double *G, const double *b, int64_t ldb, double *x,
+                               int64_t ldx, int32_t *info);
+CSRK_API int csrk_als_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *V, int64_t ldv, int32_t k,
+                           int panel_type, int scale, int rhs_mode, const double *base, double lam_n, double *out,
+                           int64_t ldo, int32_t *info);
+/* Device forms: every pointer in HBM, launched on `stream` (NULL = the default stream); nothing is allocated and the host
+ * is not synchronised. */
+CSRK_API int csrk_solve_blocks_device(int64_t n, int32_t k, const double *d_G, const double *d_b, int64_t ldb,
+                                      double *d_x, int64_t ldx, int32_t *d_info, void *stream);
+CSRK_API int csrk_als_rows_device(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *d_V, int64_t ldv,
+                                  int32_t k, int panel_type, int scale, int rhs_mode, const double *d_base,
+                                  double lam_n, double *d_out, int64_t ldo, int32_t *d_info, void *stream);
+/* Diagnostics: the five limits above, in that order;  n <= 5.  No device is touched. */
+CSRK_API int csrk_als_limits(int64_t *out, int n);
+
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).
  * Bit-exact with the reference's stable counting sort: output rowptrs keep the input

@@ -100,6 +100,11 @@ SIGNATURES = {
     'csrk_als_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, _vp, _i64, _vp,
                                     _vp]),
     'csrk_als_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_topk_scores': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp, _i64,
+                                _vp]),
+    'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,
+                                       _i64, _vp, _vp]),
+    'csrk_topk_scores_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

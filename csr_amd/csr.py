@@ -439,6 +439,27 @@ class CSR:
         blocks = [top(blk) for blk in self._row_blocks(K.max_nnz)]
         return blocks[0] if len(blocks) == 1 else CSR._assemble_shards(blocks)
 
+    def topk_scores(self, U, V, n, *, min_score=None, rows=None, exclude=True):
+        """
+        Recommendations from a factor model, with this matrix as the pairs already seen: for each row i of rows =
+        (begin, end) (None: all rows) the n items j with the largest score dot(U[i, :], V[j, :]) among the columns row i does
+        not store (exclude=False: among all columns) whose score is not below min_score (None: no threshold).  Returns
+        (items int32 [m, n], scores float64 [m, n], counts int32 [m]): best first, padded with item -1 and score -inf
+        beyond counts[i].  U [nrows x k] and V [ncols x k] are both float32 or both float64; every score is one chain of k
+        fused multiply-adds in float64, NaN ranks above +Inf, -0.0 ties with +0.0 and ties go to the smaller item, so the
+        result is a function of the inputs, bit for bit (include/csrk.h, csrk_topk_scores).  The dense block of scores is
+        never formed.  This matrix must be canonical (sort_rows / coalesce); its values are not read.  Runs on the device
+        only.  Not a reference entry point.
+        """
+        K, fn = self._ext('topk_scores')
+        K.topk_scores_args(self, U, V, n, min_score, rows)
+        if not exclude:      # (the panels have this matrix's shape: checked above)
+            return fn(None, U, V, n, min_score, rows)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            return fn(h, U, V, n, min_score, rows)
+
     # ---- two matrices entry by entry -----------------------------------------------------------
     def _combine(self, other, op, alpha=1.0, beta=1.0):
         """

@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
-is_canonical.
+is_canonical, topk_scores.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -911,6 +911,85 @@ def als_rows(h, V, scale=False, rhs='values', base=None, lam_n=0.0, rows=None):
     _call(lib.csrk_als_rows, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), rcode, ptr(base), lam_n, ptr(out), k,
           ptr(info))
     return out, info
+
+
+def topk_scores_limits():
+    "(largest k, largest n, rows per workgroup, items per tile, factors per LDS chunk, list entries per row for n <= 32)"
+    out = (C.c_int64 * 6)()
+    check(lib.csrk_topk_scores_limits(out, 6))
+    return tuple(out)
+
+
+def topk_scores_args(h, U, V, n, min_score=None, rows=None):
+    """
+    (U, ldu, V, ldv, n_items, k, panel code, n, min_score, row_begin, row_end) as the library takes them; ValueError for
+    anything it would refuse as invalid.  h is anything with nrows and ncols (a handle or a CSR: the seen pairs) or None
+    (nothing seen: U's rows and V's rows give the shape); no library call is made.
+    """
+    import numbers
+    U, V = np.asarray(U), np.asarray(V)
+    if U.ndim != 2 or V.ndim != 2:
+        raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
+    if U.dtype != V.dtype:
+        raise ValueError(f'U and V must have the same dtype, not {U.dtype} and {V.dtype}')
+    if U.dtype not in _PANEL_CODES:
+        raise ValueError(f'U and V must be float32 or float64, not {U.dtype}')
+    if U.shape[1] != V.shape[1]:
+        raise ValueError(f'U and V have {U.shape[1]} and {V.shape[1]} columns')
+    if U.shape[1] == 0:
+        raise ValueError('panels have no columns (k = 0)')
+    nrows = U.shape[0] if h is None else int(h.nrows)
+    n_items = V.shape[0] if h is None else int(h.ncols)
+    if nrows > np.iinfo('i4').max or n_items > np.iinfo('i4').max:
+        raise ValueError(f'{nrows} rows or {n_items} items are more than 32-bit indices hold')
+    U, ldu = _panel(U, nrows, 'U')
+    V, ldv = _panel(V, n_items, 'V')
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+        raise ValueError(f'n must be an integer, not {n!r}')
+    if n < 1:
+        raise ValueError(f'n must be at least 1, not {n}')
+    if isinstance(min_score, bool) or not (min_score is None or isinstance(min_score, numbers.Real)):
+        raise ValueError(f'min_score must be one real number or None, not {min_score!r}')
+    ms = -np.inf if min_score is None else float(min_score)
+    if ms != ms:
+        raise ValueError('min_score is NaN')
+    if rows is None:
+        rb, re_ = 0, nrows
+    else:
+        try:
+            rb, re_ = rows
+        except (TypeError, ValueError):
+            raise ValueError(f'rows must be (begin, end), not {rows!r}') from None
+        for v in (rb, re_):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f'rows must be two integers, not {rows!r}')
+        rb, re_ = int(rb), int(re_)
+        if not 0 <= rb <= re_ <= nrows:
+            raise ValueError(f'rows ({rb}, {re_}) is not a range within the {nrows} rows')
+    return U, ldu, V, ldv, n_items, U.shape[1], _PANEL_CODES[U.dtype], min(int(n), np.iinfo('i4').max), ms, rb, re_
+
+
+def topk_scores(h, U, V, n, min_score=None, rows=None):
+    """
+    Recommendations from factors: for each row i of rows = (begin, end) (None: all rows) the n best items j by the score
+    dot(U[i, :], V[j, :]) among those the handle's matrix does not store in row i (h = None: nothing is left out) and whose
+    score is not below min_score (None: no threshold) -- (items int32 [m, n], scores float64 [m, n], counts int32 [m]),
+    best first, padded with item -1 and score -inf beyond counts[i].  U [nrows x k] and V [ncols x k] are both float32 or
+    both float64; a score is one chain of k fused multiply-adds in float64; NaN ranks above +Inf, -0.0 ties with +0.0, ties
+    go to the smaller item (include/csrk.h, csrk_topk_scores).  The handle's matrix must be canonical.  Not a reference
+    entry point.
+    """
+    U, ldu, V, ldv, n_items, k, code, n, ms, rb, re_ = topk_scores_args(h, U, V, n, min_score, rows)
+    m = re_ - rb
+    lim = topk_scores_limits()
+    if k > lim[0] or n > lim[1]:      # the library's refusal, before any result array is made
+        check(lib.csrk_topk_scores(0 if h is None else _live(h), rb, re_, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, None, n,
+                                   None, n, None))
+        raise ValueError(f'k = {k} or n = {n} is above the limits {lim[:2]}')
+    items, scores, counts = np.empty((m, n), np.int32), np.empty((m, n), np.float64), np.zeros(m, np.int32)
+    _call(lib.csrk_topk_scores, 0 if h is None else _live(h), rb, re_, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, ptr(items),
+          n, ptr(scores), n, ptr(counts))
+    return items, scores, counts
 
 
 def set_spgemm_order(order):

@@ -551,6 +551,63 @@ CSRK_API int csrk_coalesce_last_route(int *route);
  * csrk_combine and csrk_coalesce use) and dropped by whatever rewrites the handle's columns (csrk_order_columns). */
 CSRK_API int csrk_is_canonical(csrk_handle_t h, int *canonical, int32_t *first_bad_row);
 
+/* ---- topk_scores: each row's n_top best unseen items from the factors U and V ----------------------
+ * Not a reference entry point: the last step of the ALS path (csrk_als_rows trains, csrk_sddmm gives loss and residuals):
+ * for every row of a range, score ALL items as U[i] . V[j], leave out the (row, item) pairs `seen` stores and the scores
+ * below a threshold, keep the n_top best.  The rows x n_items block of scores is never stored.
+ *   1. Operands.  U is dense row-major, indexed by the ABSOLUTE row i of [row_begin, row_end): U[i][t] at U + i * ldu + t.
+ *      V is dense row-major [n_items x k].  Both are float32 or both float64 (panel_type = CSRK_VAL_F32 / CSRK_VAL_F64);
+ *      ldu, ldv >= k in elements.  `seen` is 0 (nothing is excluded) or a handle; with a handle n_items must equal its
+ *      ncols and row_end <= its nrows, and it must be canonical (every row strictly ascending in column): the check is
+ *      csrk_is_canonical's remembered one, and the refusal names the first bad row as csrk_combine's does.  Its values are
+ *      never read (a structure-only handle will do), either pointer width is taken, and its column indices are compared,
+ *      never used as addresses.  `seen` is not modified and keeps its plans.
+ *   2. Score.  For row i and item j:   s = +0.0;  for t = 0 .. k-1 ascending:  s = fma(U[i][t], V[j][t], s)
+ *      -- one serial chain of fused multiply-adds in float64, float32 elements widened exactly first.  Parallelism is over
+ *      (row, item) pairs, never inside a chain: no split sums, no float atomics, no matrix instructions.
+ *   3. Candidates.  Item j is a candidate of row i unless `seen` stores (i, j) or s < min_score is true: NaN passes, and
+ *      min_score = -INFINITY is no threshold (csrk_topk_rows' rule 1).
+ *   4. Selection.  Of a row's candidates the first n_top in the total order of csrk_topk_rows (its rule 2) are kept, best
+ *      first: larger score first; any NaN above +Inf and all NaNs tied; -0.0 ties +0.0; TIES GO TO THE SMALLER ITEM INDEX.
+ *      Items are distinct, so the order is strict and the result unique.
+ *   5. Output.  counts[i - row_begin] = the number kept; for r < that, items[(i - row_begin) * ldi + r] is the item index
+ *      and scores[(i - row_begin) * lds + r] the chain's bits unchanged (-0.0 stays -0.0); for count <= r < n_top the
+ *      padding is item -1 and score -INFINITY.  ldi, lds >= n_top in elements; columns at or beyond n_top are not touched.
+ *      counts may be NULL.
+ *   6. Invariance.  An output depends only on U's row i, V, row i of `seen`, k, the panel type, n_top and min_score: not on
+ *      the row range asked for, the strides, the alignment, the pointer width, the stream, the launch geometry or repeated
+ *      calls.  U and V are read in 16-B pieces when both pointers, both strides and k allow it, else by element: the same
+ *      bits either way.
+ *   7. Special values.  IEEE throughout; no path skips a zero.  A NaN or Inf in U's row i reaches row i only.  A NaN in V's
+ *      row j reaches every row for which j is not seen, and no other output bit.  A NaN that the chain creates (Inf - Inf,
+ *      0 * Inf) has its position specified, not its sign or payload.
+ *   8. Device form.  Allocates nothing and does not synchronise the host, with one exception: the first call that asks a
+ *      handle whether it is canonical looks at its rows (rule 1; csrk_is_canonical beforehand takes that look).  One
+ *      workgroup takes a block of rows across all items and keeps the rows' running lists on the chip: no scratch memory.
+ *      The items of a small row range are not split across workgroups.  The host form sends the panels packed (the rows of
+ *      the range only) and is synchronous.
+ *   9. Refusals; a refused call writes nothing.  CSRK_ERR_INVALID: k < 1, n_top < 1, n_items < 0; ldu < k, ldv < k,
+ *      ldi < n_top, lds < n_top; an unknown panel_type; a NaN min_score; row_begin < 0 or row_begin > row_end; with a handle,
+ *      row_end > nrows or n_items != ncols; a `seen` that is not canonical or not a handle; NULL items or scores when there
+ *      are rows; a NULL U when there are rows; a NULL V when there are rows and items; a pointer not aligned to its
+ *      element.  CSRK_ERR_UNSUPPORTED: k above out[0] of csrk_topk_scores_limits (at least 256), n_top above out[1] (at
+ *      least 128).  row_begin == row_end: CSRK_OK, nothing launched.  n_items == 0: CSRK_OK, counts 0 and padding only.
+ *      n_top may exceed n_items.
+ *  10. Limits (csrk_topk_scores_limits): out[0] = the largest k; [1] = the largest n_top; [2] = the rows of a workgroup;
+ *      [3] = the items of a tile; [4] = the factors staged through LDS per chunk (a chain crosses chunks in order); [5] = the
+ *      entries a row's running list holds between compactions when n_top <= 32 (n_top + 16 above that);  n <= 6.  By rule
+ *      6 none of them changes a bit. */
+CSRK_API int csrk_topk_scores(csrk_handle_t seen, int32_t row_begin, int32_t row_end, const void *U, int64_t ldu,
+                              const void *V, int64_t ldv, int32_t n_items, int32_t k, int panel_type, int32_t n_top,
+                              double min_score, int32_t *items, int64_t ldi, double *scores, int64_t lds, int32_t *counts);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream). */
+CSRK_API int csrk_topk_scores_device(csrk_handle_t seen, int32_t row_begin, int32_t row_end, const void *d_U, int64_t ldu,
+                                     const void *d_V, int64_t ldv, int32_t n_items, int32_t k, int panel_type,
+                                     int32_t n_top, double min_score, int32_t *d_items, int64_t ldi, double *d_scores,
+                                     int64_t lds, int32_t *d_counts, void *stream);
+/* Diagnostics: the six limits of rule 10, in its order;  n <= 6.  No device is touched. */
+CSRK_API int csrk_topk_scores_limits(int64_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

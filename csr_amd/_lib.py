@@ -105,6 +105,9 @@ SIGNATURES = {
     'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,
                                        _i64, _vp, _vp]),
     'csrk_topk_scores_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_rank_entries': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp]),
+    'csrk_rank_entries_device': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp, _vp]),
+    'csrk_rank_entries_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

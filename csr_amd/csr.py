@@ -460,6 +460,37 @@ class CSR:
         with releasing(K.to_handle(self), K) as h:
             return fn(h, U, V, n, min_score, rows)
 
+    def rank_entries(self, U, V, test, *, rows=None, exclude=True, return_scores=False):
+        """
+        Offline evaluation of a factor model, with this matrix as the pairs already seen and `test`, a CSR of the same
+        shape, as the held-out pairs: for every entry (i, j) of `test` in rows = (begin, end) (None: all rows), in storage
+        order, the position j takes in row i's full ranking of the columns row i does not store here (exclude=False: of all
+        columns) -- the number of such columns c != j whose score dot(U[i, :], V[c, :]) comes before j's.  Returns ranks
+        (int32, one per entry), or (ranks, scores float64) with return_scores=True.  Scores and order are topk_scores': one
+        chain of k fused multiply-adds in float64, NaN above +Inf, -0.0 tied with +0.0, ties to the smaller column, so an
+        entry of rank r < n is topk_scores' items[i][r] and every bit is a function of the inputs (include/csrk.h,
+        csrk_rank_entries).  Hit rate, MRR and nDCG follow from the ranks; for percentile rank and AUC the number of
+        candidates of row i is ncols - row_nnzs()[i] (ncols with exclude=False).  This matrix must be canonical (sort_rows /
+        coalesce); `test` may hold its columns in any order and more than once; the values of neither are read.  The dense
+        block of scores is never formed.  Runs on the device only.  Not a reference entry point.
+        """
+        K, fn = self._ext('rank_entries')
+        if not isinstance(test, CSR):
+            raise ValueError(f'test must be a CSR, not {type(test).__name__}')
+        K.rank_entries_args(self, test, U, V, rows)
+        for m in ((self, test) if exclude else (test,)):
+            if m.nnz > K.max_nnz:
+                raise ValueError('CSR size {} exceeds max nnz {}'.format(m.nnz, K.max_nnz))
+        with releasing(K.to_handle(test), K) as t_h:
+            if not exclude:
+                ranks, scores = fn(None, t_h, U, V, rows)
+            elif test is self:                   # one device copy serves both sides
+                ranks, scores = fn(t_h, t_h, U, V, rows)
+            else:
+                with releasing(K.to_handle(self), K) as s_h:
+                    ranks, scores = fn(s_h, t_h, U, V, rows)
+        return (ranks, scores) if return_scores else ranks
+
     # ---- two matrices entry by entry -----------------------------------------------------------
     def _combine(self, other, op, alpha=1.0, beta=1.0):
         """

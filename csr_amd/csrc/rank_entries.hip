@@ -1,0 +1,422 @@
+// Offline evaluation of a factor model for libcsrk on gfx950: csrk_rank_entries gives, for every entry (i, j) of a CSR
+// matrix `test`, the number of items that row i has not seen and that come before j in the row's full ranking by
+// U[i] . V[c] (the contract is in include/csrk.h).  The rows x n_items block of scores never leaves the chip.
+//
+// Score.  The tile of topk_scores.hip (score_tile.h): a 256-thread workgroup owns 64 rows of U and sweeps V in tiles of 64
+// items, 4 x 4 serial chains of fused multiply-adds per thread, the panels staged through LDS 16 factors at a time in two
+// buffers.  Nothing is summed in pieces, so a score has the bits csrk_topk_scores gives it.
+//
+// Counting.  A workgroup takes up to RE_T (32) test entries of each of its rows per SWEEP of V:
+//   pre-pass   one wavefront per row: lane x runs the chain of the row's x-th entry straight from the panels (the same k
+//              fused multiply-adds in the same order as the tile's chain: the same bits), writes the score out, and the
+//              wavefront orders the entries by (key descending, item ascending) all-pairs, as ts_compact does, keeping
+//              every entry's place in the row;
+//   sweep      every score of a tile that comes before the row's LAST listed entry (one comparison against registers:
+//              most scores of a row whose held-out items rank high end here) finds by binary search the first listed
+//              entry m it comes before and adds one to hist[row][m], an integer LDS atomic.  (key, item) pairs equal to a
+//              listed entry's -- the entry's own item -- come before nothing they tie with, so no item counts itself;
+//   seen       the sweep counted every item.  One wavefront per row then runs the chain of every entry `seen` stores in
+//              the row and takes the same step with -1.  Integers: the order of the atomics decides nothing;
+//   finish     a prefix sum over hist[row][0 .. m] is the rank of the entry listed at m, written to its place.
+// A row with more than RE_T entries is swept again per RE_T of them; the number of sweeps of a workgroup is the largest
+// its rows need, found in the kernel.  No scratch memory, no host round trip.
+//
+// LDS: 33 KiB of staging lines + 43.5 KiB of lists and counters = 76.5 KiB per workgroup, two workgroups per CU.
+#include <cstdlib>
+
+#include "common.h"
+#include "score_tile.h"
+
+namespace csrk {
+
+constexpr int RE_T = 32;                        // test entries of a row per sweep
+constexpr int RE_LDT = RE_T + 1;                // list line (rows fall into different banks)
+constexpr int RE_K_MAX = 1024;
+constexpr int32_t RE_BAD_ITEM = 0x7fffffff;     // listed for a test column outside [0, n_items): never dereferenced
+static_assert(RE_T <= WAVE, "one lane per listed entry");
+
+// does (key ka, item ja) come before (kb, jb) in csrk_topk_scores' order?
+__device__ __forceinline__ bool re_before(uint64_t ka, int32_t ja, uint64_t kb, int32_t jb) { return ka > kb || (ka == kb && ja < jb); }
+
+// csrk_topk_scores' rule 2 for one pair, straight from the panels
+template <class T> __device__ __forceinline__ double re_chain(const T *__restrict__ u, const T *__restrict__ v, int k)
+{
+    double s = 0.0;
+    for (int t = 0; t < k; t++) s = __builtin_fma((double)u[t], (double)v[t], s);
+    return s;
+}
+
+// the first of the n listed entries (best first) that (ks, j) comes before; n when there is none
+__device__ __forceinline__ int re_slot(const uint64_t *__restrict__ sk, const int32_t *__restrict__ si, int n, uint64_t ks, int32_t j)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (re_before(ks, j, sk[mid], si[mid]))
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int64_t re_ptr(const void *__restrict__ rp, int ptr64, int64_t row)
+{
+    return ptr64 ? ((const int64_t *)rp)[row] : (int64_t)((const int32_t *)rp)[row];
+}
+
+template <class T, bool WIDE>
+__global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__restrict__ seen_rp, int seen_ptr64,
+                                                                 const int32_t *__restrict__ seen_ci, const void *__restrict__ test_rp,
+                                                                 int test_ptr64, const int32_t *__restrict__ test_ci, int32_t row_begin,
+                                                                 int32_t nrows, const T *__restrict__ U, int64_t ldu,
+                                                                 const T *__restrict__ V, int64_t ldv, int32_t n_items, int32_t k, int count,
+                                                                 int32_t *__restrict__ ranks, double *__restrict__ scores)
+{
+    constexpr int PER = WIDE ? 16 / (int)sizeof(T) : 1;
+    __shared__ __attribute__((aligned(16))) double su2[2][TS_KC][TS_LD];      // two buffers: one barrier per chunk
+    __shared__ __attribute__((aligned(16))) double sv2[2][TS_KC][TS_LD];
+    __shared__ uint64_t s_key[TS_ROWS][RE_LDT];                   // a row's listed entries, best first
+    __shared__ int32_t s_item[TS_ROWS][RE_LDT];
+    __shared__ int32_t s_pos[TS_ROWS][RE_LDT];                    // the place of each in this sweep's part of the row
+    __shared__ int32_t s_hist[TS_ROWS][RE_LDT];
+    __shared__ int64_t s_t0[TS_ROWS], s_t1[TS_ROWS], s_e0[TS_ROWS], s_e1[TS_ROWS];
+    __shared__ int32_t s_cnt[TS_ROWS];
+    __shared__ unsigned long long s_nsw;
+
+    const int tid = threadIdx.x, ty = tid / (TS_TILE / TS_B), tx = tid % (TS_TILE / TS_B);
+    const int lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int64_t r0 = (int64_t)blockIdx.x * TS_ROWS;             // the block's first row, relative to row_begin
+    const int64_t nvalid = (int64_t)nrows - r0 < TS_ROWS ? (int64_t)nrows - r0 : TS_ROWS;
+    const int64_t base = re_ptr(test_rp, test_ptr64, row_begin);
+
+    if (tid == 0) s_nsw = 0;
+    __syncthreads();
+    if (tid < TS_ROWS) {
+        int64_t t0 = 0, t1 = 0, e0 = 0, e1 = 0;
+        if (tid < nvalid) {
+            const int64_t row = (int64_t)row_begin + r0 + tid;
+            t0 = re_ptr(test_rp, test_ptr64, row);
+            t1 = re_ptr(test_rp, test_ptr64, row + 1);
+            if (seen_rp) {
+                e0 = re_ptr(seen_rp, seen_ptr64, row);
+                e1 = re_ptr(seen_rp, seen_ptr64, row + 1);
+            }
+        }
+        if (t1 < t0) t1 = t0;
+        s_t0[tid] = t0, s_t1[tid] = t1, s_e0[tid] = e0, s_e1[tid] = e1;
+        if (t1 > t0) atomicMax(&s_nsw, (unsigned long long)((t1 - t0 + RE_T - 1) / RE_T));
+    }
+    __syncthreads();
+    const int64_t nsw = (int64_t)s_nsw;
+    if (nsw == 0) return;                                         // no test entry in these rows
+    uint64_t sink = 0;
+
+    for (int64_t c = 0; c < nsw; c++) {
+        // ---- pre-pass: this sweep's entries of every row, scored and ordered (one wavefront per row)
+        for (int r = w; r < TS_ROWS; r += TS_THREADS / WAVE) {
+            const int64_t first = s_t0[r] + c * RE_T, left = s_t1[r] - first;
+            const int n = left <= 0 ? 0 : (left < RE_T ? (int)left : RE_T);
+            uint64_t key = 0;
+            int32_t item = RE_BAD_ITEM;
+            if (lane < RE_LDT) s_hist[r][lane] = 0;
+            if (lane < n) {
+                const int32_t j = test_ci[first + lane];
+                double s = __longlong_as_double(0x7ff8000000000000ll);
+                if (j >= 0 && j < n_items) {
+                    s = re_chain<T>(U + (r0 + r) * ldu, V + (int64_t)j * ldv, k);
+                    key = topk_key(s);
+                    item = j;
+                }
+                if (scores) scores[first + lane - base] = s;
+                s_key[r][lane] = key;
+                s_item[r][lane] = item;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            int rank = 0;
+            for (int y = 0; y < n; y++) {
+                const uint64_t ky = s_key[r][y];
+                const int32_t iy = s_item[r][y];
+                rank += (re_before(ky, iy, key, item) || (ky == key && iy == item && y < lane)) ? 1 : 0;
+            }
+            // the wavefront has read the list before any lane rewrites it (LDS operations of one wavefront complete in issue order)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (lane < n) {
+                s_key[r][rank] = key;
+                s_item[r][rank] = item;
+                s_pos[r][rank] = lane;
+            }
+            if (lane == 0) s_cnt[r] = n;
+        }
+        __syncthreads();
+
+        // a row's last listed entry: a score that does not come before it comes before none (no entry: nothing does)
+        int cnt[TS_B];
+        uint64_t lastk[TS_B];
+        int32_t lasti[TS_B];
+#pragma unroll
+        for (int i = 0; i < TS_B; i++) {
+            const int r = TS_B * ty + i;
+            cnt[i] = s_cnt[r];
+            lastk[i] = cnt[i] ? s_key[r][cnt[i] - 1] : ~0ull;
+            lasti[i] = cnt[i] ? s_item[r][cnt[i] - 1] : -1;
+        }
+
+        // ---- sweep: the product of topk_scores.hip, tile by tile
+        TsUnits<T, PER> fu, fv;                                   // the chunk after the one in use
+        if (n_items > 0) {
+            ts_fetch<T, PER>(fu, U, ldu, r0, nvalid, 0, k, tid);
+            ts_fetch<T, PER>(fv, V, ldv, 0, (int64_t)n_items, 0, k, tid);
+        }
+        int buf = 0;
+        for (int64_t j0 = 0; j0 < n_items; j0 += TS_TILE) {
+            double acc[TS_B][TS_B];
+#pragma unroll
+            for (int i = 0; i < TS_B; i++)
+#pragma unroll
+                for (int jj = 0; jj < TS_B; jj++) acc[i][jj] = 0.0;
+            for (int t0 = 0; t0 < k; t0 += TS_KC, buf ^= 1) {
+                double (*__restrict__ su)[TS_LD] = su2[buf], (*__restrict__ sv)[TS_LD] = sv2[buf];
+                ts_put<T, PER>(fu, su, tid);
+                ts_put<T, PER>(fv, sv, tid);
+                __syncthreads();      // (one per chunk: whoever writes this buffer again has passed the next chunk's barrier, after everyone's use of it)
+                {
+                    const bool more = t0 + TS_KC < k;             // the next chunk: of this tile, or the first of the next tile
+                    const int64_t jn = more ? j0 : j0 + TS_TILE;
+                    if (jn < n_items) {
+                        ts_fetch<T, PER>(fu, U, ldu, r0, nvalid, more ? t0 + TS_KC : 0, k, tid);
+                        ts_fetch<T, PER>(fv, V, ldv, jn, (int64_t)n_items - jn, more ? t0 + TS_KC : 0, k, tid);
+                    }
+                }
+                const int kc = k - t0 < TS_KC ? k - t0 : TS_KC;
+                if (kc == TS_KC) {
+#pragma unroll
+                    for (int t = 0; t < TS_KC; t++) {
+                        const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
+                        const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                        const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+                        for (int i = 0; i < TS_B; i++)
+#pragma unroll
+                            for (int jj = 0; jj < TS_B; jj++) acc[i][jj] = __builtin_fma(u[i], v[jj], acc[i][jj]);
+                    }
+                } else {
+                    for (int t = 0; t < kc; t++) {
+                        const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
+                        const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                        const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+                        for (int i = 0; i < TS_B; i++)
+#pragma unroll
+                            for (int jj = 0; jj < TS_B; jj++) acc[i][jj] = __builtin_fma(u[i], v[jj], acc[i][jj]);
+                    }
+                }
+            }
+            if (!count) {                                         // diagnostic: the product alone
+#pragma unroll
+                for (int i = 0; i < TS_B; i++)
+#pragma unroll
+                    for (int jj = 0; jj < TS_B; jj++) sink ^= (uint64_t)__double_as_longlong(acc[i][jj]);
+                continue;
+            }
+#pragma unroll
+            for (int i = 0; i < TS_B; i++)
+#pragma unroll
+                for (int jj = 0; jj < TS_B; jj++) {
+                    const int64_t j = j0 + TS_B * tx + jj;
+                    const uint64_t ks = topk_key(acc[i][jj]);
+                    if (j < n_items && re_before(ks, (int32_t)j, lastk[i], lasti[i])) {
+                        const int r = TS_B * ty + i;
+                        atomicAdd(&s_hist[r][re_slot(s_key[r], s_item[r], cnt[i], ks, (int32_t)j)], 1);      // (a slot < cnt[i]: it comes before the last)
+                    }
+                }
+        }
+        __syncthreads();
+
+        // ---- the items `seen` stores were counted like any other: take them out again (one wavefront per row)
+        if (seen_rp && count)
+            for (int r = w; r < nvalid; r += TS_THREADS / WAVE) {
+                const int n = s_cnt[r];
+                if (!n) continue;
+                const uint64_t lk = s_key[r][n - 1];
+                const int32_t li = s_item[r][n - 1];
+                for (int64_t e = s_e0[r] + lane; e < s_e1[r]; e += WAVE) {
+                    const int32_t j = seen_ci[e];
+                    if (j < 0 || j >= n_items) continue;          // (no item: the sweep did not count it)
+                    const uint64_t ks = topk_key(re_chain<T>(U + (r0 + r) * ldu, V + (int64_t)j * ldv, k));
+                    if (re_before(ks, j, lk, li)) atomicSub(&s_hist[r][re_slot(s_key[r], s_item[r], n, ks, j)], 1);
+                }
+            }
+        __syncthreads();
+
+        // ---- finish: the entry listed at m is preceded by what fell into slots 0 .. m
+        if (count && tid < nvalid) {
+            const int n = s_cnt[tid];
+            const int64_t first = s_t0[tid] + c * RE_T - base;
+            int32_t run = 0;
+            for (int m = 0; m < n; m++) {
+                run += s_hist[tid][m];
+                ranks[first + s_pos[tid][m]] = s_item[tid][m] == RE_BAD_ITEM ? -1 : run;
+            }
+        }
+        __syncthreads();
+    }
+    if (!count && sink == 0x7ff8c0dec0dec0deull && tid < nvalid && s_t1[tid] > s_t0[tid]) ranks[s_t0[tid] - base] = 0;      // (keeps the product alive)
+}
+
+// the refusals that need no handle come first: they are answered whatever the handles are
+static int re_scalars(int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t k, int panel_type)
+{
+    CSRK_REQUIRE(k >= 1, "rank_entries: k must be at least 1 (k=%d)", k);
+    CSRK_REQUIRE(ldu >= k && ldv >= k, "rank_entries: bad panel geometry k=%d ldu=%lld ldv=%lld", k, (long long)ldu, (long long)ldv);
+    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64,
+                 "rank_entries: panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d", panel_type);
+    CSRK_REQUIRE(row_begin >= 0 && row_begin <= row_end, "rank_entries: bad row range [%d, %d)", row_begin, row_end);
+    if (k > RE_K_MAX) {
+        set_error("csrk_rank_entries: k=%d is above the largest supported k=%d (csrk_rank_entries_limits)", k, RE_K_MAX);
+        return CSRK_ERR_UNSUPPORTED;
+    }
+    return CSRK_OK;
+}
+
+// then the handles (seen may be 0) and what they must agree on; the caller holds no lock
+static int re_check(csrk_handle_t seen_h, csrk_handle_t test_h, int32_t row_begin, int32_t row_end, Matrix **ms, Matrix **mt)
+{
+    Matrix *seen = nullptr, *test = nullptr;
+    if (seen_h) {
+        seen = from_handle(seen_h);
+        if (!seen) return CSRK_ERR_INVALID;
+    }
+    test = from_handle(test_h);
+    if (!test) return CSRK_ERR_INVALID;
+    CSRK_REQUIRE(row_end <= test->nrows, "rank_entries: bad row range [%d, %d) of %d rows", row_begin, row_end, test->nrows);
+    if (seen) {
+        CSRK_REQUIRE(seen->nrows == test->nrows && seen->ncols == test->ncols, "rank_entries: seen is %d x %d but test is %d x %d",
+                     seen->nrows, seen->ncols, test->nrows, test->ncols);
+        CSRK_REQUIRE(seen->device == test->device, "rank_entries: seen and test are on different devices");
+        std::lock_guard<std::mutex> lk(seen->mu);
+        CSRK_TRY(look_at_rows(seen));                             // (remembered: a device pass only the first time a handle is asked)
+        CSRK_REQUIRE(seen->canonical == 1,
+                     "rank_entries: seen is not canonical: row %d is not strictly ascending in column (csrk_order_columns sorts, "
+                     "csrk_coalesce merges repeats)",
+                     seen->noncanonical_row);
+    }
+    *ms = seen, *mt = test;
+    return CSRK_OK;
+}
+
+// dU points at row row_begin of U; there are rows and test stores entries
+static int re_device(Matrix *seen, Matrix *test, int32_t row_begin, int32_t row_end, const void *dU, int64_t ldu, const void *dV,
+                     int64_t ldv, int32_t k, int panel_type, int32_t *dranks, double *dscores, hipStream_t s)
+{
+    CSRK_REQUIRE(dranks, "rank_entries: ranks is NULL");
+    CSRK_REQUIRE(dU && dV, "rank_entries: U or V is NULL");
+    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 && ((uintptr_t)dranks % 4) == 0,
+                 "rank_entries: U, V, ranks or scores is not aligned to its element size");
+    if (s) {
+        if (seen) {
+            std::lock_guard<std::mutex> lk(seen->mu);
+            seen->used_user_stream = true;
+        }
+        std::lock_guard<std::mutex> lk(test->mu);
+        test->used_user_stream = true;
+    }
+    // 16-B loads when every piece of every row of both panels is whole and 16-B aligned; else element loads: the same bits
+    const int64_t per16 = (int64_t)(16 / es);
+    const bool wide = ((uintptr_t)dU & 15) == 0 && ((uintptr_t)dV & 15) == 0 && ldu % per16 == 0 && ldv % per16 == 0 && k % per16 == 0;
+    const char *env = getenv("CSRK_RANK_ENTRIES_COUNT");          // diagnostic: "0" times the product alone (the outputs are not written)
+    const int count = !(env && env[0] == '0' && !env[1]);
+    const int32_t n = row_end - row_begin;
+    const unsigned grid = (unsigned)ceil_div((int64_t)n, TS_ROWS);
+#define RE_GO(T, W)                                                                                                               \
+    rank_entries_kernel<T, W><<<grid, TS_THREADS, 0, s>>>(seen ? seen->d_rowptrs : nullptr, seen ? seen->ptr64 : 0,               \
+                                                           seen ? seen->d_colinds : nullptr, test->d_rowptrs, test->ptr64,         \
+                                                           test->d_colinds, row_begin, n, (const T *)dU, ldu, (const T *)dV, ldv,  \
+                                                           test->ncols, k, count, dranks, dscores)
+    if (panel_type == CSRK_VAL_F64) {
+        if (wide) RE_GO(double, true);
+        else RE_GO(double, false);
+    } else {
+        if (wide) RE_GO(float, true);
+        else RE_GO(float, false);
+    }
+#undef RE_GO
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+}  // namespace csrk
+
+using namespace csrk;
+
+extern "C" {
+
+int csrk_rank_entries_limits(int64_t *out, int n)
+{
+    CSRK_REQUIRE(out && n >= 0, "csrk_rank_entries_limits: out is NULL or n < 0");
+    const int64_t v[5] = {RE_K_MAX, TS_ROWS, TS_TILE, TS_KC, RE_T};
+    for (int i = 0; i < n && i < 5; i++) out[i] = v[i];
+    return CSRK_OK;
+}
+
+int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin, int32_t row_end, const void *d_U, int64_t ldu,
+                             const void *d_V, int64_t ldv, int32_t k, int panel_type, int32_t *d_ranks, double *d_scores, void *stream)
+{
+    Matrix *ms, *mt;
+    CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
+    CSRK_TRY(re_check(seen, test, row_begin, row_end, &ms, &mt));
+    if (row_begin == row_end || mt->nnz == 0) return CSRK_OK;
+    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const void *u0 = d_U ? (const char *)d_U + (size_t)row_begin * (size_t)ldu * es : nullptr;
+    return re_device(ms, mt, row_begin, row_end, u0, ldu, d_V, ldv, k, panel_type, d_ranks, d_scores, (hipStream_t)stream);
+}
+
+int csrk_rank_entries(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin, int32_t row_end, const void *U, int64_t ldu,
+                      const void *V, int64_t ldv, int32_t k, int panel_type, int32_t *ranks, double *scores)
+{
+    Matrix *ms, *mt;
+    // argument checks first, with the caller's pointers (the device call below sees packed copies)
+    CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
+    CSRK_TRY(re_check(seen, test, row_begin, row_end, &ms, &mt));
+    if (row_begin == row_end || mt->nnz == 0) return CSRK_OK;
+    // the entries of the range: two row pointers (the host form is synchronous anyway)
+    int64_t e[2];
+    for (int i = 0; i < 2; i++) {
+        const int64_t row = i ? row_end : row_begin;
+        if (mt->ptr64) {
+            CSRK_HIP(hipMemcpy(&e[i], (const int64_t *)mt->d_rowptrs + row, 8, hipMemcpyDeviceToHost));
+        } else {
+            int32_t v = 0;
+            CSRK_HIP(hipMemcpy(&v, (const int32_t *)mt->d_rowptrs + row, 4, hipMemcpyDeviceToHost));
+            e[i] = v;
+        }
+    }
+    if (e[1] <= e[0]) return CSRK_OK;
+    CSRK_REQUIRE(ranks, "rank_entries: ranks is NULL");
+    CSRK_REQUIRE(U && V, "rank_entries: U or V is NULL");
+    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    CSRK_REQUIRE(((uintptr_t)U % es) == 0 && ((uintptr_t)V % es) == 0 && ((uintptr_t)scores % 8) == 0 && ((uintptr_t)ranks % 4) == 0,
+                 "rank_entries: U, V, ranks or scores is not aligned to its element size");
+    const size_t n = (size_t)(row_end - row_begin), ne = (size_t)(e[1] - e[0]), n_items = (size_t)mt->ncols;
+    // the panels travel packed (ld = k): the bits do not depend on the stride
+    DevBuf dU, dV, dR, dS;
+    CSRK_TRY(dU.alloc(n * k * es));
+    CSRK_TRY(dV.alloc(n_items * k * es));
+    CSRK_TRY(dR.alloc(ne * 4));
+    if (scores) CSRK_TRY(dS.alloc(ne * 8));
+    CSRK_HIP(hipMemcpy2D(dU.p, (size_t)k * es, (const char *)U + (size_t)row_begin * (size_t)ldu * es, (size_t)ldu * es, (size_t)k * es, n,
+                         hipMemcpyHostToDevice));
+    if (n_items) CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, n_items, hipMemcpyHostToDevice));
+    CSRK_TRY(re_device(ms, mt, row_begin, row_end, dU.p, k, dV.p, k, k, panel_type, dR.as<int32_t>(), scores ? dS.as<double>() : nullptr,
+                       nullptr));
+    CSRK_HIP(hipMemcpy(ranks, dR.p, ne * 4, hipMemcpyDeviceToHost));
+    if (scores) CSRK_HIP(hipMemcpy(scores, dS.p, ne * 8, hipMemcpyDeviceToHost));
+    return CSRK_OK;
+}
+
+}  // extern "C"

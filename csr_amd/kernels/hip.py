@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
-is_canonical, topk_scores.
+is_canonical, topk_scores, rank_entries.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -990,6 +990,53 @@ def topk_scores(h, U, V, n, min_score=None, rows=None):
     _call(lib.csrk_topk_scores, 0 if h is None else _live(h), rb, re_, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, ptr(items),
           n, ptr(scores), n, ptr(counts))
     return items, scores, counts
+
+
+def rank_entries_limits():
+    "(largest k, rows per workgroup, items per tile, factors per LDS chunk, test entries of a row per sweep)"
+    out = (C.c_int64 * 5)()
+    check(lib.csrk_rank_entries_limits(out, 5))
+    return tuple(out)
+
+
+def rank_entries_args(seen_h, test_h, U, V, rows=None):
+    """
+    (U, ldu, V, ldv, k, panel code, row_begin, row_end) as the library takes them; ValueError for anything it would refuse
+    as invalid.  test_h is anything with nrows and ncols (a handle or a CSR: the held-out pairs), seen_h the same (the
+    pairs already seen) or None; no library call is made.
+    """
+    for name, h in (('test', test_h), ('seen', seen_h)):
+        if h is None and name == 'seen':
+            continue
+        if isinstance(h, np.ndarray) or not all(hasattr(h, a) for a in ('nrows', 'ncols', 'nnz')):
+            raise ValueError(f'{name} must be a CSR or a handle, not {type(h).__name__}')
+    if seen_h is not None and (int(seen_h.nrows), int(seen_h.ncols)) != (int(test_h.nrows), int(test_h.ncols)):
+        raise ValueError(f'seen is {seen_h.nrows} x {seen_h.ncols} but test is {test_h.nrows} x {test_h.ncols}')
+    U, ldu, V, ldv, _, k, code, _, _, rb, re_ = topk_scores_args(test_h, U, V, 1, None, rows)
+    return U, ldu, V, ldv, k, code, rb, re_
+
+
+def rank_entries(seen_h, test_h, U, V, rows=None):
+    """
+    Offline evaluation of a factor model: for every entry (i, j) that test_h stores in rows = (begin, end) (None: all rows),
+    in storage order, the number of items c != j that seen_h does not store in row i (None: no item is left out) and whose
+    score dot(U[i, :], V[c, :]) comes before j's -- (ranks int32 [m], scores float64 [m]) with m the entries of those rows.
+    Scores and order are topk_scores': one chain of k fused multiply-adds in float64, NaN above +Inf, -0.0 tied with +0.0,
+    ties to the smaller item; an entry of rank r < n that seen_h does not store is topk_scores' items[i][r] (include/csrk.h,
+    csrk_rank_entries).  seen_h's matrix must be canonical, test_h's need not be.  Not a reference entry point.
+    """
+    U, ldu, V, ldv, k, code, rb, re_ = rank_entries_args(seen_h, test_h, U, V, rows)
+    sh = 0 if seen_h is None else _live(seen_h)
+    lim = rank_entries_limits()
+    if k > lim[0]:      # the library's refusal, before any result array is made
+        check(lib.csrk_rank_entries(sh, _live(test_h), rb, re_, ptr(U), ldu, ptr(V), ldv, k, code, None, None))
+        raise ValueError(f'k = {k} is above the limit {lim[0]}')
+    m = 0
+    if re_ > rb and test_h.nnz:
+        m = row_extent(test_h, re_ - 1)[1] - row_extent(test_h, rb)[0]
+    ranks, scores = _out(m, np.int32), _out(m, np.float64)
+    _call(lib.csrk_rank_entries, sh, _live(test_h), rb, re_, ptr(U), ldu, ptr(V), ldv, k, code, ptr(ranks), ptr(scores))
+    return ranks, scores
 
 
 def set_spgemm_order(order):

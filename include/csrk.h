@@ -552,8 +552,8 @@ CSRK_API int csrk_coalesce_last_route(int *route);
 CSRK_API int csrk_is_canonical(csrk_handle_t h, int *canonical, int32_t *first_bad_row);
 
 /* ---- topk_scores: each row's n_top best unseen items from the factors U and V ----------------------
- * Not a reference entry point: the last step of the ALS path (csrk_als_rows trains, csrk_sddmm gives loss and residuals):
- * for every row of a range, score ALL items as U[i] . V[j], leave out the (row, item) pairs `seen` stores and the scores
+ * Not a reference entry point: from trained factors to recommendations (csrk_als_rows trains, csrk_sddmm gives loss and
+ * residuals, csrk_rank_entries below evaluates): for every row of a range, score ALL items as U[i] . V[j], leave out the (row, item) pairs `seen` stores and the scores
  * below a threshold, keep the n_top best.  The rows x n_items block of scores is never stored.
  *   1. Operands.  U is dense row-major, indexed by the ABSOLUTE row i of [row_begin, row_end): U[i][t] at U + i * ldu + t.
  *      V is dense row-major [n_items x k].  Both are float32 or both float64 (panel_type = CSRK_VAL_F32 / CSRK_VAL_F64);
@@ -607,6 +607,65 @@ CSRK_API int csrk_topk_scores_device(csrk_handle_t seen, int32_t row_begin, int3
                                      int64_t lds, int32_t *d_counts, void *stream);
 /* Diagnostics: the six limits of rule 10, in its order;  n <= 6.  No device is touched. */
 CSRK_API int csrk_topk_scores_limits(int64_t *out, int n);
+
+/* ---- rank_entries: where each held-out entry lands among its row's unseen items --------------------
+ * Not a reference entry point: offline evaluation after csrk_topk_scores.  For every entry (i, j) of `test`, the number of
+ * items that row i has not seen and that come before j in the row's full ranking by U[i] . V[c].  Hit rate, MRR and nDCG
+ * at any cut-off, AUC and mean percentile rank follow from that number on the host; the rows x n_items block of scores is
+ * never stored.
+ *   1. Operands.  `test` is a handle; n_items is its ncols.  U and V are as in csrk_topk_scores' rule 1: U is indexed by the
+ *      ABSOLUTE row i of [row_begin, row_end), V is [n_items x k], both float32 or both float64 (panel_type), ldu, ldv >= k
+ *      in elements.  `seen` is 0 (nothing is excluded) or a handle with test's nrows and ncols; it must be canonical: the
+ *      check is csrk_is_canonical's remembered one, and the refusal names the first bad row as csrk_topk_scores' does.
+ *      `test` need not be canonical: unsorted and repeated columns are just more entries.  The values of neither are ever
+ *      read (structure-only handles will do), either pointer width is taken for either, neither is modified and both keep
+ *      their plans.  The columns of `test` and `seen` select rows of V, as csrk_sddmm's pattern does, and must lie in
+ *      [0, n_items); one that does not is not dereferenced: as an entry of `test` it gets rank -1 and a NaN score, as an
+ *      entry of `seen` it excludes nothing.
+ *   2. Score.  csrk_topk_scores' rule 2:   s = +0.0;  for t = 0 .. k-1 ascending:  s = fma(U[i][t], V[j][t], s)
+ *      -- one serial chain of fused multiply-adds in float64, float32 elements widened exactly first; no split sums, no float
+ *      atomics, no matrix instructions.  The score of a pair has the bits csrk_topk_scores gives it.
+ *   3. Rank.  For a test entry e = (i, j) with score s_e let C be the items c of [0, n_items), c != j, that `seen` does not
+ *      store in row i.  rank_e = the number of c in C whose (s_c, c) comes before (s_e, j) in the total order of
+ *      csrk_topk_scores' rule 4: larger score first; any NaN above +Inf and all NaNs tied; -0.0 ties +0.0; on equal keys the
+ *      smaller item index first.  j itself is ranked whether or not `seen` stores (i, j); the other test entries of the row
+ *      are ordinary competitors; an item repeated in a test row gets the same rank each time.  Row i has
+ *      n_items - (the entries `seen` stores in row i) candidates, the held-out item included when `seen` does not store it.
+ *   4. Output.  With base = test.rowptrs[row_begin], for every entry e of rows [row_begin, row_end) in test's storage order:
+ *      ranks[e - base] = rank_e and, when scores is not NULL, scores[e - base] = the chain's bits unchanged (-0.0 stays
+ *      -0.0).  Nothing else is written.
+ *   5. Agreement with csrk_topk_scores.  With the same U, V and `seen`, min_score = -INFINITY and any n_top: a test entry
+ *      that `seen` does not store and whose rank_e < n_top has items[i][rank_e] == j there, and scores[i][rank_e] has the
+ *      bits of scores[e - base] here.
+ *   6. Invariance.  An output depends only on U's row i, V, row i of `seen`, the entry's column, k and the panel type: not
+ *      on the row range asked for, the strides, the alignment (16-B pieces or element loads: the same bits), the pointer
+ *      widths, the other entries of `test` or their number, the stream, the launch geometry or repeated calls.
+ *   7. Special values.  IEEE throughout; no path skips a zero.  A NaN that a chain creates has its position specified, not
+ *      its sign or payload; every NaN has the same key, so the ranks are specified even then.
+ *   8. Device form.  Allocates nothing and does not synchronise the host, with one exception: the first call that asks
+ *      `seen` whether it is canonical looks at its rows (csrk_is_canonical beforehand takes that look).  A workgroup takes a
+ *      block of rows across all items and holds up to out[4] test entries per row on the chip; rows with more are swept
+ *      again, decided on the device: no scratch memory.  The items of a small row range are not split across workgroups.
+ *      The host form sends the panels packed (the rows of the range only) and is synchronous.
+ *   9. Refusals; a refused call writes nothing.  The scalar arguments are looked at first and answered whatever the handles
+ *      are: CSRK_ERR_INVALID for k < 1, ldu < k, ldv < k, an unknown panel_type, row_begin < 0 or row_begin > row_end;
+ *      CSRK_ERR_UNSUPPORTED for k above out[0] of csrk_rank_entries_limits (at least 256).  Then CSRK_ERR_INVALID: a `test`
+ *      or a non-zero `seen` that is not a handle; row_end > nrows; a `seen` of another shape than `test` or not canonical;
+ *      when there is work, a NULL ranks, U or V or a pointer not aligned to its element.  row_begin == row_end, or a range
+ *      without test entries: CSRK_OK, nothing launched (the device form, which does not read row pointers on the host,
+ *      launches unless `test` is empty altogether; workgroups without test entries end at once).
+ *  10. Limits (csrk_rank_entries_limits): out[0] = the largest k; [1] = the rows of a workgroup; [2] = the items of a tile;
+ *      [3] = the factors staged through LDS per chunk; [4] = T, the test entries of a row held on the chip per sweep (a row
+ *      with more is swept again per T of them, so any number works);  n <= 5.  By rule 6 none of them changes a bit. */
+CSRK_API int csrk_rank_entries(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin, int32_t row_end, const void *U,
+                               int64_t ldu, const void *V, int64_t ldv, int32_t k, int panel_type, int32_t *ranks,
+                               double *scores);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream). */
+CSRK_API int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin, int32_t row_end,
+                                      const void *d_U, int64_t ldu, const void *d_V, int64_t ldv, int32_t k, int panel_type,
+                                      int32_t *d_ranks, double *d_scores, void *stream);
+/* Diagnostics: the five limits of rule 10, in its order;  n <= 5.  No device is touched. */
+CSRK_API int csrk_rank_entries_limits(int64_t *out, int n);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,8 @@ SIGNATURES = {
     'csrk_spgemm_set_order': (_int, [_int]),
     'csrk_spgemm_get_order': (_int, [C.POINTER(_int)]),
     'csrk_spgemm_last_route': (_int, [C.POINTER(_int)]),
+    'csrk_spgemm_last_stats': (_int, [C.POINTER(_i64), _int]),
+    'csrk_spgemm_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_spmm_dense': (_int, [handle_t, _vp, _i32, _i64, _vp, _i64]),
     'csrk_spmm_dense_device': (_int, [handle_t, _vp, _i32, _i64, _vp, _i64, _vp]),
     'csrk_spmm_plan_stats': (_int, [handle_t, _vp, _int]),

@@ -41,6 +41,12 @@ namespace csrk {
 int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 bool spgemm_reference_order_wanted();                                            // spgemm_order.hip
 int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products);
+void spgemm_order_limits(int64_t out[5]);
+
+// csrk_spgemm_last_stats: what the calling thread's last general product did with its rows (include/csrk.h has the layout);
+// zeroed by every csrk_spgemm_ab / _abt, filled at the end of spgemm_run from what the driver holds on the host anyway
+constexpr int SG_N_STATS = 16;
+static thread_local int64_t t_last_stats[SG_N_STATS];
 
 struct MatView {
     const void *rp;
@@ -1590,6 +1596,8 @@ static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, De
             return CSRK_ERR_HIP;
         }
         *out = c;
+        t_last_stats[0] = 1;
+        t_last_stats[1] = FAST ? 1 : 0;
         return CSRK_OK;
     }
     MatView av = view_of(a), bv = view_of(b);
@@ -1998,6 +2006,12 @@ static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, De
         return rc;
     }
     *out = c;
+    {
+        const int64_t st[SG_N_STATS] = {1, FAST ? 1 : 0, strips, n_strip, n_strip_e, strip_fused ? 1 : 0, n_esc, esc_products,
+                                        n_large, lds_symbolic ? 1 : 0, n_lds, n_hash, n_hbm, small_fused ? 1 : 0,
+                                        mid_rows ? 1 : 0, hash_rows ? 1 : 0};
+        for (int k = 0; k < SG_N_STATS; k++) t_last_stats[k] = st[k];
+    }
     if (products) {                                  // the rows' product counts: the ordering pass needs them too
         products->release();
         products->bytes = ub.bytes;
@@ -2030,6 +2044,7 @@ static int spgemm_impl(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend)
         if (rc != CSRK_OK) {
             delete *out;
             *out = nullptr;
+            for (int k = 0; k < SG_N_STATS; k++) t_last_stats[k] = 0;      // (a failed call reports nothing)
             return rc;
         }
     }
@@ -2058,9 +2073,27 @@ int csrk_spgemm_last_route(int *route)
     return CSRK_OK;
 }
 
+int csrk_spgemm_last_stats(int64_t *out, int n)
+{
+    CSRK_REQUIRE(out && n >= 0, "out is NULL");
+    for (int i = 0; i < n && i < SG_N_STATS; i++) out[i] = t_last_stats[i];
+    return CSRK_OK;
+}
+
+int csrk_spgemm_limits(int64_t *out, int n)
+{
+    CSRK_REQUIRE(out && n >= 0, "out is NULL");
+    int64_t v[20] = {SG_WAVE_CAP, SG_CAP, SGE_MIN, SGE_TILE, SGS_W, SGS_MAX_S, SGS_MIN_PER_CELL, SGS_MIN_PER_UNIT, SGS_HEAVY_J,
+                     SGL_W, SGL_MAXTILES, SGL_MAXBITS, SGB_CAP, SG_COUNT_LONG, SG_COUNT_VLONG};
+    spgemm_order_limits(v + 15);
+    for (int i = 0; i < n && i < 20; i++) out[i] = v[i];
+    return CSRK_OK;
+}
+
 int csrk_spgemm_ab(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 {
     t_last_route = 0;      // (a call that fails before spgemm_impl must not report the previous call's route)
+    for (int k = 0; k < SG_N_STATS; k++) t_last_stats[k] = 0;
     CSRK_REQUIRE(out, "out is NULL");
     *out = 0;
     Matrix *a = from_handle(ah), *b = from_handle(bh);
@@ -2075,6 +2108,7 @@ int csrk_spgemm_ab(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 int csrk_spgemm_abt(csrk_handle_t ah, csrk_handle_t bh, csrk_handle_t *out)
 {
     t_last_route = 0;
+    for (int k = 0; k < SG_N_STATS; k++) t_last_stats[k] = 0;
     CSRK_REQUIRE(out, "out is NULL");
     *out = 0;
     Matrix *a = from_handle(ah), *b = from_handle(bh);

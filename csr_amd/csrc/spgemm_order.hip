@@ -801,6 +801,13 @@ int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *
     return CSRK_OK;
 }
 
+// the ordering pass's row tiers and the placing window, for csrk_spgemm_limits (spgemm.hip)
+void spgemm_order_limits(int64_t out[5])
+{
+    const int64_t v[5] = {SO_LEAST, SO_TINY, SO_WAVE, SO_MID, SO_WIN};
+    for (int i = 0; i < 5; i++) out[i] = v[i];
+}
+
 }  // namespace csrk
 
 using namespace csrk;

@@ -1067,6 +1067,30 @@ def spgemm_last_route():
     return 'dense-panel' if r.value else 'general'
 
 
+SPGEMM_STATS = ('general', 'fast', 'strips', 'strip_rows', 'strip_entries', 'strip_fused', 'esc_rows', 'esc_products', 'large_rows',
+                'lds_symbolic', 'lds_rows', 'hash_big_rows', 'hbm_rows', 'small_fused', 'mid_rows', 'hash_rows')
+SPGEMM_LIMITS = ('SG_WAVE_CAP', 'SG_CAP', 'SGE_MIN', 'SGE_TILE', 'SGS_W', 'SGS_MAX_S', 'SGS_MIN_PER_CELL', 'SGS_MIN_PER_UNIT',
+                 'SGS_HEAVY_J', 'SGL_W', 'SGL_MAXTILES', 'SGL_MAXBITS', 'SGB_CAP', 'SG_COUNT_LONG', 'SG_COUNT_VLONG', 'SO_LEAST',
+                 'SO_TINY', 'SO_WAVE', 'SO_MID', 'SO_WIN')
+
+
+def spgemm_last_stats():
+    """
+    what the general product did with the rows of this thread's last mult_ab / mult_abt, as a dict (include/csrk.h,
+    csrk_spgemm_last_stats): all zero after a call that failed or took the dense-panel route
+    """
+    out = (C.c_int64 * len(SPGEMM_STATS))()
+    check(lib.csrk_spgemm_last_stats(out, len(SPGEMM_STATS)))
+    return dict(zip(SPGEMM_STATS, (int(v) for v in out)))
+
+
+def spgemm_limits():
+    "the compile-time constants the general product routes its rows by, as a dict (include/csrk.h, csrk_spgemm_limits)"
+    out = (C.c_int64 * len(SPGEMM_LIMITS))()
+    check(lib.csrk_spgemm_limits(out, len(SPGEMM_LIMITS)))
+    return dict(zip(SPGEMM_LIMITS, (int(v) for v in out)))
+
+
 def set_spmv_algo(h, name):
     "select the SpMV kernel for this handle: 'auto' | 'merge' | 'vector' | 'scalar'"
     code = {'auto': _lib.SPMV_AUTO, 'merge': _lib.SPMV_MERGE, 'vector': _lib.SPMV_VECTOR,

@@ -229,6 +229,30 @@ CSRK_API int csrk_spgemm_get_order(int *order);
  * switches the route off.  csrk_spgemm_last_route: what the calling thread's last product took -- 0 the general product,
  * 1 the dense-panel route; 0 after a call that failed. */
 CSRK_API int csrk_spgemm_last_route(int *route);
+/* Diagnostics: what the general product (csrc/spgemm.hip) did with the rows of the calling thread's last csrk_spgemm_ab /
+ * _abt.  All zero after a call that failed or took the dense-panel route; filled from what the driver holds on the host,
+ * without a kernel, a copy or a synchronisation of its own.  Rows by their product count u = sum over A_i of |B_j|:
+ *   out[0]  1: the general product ran
+ *   out[1]  1: FAST form (int32 row pointers and float64 values on both operands), 0: the general form
+ *   out[2]  column strips per row in force (0: strips off -- general form, B's rows not ascending, too many columns,
+ *           CSRK_SPGEMM_STRIPS=0)
+ *   out[3]  rows on the strips, [4] their entries of A, [5] 1: the strips' one-pass form, 0: two passes (or no strip row)
+ *   out[6]  rows of expand-sort-compress, [7] their products
+ *   out[8]  rows of the fallback paths (more than 1024 products, neither strips nor expand-sort-compress),
+ *   out[9]  1: their distinct outputs were counted in LDS, which splits them into [10] LDS tiles, [11] the 8192-slot hash
+ *           table, [12] HBM work rows (without the LDS count all of them are HBM work rows)
+ *   out[13] 1: the rows of at most 128 products in one pass (0: two passes, or there is none)
+ *   out[14] 1: the 32-lane kernel (33 .. 128 products) ran, [15] 1: the workgroup hash kernel (129 .. 1024 products) ran
+ * csrk_spgemm_limits: the constants behind those decisions -- [0] products of a sub-wavefront row at most (128), [1] of a
+ * workgroup-hash row (1024), [2] rows above this many products go to expand-sort-compress (32), [3] its positions per tile
+ * (1024), [4] columns per strip (832), [5] strips per row at most (256), [6] products per (A entry, strip) and [7] per
+ * (row, strip) a strip row has at least on average (4, 512), [8] entries of A from which a strip row is scheduled first
+ * (1024), [9] columns per LDS tile (20096), [10] LDS tiles per row at most (8), [11] columns the LDS count covers (2^20),
+ * [12] distinct outputs of a big-hash row at most (4096), [13] / [14] entries of A above which a row is counted by a
+ * wavefront / by all wavefronts (64, 4096), [15] .. [18] the ordering pass's row tiers in products (64, 256, 1024, 4096),
+ * [19] product indices per window of its placing kernel (2^19). */
+CSRK_API int csrk_spgemm_last_stats(int64_t *out, int n);
+CSRK_API int csrk_spgemm_limits(int64_t *out, int n);
 
 /* ---- dense-panel SpMM: C = A B, B dense row-major [ncols x k] --------------------------
  * Not a reference entry point (the reference's mult_ab is sparse x sparse only); serves

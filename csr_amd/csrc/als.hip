@@ -6,10 +6,10 @@
 // Both run one device routine, al_ldl_solve, so a fused row and the composed path (gram_rows, then solve_blocks) agree bit
 // for bit.
 //
-// Where the block lives.  The accumulation is gram.hip's, restated here so that gram.hip's code and bits stay as they are: a
-// TEAM of threads owns a row (16 lanes for k <= 16, a wavefront for k <= 40, a 256-thread workgroup above), the lower
-// triangle is cut into 4 x 4 register tiles, one per thread (up to three for k > 88), and the row's V rows go through LDS
-// AL_STAGE entries per step in two buffers.  When the row's entries are done the block sits in registers, and it is
+// Where the block lives.  The accumulation is the routine gram.hip runs, gram_tile.h's gt_accumulate, with the right-hand
+// side switched on: a TEAM of threads owns a row (16 lanes for k <= 16, a wavefront for k <= 40, a 256-thread workgroup
+// above), the lower triangle is cut into 4 x 4 register tiles, one per thread (up to three for k > 88), and the row's V rows
+// go through LDS GT_STAGE entries per step in two buffers.  When the row's entries are done the block sits in registers, and it is
 // factorised THERE: a right-looking LDL^T step for column j is a rank-one update of the trailing triangle,
 //     a[i][m] = fma(-L[i][j], C[m][j], a[i][m])      (j < m <= i),      L[i][j] = round(C[i][j] * r_j),   r_j = 1.0 / C[j][j]
 // which has the shape of one more staged entry of the accumulation: a tile needs four p- and four q-operands of column j.
@@ -28,66 +28,12 @@
 //
 // info = j + 1 for the first pivot with d_j > 0 false (every thread sees every pivot), 0 otherwise.  No pivoting, no square
 // root, no special case: a bad pivot goes through IEEE arithmetic.
-#include "common.h"
+#include "gram_tile.h"
 
 namespace csrk {
 
-constexpr int AL_THREADS = 256;
-constexpr int AL_STAGE = 8;                      // entries staged per step
-constexpr int AL_B = 4;                          // register tile edge
-constexpr int AL_K_SUB = 16;                     // k up to this: 16 lanes per system
-constexpr int AL_K_WAVE = 40;                    // k up to this: a wavefront per system
-constexpr int AL_K_ONE = 88;                     // k up to this: a workgroup per system, one tile per thread
-constexpr int AL_K_MAX = 128;                    // k up to this: a workgroup per system, up to three tiles per thread
-
-template <int CLS> struct AlClass;
-template <> struct AlClass<0> { static constexpr int TEAM = 16, KMAX = AL_K_SUB, TPT = 1; };
-template <> struct AlClass<1> { static constexpr int TEAM = 64, KMAX = AL_K_WAVE, TPT = 1; };
-template <> struct AlClass<2> { static constexpr int TEAM = 256, KMAX = AL_K_ONE, TPT = 1; };
-template <> struct AlClass<3> { static constexpr int TEAM = 256, KMAX = AL_K_MAX, TPT = 3; };
-
-typedef double al_d2 __attribute__((ext_vector_type(2)));
-typedef float al_f4 __attribute__((ext_vector_type(4)));
-
-// one unit of a panel row as float64: PER elements (a 16-B piece when PER > 1, else one element)
-template <class T, int PER> __device__ __forceinline__ void al_load(const T *__restrict__ p, double d[PER]);
-template <> __device__ __forceinline__ void al_load<double, 1>(const double *__restrict__ p, double d[1]) { d[0] = *p; }
-template <> __device__ __forceinline__ void al_load<float, 1>(const float *__restrict__ p, double d[1]) { d[0] = (double)*p; }
-template <> __device__ __forceinline__ void al_load<double, 2>(const double *__restrict__ p, double d[2])
-{
-    const al_d2 a = *(const al_d2 *)p;
-    d[0] = a.x, d[1] = a.y;
-}
-template <> __device__ __forceinline__ void al_load<float, 4>(const float *__restrict__ p, double d[4])
-{
-    const al_f4 a = *(const al_f4 *)p;
-    d[0] = (double)a.x, d[1] = (double)a.y, d[2] = (double)a.z, d[3] = (double)a.w;
-}
-
-// the team's threads have all written their LDS words before any of them reads (a team never spans workgroups)
-template <int TEAM> __device__ __forceinline__ void al_team_sync()
-{
-    if constexpr (TEAM > WAVE) {
-        __syncthreads();
-    } else {      // within one wavefront LDS operations complete in issue order: order the compiler and the counters
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-}
-
-// tile t of the lower triangle, row-major over 4 x 4 blocks: block row bp, block column bq <= bp
-__device__ __forceinline__ void al_tile(int t, bool has, int &p0, int &q0)
-{
-    int b = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while (b * (b + 1) / 2 > t) b--;
-    while ((b + 1) * (b + 2) / 2 <= t) b++;
-    p0 = has ? AL_B * b : 0;
-    q0 = has ? AL_B * (t - b * (b + 1) / 2) : 0;
-}
-
 // acc[..][i][jj] for a jj known only at run time (the tiles live in registers: no indexed access)
-__device__ __forceinline__ double al_pick(const double (&a)[AL_B], int jj)
+__device__ __forceinline__ double al_pick(const double (&a)[GT_B], int jj)
 {
     return jj == 0 ? a[0] : jj == 1 ? a[1] : jj == 2 ? a[2] : a[3];
 }
@@ -96,7 +42,7 @@ __device__ __forceinline__ double al_pick(const double (&a)[AL_B], int jj)
 // published); zx: b[tid] in, x[tid] out, for tid < k; col[2][KP] and piv[2]: the team's LDS.  Returns info, the same in
 // every thread of the team.  Every thread of the team calls it (it holds team barriers).
 template <int TEAM, int TPT, int KP>
-__device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][AL_B][AL_B], const int (&p0)[TPT], const int (&q0)[TPT],
+__device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][GT_B][GT_B], const int (&p0)[TPT], const int (&q0)[TPT],
                                             const bool (&has)[TPT], double &zx, int k, int tid, double (*col)[KP], double *piv)
 {
     int info = 0, step = 0;
@@ -106,30 +52,30 @@ __device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][AL_B][AL_B], cons
         // column j as it stands is C[j .. k-1][j]: its owners publish it, thread j publishes z_j
 #pragma unroll
         for (int r = 0; r < TPT; r++)
-            if (has[r] && q0[r] <= j && j < q0[r] + AL_B) {
+            if (has[r] && q0[r] <= j && j < q0[r] + GT_B) {
                 const int jj = j - q0[r];
 #pragma unroll
-                for (int i = 0; i < AL_B; i++) {
+                for (int i = 0; i < GT_B; i++) {
                     const int p = p0[r] + i;
                     if (p >= j && p < k) col[buf][p] = al_pick(acc[r][i], jj);
                 }
             }
         if (tid == j) piv[buf] = z;
-        al_team_sync<TEAM>();
+        gt_team_sync<TEAM>();
         const double d = col[buf][j];
         const double rj = 1.0 / d;                                          // one correctly rounded division
         if (info == 0 && !(d > 0.0)) info = j + 1;
 #pragma unroll
         for (int r = 0; r < TPT; r++)
-            if (has[r] && q0[r] + AL_B > j && p0[r] + AL_B > j) {
-                const al_d2 a0 = *(const al_d2 *)&col[buf][p0[r]], a1 = *(const al_d2 *)&col[buf][p0[r] + 2];
-                const al_d2 b0 = *(const al_d2 *)&col[buf][q0[r]], b1 = *(const al_d2 *)&col[buf][q0[r] + 2];
-                const double cp[AL_B] = {a0.x, a0.y, a1.x, a1.y}, cq[AL_B] = {b0.x, b0.y, b1.x, b1.y};
+            if (has[r] && q0[r] + GT_B > j && p0[r] + GT_B > j) {
+                const gt_d2 a0 = *(const gt_d2 *)&col[buf][p0[r]], a1 = *(const gt_d2 *)&col[buf][p0[r] + 2];
+                const gt_d2 b0 = *(const gt_d2 *)&col[buf][q0[r]], b1 = *(const gt_d2 *)&col[buf][q0[r] + 2];
+                const double cp[GT_B] = {a0.x, a0.y, a1.x, a1.y}, cq[GT_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
-                for (int i = 0; i < AL_B; i++) {
+                for (int i = 0; i < GT_B; i++) {
                     const double l = __dmul_rn(cp[i], rj);                  // L[p][j]
 #pragma unroll
-                    for (int jj = 0; jj < AL_B; jj++) {
+                    for (int jj = 0; jj < GT_B; jj++) {
                         const int q = q0[r] + jj;
                         const double u = __builtin_fma(-l, cq[jj], acc[r][i][jj]);
                         acc[r][i][jj] = q > j ? u : (q == j ? l : acc[r][i][jj]);
@@ -145,17 +91,17 @@ __device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][AL_B][AL_B], cons
         // row t of L, columns 0 .. t-1: its owners publish it, thread t publishes x_t
 #pragma unroll
         for (int r = 0; r < TPT; r++)
-            if (has[r] && p0[r] <= t && t < p0[r] + AL_B) {
+            if (has[r] && p0[r] <= t && t < p0[r] + GT_B) {
                 const int i = t - p0[r];
 #pragma unroll
-                for (int jj = 0; jj < AL_B; jj++) {
+                for (int jj = 0; jj < GT_B; jj++) {
                     const int q = q0[r] + jj;
-                    const double a[AL_B] = {acc[r][0][jj], acc[r][1][jj], acc[r][2][jj], acc[r][3][jj]};
+                    const double a[GT_B] = {acc[r][0][jj], acc[r][1][jj], acc[r][2][jj], acc[r][3][jj]};
                     if (q < t) col[buf][q] = al_pick(a, i);
                 }
             }
         if (tid == t) piv[buf] = x;
-        al_team_sync<TEAM>();
+        gt_team_sync<TEAM>();
         if (tid < t) x = __builtin_fma(-col[buf][tid], piv[buf], x);
     }
     zx = x;
@@ -163,33 +109,33 @@ __device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][AL_B][AL_B], cons
 }
 
 template <int CLS>
-__global__ __launch_bounds__(AL_THREADS) void solve_blocks_kernel(int64_t n, int32_t k, const double *__restrict__ G,
+__global__ __launch_bounds__(GT_THREADS) void solve_blocks_kernel(int64_t n, int32_t k, const double *__restrict__ G,
                                                                  const double *__restrict__ b, int64_t ldb, double *__restrict__ x,
                                                                  int64_t ldx, int32_t *__restrict__ info)
 {
-    typedef AlClass<CLS> C;
-    constexpr int TEAM = C::TEAM, KP = C::KMAX, TPT = C::TPT, TEAMS = AL_THREADS / TEAM;
+    typedef GramClass<CLS> C;
+    constexpr int TEAM = C::TEAM, KP = C::KMAX, TPT = C::TPT, TEAMS = GT_THREADS / TEAM;
     __shared__ __attribute__((aligned(16))) double col[TEAMS][2][KP];
     __shared__ double piv[TEAMS][2];
 
     const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;
     const int64_t sys = (int64_t)blockIdx.x * TEAMS + team;
-    if (TEAM < AL_THREADS && sys >= n) return;                              // (a whole team; teams never meet at a barrier)
+    if (TEAM < GT_THREADS && sys >= n) return;                              // (a whole team; teams never meet at a barrier)
     const double *__restrict__ g = G + sys * k * k;
 
-    const int nb = (k + AL_B - 1) / AL_B, ntiles = nb * (nb + 1) / 2;
+    const int nb = (k + GT_B - 1) / GT_B, ntiles = nb * (nb + 1) / 2;
     int p0[TPT], q0[TPT];
     bool has[TPT];
-    double acc[TPT][AL_B][AL_B];
+    double acc[TPT][GT_B][GT_B];
 #pragma unroll
     for (int r = 0; r < TPT; r++) {
         const int t = tid + r * TEAM;
         has[r] = t < ntiles;
-        al_tile(t, has[r], p0[r], q0[r]);
+        gt_tile(t, has[r], p0[r], q0[r]);
 #pragma unroll
-        for (int i = 0; i < AL_B; i++)
+        for (int i = 0; i < GT_B; i++)
 #pragma unroll
-            for (int j = 0; j < AL_B; j++) {
+            for (int j = 0; j < GT_B; j++) {
                 const int p = p0[r] + i, q = q0[r] + j;
                 acc[r][i][j] = (has[r] && p < k && q <= p) ? g[(int64_t)p * k + q] : 0.0;
             }
@@ -201,128 +147,45 @@ __global__ __launch_bounds__(AL_THREADS) void solve_blocks_kernel(int64_t n, int
 }
 
 template <class T, bool WIDE, int CLS, bool SCALE>
-__global__ __launch_bounds__(AL_THREADS) void als_kernel(const void *__restrict__ rp, int ptr64, const int32_t *__restrict__ ci,
+__global__ __launch_bounds__(GT_THREADS) void als_kernel(const void *__restrict__ rp, int ptr64, const int32_t *__restrict__ ci,
                                                          const void *__restrict__ vals, int vt, int32_t row_begin, int32_t row_end,
                                                          const T *__restrict__ V, int64_t ldv, int32_t k, int rhs_mode,
                                                          const double *__restrict__ base, double lam_n, double *__restrict__ out,
                                                          int64_t ldo, int32_t *__restrict__ info)
 {
-    typedef AlClass<CLS> C;
-    constexpr int TEAM = C::TEAM, KP = C::KMAX, TPT = C::TPT, TEAMS = AL_THREADS / TEAM;
-    constexpr int PER = WIDE ? 16 / (int)sizeof(T) : 1;                     // elements per load
-    constexpr int NL = (AL_STAGE * (KP / PER) + TEAM - 1) / TEAM;           // loads per thread and step
-    __shared__ __attribute__((aligned(16))) double sv[TEAMS][2][AL_STAGE][KP];
+    typedef GramClass<CLS> C;
+    constexpr int TEAM = C::TEAM, KP = C::KMAX, TPT = C::TPT, TEAMS = GT_THREADS / TEAM;
+    __shared__ __attribute__((aligned(16))) double sv[TEAMS][2][GT_STAGE][KP];
     __shared__ __attribute__((aligned(16))) double col[TEAMS][2][KP];
-    __shared__ double sw[TEAMS][2][AL_STAGE];
+    __shared__ double sw[TEAMS][2][GT_STAGE];
     __shared__ double piv[TEAMS][2];
 
     const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;
     const int64_t row = (int64_t)row_begin + (int64_t)blockIdx.x * TEAMS + team;
-    if (TEAM < AL_THREADS && row >= row_end) return;                        // (a whole team; teams never meet at a barrier)
+    if (TEAM < GT_THREADS && row >= row_end) return;                        // (a whole team; teams never meet at a barrier)
     const int64_t e0 = ptr64 ? ((const int64_t *)rp)[row] : (int64_t)((const int32_t *)rp)[row];
     const int64_t e1 = ptr64 ? ((const int64_t *)rp)[row + 1] : (int64_t)((const int32_t *)rp)[row + 1];
 
     // this thread's tiles of the lower triangle
-    const int nb = (k + AL_B - 1) / AL_B, ntiles = nb * (nb + 1) / 2;
+    const int nb = (k + GT_B - 1) / GT_B, ntiles = nb * (nb + 1) / 2;
     int p0[TPT], q0[TPT];
     bool has[TPT];
-    double acc[TPT][AL_B][AL_B];
+    double acc[TPT][GT_B][GT_B];
 #pragma unroll
     for (int r = 0; r < TPT; r++) {
         const int t = tid + r * TEAM;
         has[r] = t < ntiles;
-        al_tile(t, has[r], p0[r], q0[r]);
+        gt_tile(t, has[r], p0[r], q0[r]);
 #pragma unroll
-        for (int i = 0; i < AL_B; i++)
+        for (int i = 0; i < GT_B; i++)
 #pragma unroll
-            for (int j = 0; j < AL_B; j++) {
+            for (int j = 0; j < GT_B; j++) {
                 const int p = p0[r] + i, q = q0[r] + j;
                 acc[r][i][j] = (has[r] && base && p < k && q <= p) ? base[(int64_t)p * k + q] : 0.0;
             }
     }
     double bacc = 0.0;                                                      // b[tid], for tid < k
-
-    // this thread's share of a step: unit x = tid + l TEAM is piece x % upr of staged entry x / upr
-    const int upr = k / PER;                                                // units per panel row (WIDE: k is a whole number of pieces)
-    int ue[NL], uo[NL];
-#pragma unroll
-    for (int l = 0; l < NL; l++) {
-        const int x = tid + l * TEAM;
-        ue[l] = x / upr;                                                    // (>= AL_STAGE: no such unit)
-        uo[l] = (x % upr) * PER;
-    }
-    const int64_t last = e1 - 1;
-    int32_t coln[NL] = {};                                                  // (only this thread's units are loaded)
-    double vreg[NL][PER], wreg = 1.0;                                       // (no values wanted or none stored: 1.0)
-    if (e0 < e1) {
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            const int64_t e = e0 + ue[l];
-            if (ue[l] < AL_STAGE) coln[l] = ci[e < last ? e : last];
-        }
-#pragma unroll
-        for (int l = 0; l < NL; l++)
-            if (ue[l] < AL_STAGE) al_load<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
-        if (vals && tid < AL_STAGE) {
-            const int64_t e = e0 + tid < last ? e0 + tid : last;
-            wreg = vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e];
-        }
-#pragma unroll
-        for (int l = 0; l < NL; l++) {
-            const int64_t e = e0 + AL_STAGE + ue[l];
-            if (ue[l] < AL_STAGE) coln[l] = ci[e < last ? e : last];
-        }
-    }
-
-    int buf = 0;
-    for (int64_t es = e0; es < e1; es += AL_STAGE, buf ^= 1) {
-        const int cnt = e1 - es < AL_STAGE ? (int)(e1 - es) : AL_STAGE;
-        // this step's V rows and weights: registers -> LDS  (entries past the row's end hold its last entry again, unused)
-#pragma unroll
-        for (int l = 0; l < NL; l++)
-            if (ue[l] < AL_STAGE) {
-#pragma unroll
-                for (int x = 0; x < PER; x++) sv[team][buf][ue[l]][uo[l] + x] = vreg[l][x];
-            }
-        if (tid < AL_STAGE) sw[team][buf][tid] = wreg;
-        al_team_sync<TEAM>();
-        // the next step's V rows and weights and the column indices of the step after it, in flight while this one is used
-        if (es + AL_STAGE < e1) {
-#pragma unroll
-            for (int l = 0; l < NL; l++)
-                if (ue[l] < AL_STAGE) al_load<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
-            if (vals && tid < AL_STAGE) {
-                const int64_t e = es + AL_STAGE + tid < last ? es + AL_STAGE + tid : last;
-                wreg = vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e];
-            }
-#pragma unroll
-            for (int l = 0; l < NL; l++) {
-                const int64_t e = es + 2 * AL_STAGE + ue[l];
-                if (ue[l] < AL_STAGE) coln[l] = ci[e < last ? e : last];
-            }
-        }
-        // the staged entries in storage order: t = round(w v_p), G[p][q] = fma(t, v_q, G[p][q]); b[p] = fma(c, v_p, b[p]).
-        // (Columns k .. 4 nb - 1 of a staged row are never written: an edge tile reads whatever LDS holds there into
-        // accumulators with p >= k or q >= k, which nothing below publishes.)
-        for (int x = 0; x < cnt; x++) {
-            const double wv = sw[team][buf][x];
-            const double w = SCALE ? wv : 1.0;
-            const double c = rhs_mode == CSRK_ALS_RHS_ONES ? 1.0 : (rhs_mode == CSRK_ALS_RHS_VALUES ? wv : 1.0 + wv);
-#pragma unroll
-            for (int r = 0; r < TPT; r++) {
-                const al_d2 a0 = *(const al_d2 *)&sv[team][buf][x][p0[r]], a1 = *(const al_d2 *)&sv[team][buf][x][p0[r] + 2];
-                const al_d2 b0 = *(const al_d2 *)&sv[team][buf][x][q0[r]], b1 = *(const al_d2 *)&sv[team][buf][x][q0[r] + 2];
-                const double vp[AL_B] = {a0.x, a0.y, a1.x, a1.y}, vq[AL_B] = {b0.x, b0.y, b1.x, b1.y};
-#pragma unroll
-                for (int i = 0; i < AL_B; i++) {
-                    const double t = SCALE ? __dmul_rn(w, vp[i]) : vp[i];
-#pragma unroll
-                    for (int j = 0; j < AL_B; j++) acc[r][i][j] = __builtin_fma(t, vq[j], acc[r][i][j]);
-                }
-            }
-            if (tid < k) bacc = __builtin_fma(c, sv[team][buf][x][tid], bacc);
-        }
-    }
+    gt_accumulate<T, WIDE, CLS, SCALE, true>(e0, e1, ci, vals, vt, V, ldv, k, rhs_mode, tid, sv[team], sw[team], acc, p0, q0, bacc);
 
     // the ridge, after the chain: G[p][p] = fma(lam_n, n_i, G[p][p])
     const double cnt_d = (double)(e1 - e0);
@@ -330,7 +193,7 @@ __global__ __launch_bounds__(AL_THREADS) void als_kernel(const void *__restrict_
     for (int r = 0; r < TPT; r++)
         if (p0[r] == q0[r]) {
 #pragma unroll
-            for (int i = 0; i < AL_B; i++) acc[r][i][i] = __builtin_fma(lam_n, cnt_d, acc[r][i][i]);
+            for (int i = 0; i < GT_B; i++) acc[r][i][i] = __builtin_fma(lam_n, cnt_d, acc[r][i][i]);
         }
 
     const int inf = al_ldl_solve<TEAM, TPT, KP>(acc, p0, q0, has, bacc, k, tid, col[team], piv[team]);
@@ -343,8 +206,8 @@ static int solve_check(int64_t n, int32_t k, int64_t ldb, int64_t ldx)
     CSRK_REQUIRE(n >= 0, "n must not be negative (n=%lld)", (long long)n);
     CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
     CSRK_REQUIRE(ldb >= k && ldx >= k, "bad geometry k=%d ldb=%lld ldx=%lld", k, (long long)ldb, (long long)ldx);
-    if (k > AL_K_MAX) {
-        set_error("csrk_solve_blocks: k=%d is above the largest supported k=%d (csrk_als_limits)", k, AL_K_MAX);
+    if (k > GT_K_MAX) {
+        set_error("csrk_solve_blocks: k=%d is above the largest supported k=%d (csrk_als_limits)", k, GT_K_MAX);
         return CSRK_ERR_UNSUPPORTED;
     }
     return CSRK_OK;
@@ -358,13 +221,13 @@ static int solve_device(int64_t n, int32_t k, const double *dG, const double *db
     CSRK_REQUIRE(dG && db && dx, "G, b or x is NULL");
     CSRK_REQUIRE(((uintptr_t)dG % 8) == 0 && ((uintptr_t)db % 8) == 0 && ((uintptr_t)dx % 8) == 0 && ((uintptr_t)dinfo % 4) == 0,
                  "G, b, x or info is not aligned to its element size");
-    const int team = k <= AL_K_SUB ? AlClass<0>::TEAM : k <= AL_K_WAVE ? AlClass<1>::TEAM : AL_THREADS;
-    CSRK_REQUIRE(ceil_div(n, AL_THREADS / team) <= INT32_MAX, "n=%lld systems are more than one launch takes", (long long)n);
+    const int team = k <= GT_K_SUB ? GramClass<0>::TEAM : k <= GT_K_WAVE ? GramClass<1>::TEAM : GT_THREADS;
+    CSRK_REQUIRE(ceil_div(n, GT_THREADS / team) <= INT32_MAX, "n=%lld systems are more than one launch takes", (long long)n);
 #define AL_GO(CLS) \
-    solve_blocks_kernel<CLS><<<(unsigned)ceil_div(n, AL_THREADS / AlClass<CLS>::TEAM), AL_THREADS, 0, s>>>(n, k, dG, db, ldb, dx, ldx, dinfo)
-    if (k <= AL_K_SUB) AL_GO(0);
-    else if (k <= AL_K_WAVE) AL_GO(1);
-    else if (k <= AL_K_ONE) AL_GO(2);
+    solve_blocks_kernel<CLS><<<(unsigned)ceil_div(n, GT_THREADS / GramClass<CLS>::TEAM), GT_THREADS, 0, s>>>(n, k, dG, db, ldb, dx, ldx, dinfo)
+    if (k <= GT_K_SUB) AL_GO(0);
+    else if (k <= GT_K_WAVE) AL_GO(1);
+    else if (k <= GT_K_ONE) AL_GO(2);
     else AL_GO(3);
 #undef AL_GO
     CSRK_LAUNCH_CHECK();
@@ -374,21 +237,12 @@ static int solve_device(int64_t n, int32_t k, const double *dG, const double *db
 static int als_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldv, int32_t k, int panel_type, int scale, int rhs_mode,
                      int64_t ldo)
 {
-    CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
-    CSRK_REQUIRE(ldv >= k, "bad panel geometry k=%d ldv=%lld", k, (long long)ldv);
+    CSRK_TRY(gt_check_geometry(ldv, k));
     CSRK_REQUIRE(ldo >= k, "bad output geometry k=%d ldo=%lld", k, (long long)ldo);
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64, "panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d",
-                 panel_type);
-    CSRK_REQUIRE(scale == 0 || scale == 1, "scale must be 0 or 1, not %d", scale);
+    CSRK_TRY(gt_check_kinds(panel_type, scale));
     CSRK_REQUIRE(rhs_mode == CSRK_ALS_RHS_ONES || rhs_mode == CSRK_ALS_RHS_VALUES || rhs_mode == CSRK_ALS_RHS_ONE_PLUS,
                  "rhs_mode must be CSRK_ALS_RHS_ONES, _VALUES or _ONE_PLUS, not %d", rhs_mode);
-    CSRK_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= m->nrows, "bad row range [%d, %d) of %d rows", row_begin,
-                 row_end, m->nrows);
-    if (k > AL_K_MAX) {
-        set_error("csrk_als_rows: k=%d is above the largest supported k=%d (csrk_als_limits)", k, AL_K_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
-    return CSRK_OK;
+    return gt_check_rows("csrk_als", m, row_begin, row_end, k);
 }
 
 static int als_device(Matrix *m, int32_t row_begin, int32_t row_end, const void *dV, int64_t ldv, int32_t k, int panel_type, int scale,
@@ -404,15 +258,13 @@ static int als_device(Matrix *m, int32_t row_begin, int32_t row_end, const void 
         std::lock_guard<std::mutex> lk(m->mu);
         if (s) m->used_user_stream = true;
     }
-    // 16-B loads when every piece of every panel row is whole and 16-B aligned; else element loads: the same bits
-    const int64_t per16 = (int64_t)(16 / es);
-    const bool wide = ((uintptr_t)dV & 15) == 0 && ldv % per16 == 0 && k % per16 == 0;
+    const bool wide = gt_panel_wide(dV, ldv, k, es);
     const bool stored = m->val_type != CSRK_VAL_NONE;               // (a structure-only matrix: every value is 1.0)
     const bool scaled = scale && stored;
     const void *vals = stored && (scaled || rhs_mode != CSRK_ALS_RHS_ONES) ? m->d_values : nullptr;
     const int64_t n = (int64_t)row_end - row_begin;
 #define AL_GO(T, W, CLS, SC)                                                                                            \
-    als_kernel<T, W, CLS, SC><<<(unsigned)ceil_div(n, AL_THREADS / AlClass<CLS>::TEAM), AL_THREADS, 0, s>>>(            \
+    als_kernel<T, W, CLS, SC><<<(unsigned)ceil_div(n, GT_THREADS / GramClass<CLS>::TEAM), GT_THREADS, 0, s>>>(            \
         m->d_rowptrs, m->ptr64, m->d_colinds, vals, m->val_type, row_begin, row_end, (const T *)dV, ldv, k, rhs_mode, dbase, lam_n, \
         dout, ldo, dinfo)
 #define AL_SC(T, W, CLS)                                                                                                \
@@ -422,9 +274,9 @@ static int als_device(Matrix *m, int32_t row_begin, int32_t row_end, const void 
     } while (0)
 #define AL_CLS(T, W)                                                                                                   \
     do {                                                                                                               \
-        if (k <= AL_K_SUB) AL_SC(T, W, 0);                                                                             \
-        else if (k <= AL_K_WAVE) AL_SC(T, W, 1);                                                                       \
-        else if (k <= AL_K_ONE) AL_SC(T, W, 2);                                                                        \
+        if (k <= GT_K_SUB) AL_SC(T, W, 0);                                                                             \
+        else if (k <= GT_K_WAVE) AL_SC(T, W, 1);                                                                       \
+        else if (k <= GT_K_ONE) AL_SC(T, W, 2);                                                                        \
         else AL_SC(T, W, 3);                                                                                           \
     } while (0)
     if (panel_type == CSRK_VAL_F64) {
@@ -450,7 +302,7 @@ extern "C" {
 int csrk_als_limits(int64_t *out, int n)
 {
     CSRK_REQUIRE(out && n >= 0, "csrk_als_limits: out is NULL or n < 0");
-    const int64_t v[5] = {AL_K_MAX, AL_STAGE, AL_K_SUB, AL_K_WAVE, AL_K_ONE};
+    const int64_t v[5] = {GT_K_MAX, GT_STAGE, GT_K_SUB, GT_K_WAVE, GT_K_ONE};
     for (int i = 0; i < n && i < 5; i++) out[i] = v[i];
     return CSRK_OK;
 }
@@ -502,15 +354,11 @@ int csrk_als_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const voi
     CSRK_TRY(als_check(m, row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, ldo));
     if (row_begin == row_end) return CSRK_OK;
     CSRK_REQUIRE(out && (V || m->nnz == 0), "V or out is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
     const size_t n = (size_t)(row_end - row_begin);
-    // the panel travels packed (ld = k): the bits do not depend on the stride
     DevBuf dV, dB, dO, dI;
-    CSRK_TRY(dV.alloc((size_t)m->ncols * k * es));
+    CSRK_TRY(gt_pack_panel(dV, V, ldv, k, panel_type == CSRK_VAL_F64 ? 8 : 4, m->ncols));
     CSRK_TRY(dO.alloc(n * k * 8));
     CSRK_TRY(dI.alloc(n * 4));
-    if (m->ncols && V)
-        CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, m->ncols, hipMemcpyHostToDevice));
     if (base) {
         CSRK_TRY(dB.alloc((size_t)k * k * 8));
         CSRK_HIP(hipMemcpy(dB.p, base, (size_t)k * k * 8, hipMemcpyHostToDevice));

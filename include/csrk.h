@@ -348,7 +348,8 @@ CSRK_API int csrk_gram_limits(int64_t *out, int n);
 /* ---- the ALS half-step: solve each row's normal equations ----------------------------------------
  * Not reference entry points.  csrk_solve_blocks solves n packed symmetric k x k systems; csrk_als_rows builds each row's
  * system (csrk_gram_rows' block, a ridge, the right-hand side) in one pass over the row's entries and solves it on the
- * chip: k float64 per row are written, the k x k block never is.  Both run one device routine (csrc/als.hip), so
+ * chip: k float64 per row are written, the k x k block never is.  It accumulates with the routine csrk_gram_rows runs
+ * (csrc/gram_tile.h) and both solve with one device routine (csrc/als.hip), so
  * csrk_als_rows equals csrk_gram_rows + the ridge + csrk_solve_blocks bit for bit.  All arithmetic is float64;
  * fma(-a, b, c) is round(c - a b), one rounding.
  *

@@ -84,7 +84,7 @@ def _pd_base(k, seed, lam=0.5):
 def limits():
     from csr_amd.kernels import hip as K
     lim = K.als_limits()
-    assert lim[1] == K.gram_limits()[1]
+    assert tuple(lim) == tuple(K.gram_limits())          # one set of constants (csrc/gram_tile.h)
     return lim
 
 

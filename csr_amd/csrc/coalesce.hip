@@ -20,28 +20,13 @@
 //           same bits.  (One column 10^6 times in one row is 10^6 dependent adds on one lane.)
 // Every slot is counted, nothing is appended in arrival order and no atomic touches a value: the result is a function of
 // (h, dup).  Column indices are compared and copied, never used as addresses.
-#include "common.h"
+#include "result.h"
 
 namespace csrk {
 
 int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 
 static thread_local int g_coalesce_route = 0;
-
-// the last row that starts at or before entry e: the row that holds it (nrows >= 1, rp[0] = 0 <= e)
-template <class P>
-__device__ __forceinline__ int64_t co_row_of(const P *__restrict__ rp, int32_t nrows, int64_t e)
-{
-    int64_t lo = 0, hi = (int64_t)nrows - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if ((int64_t)rp[mid] <= e)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
 
 // ---- LOOK -------------------------------------------------------------------------------------------------------------------
 // res[0]: the lowest row that is not strictly ascending (INT32_MAX: none);  res[1]: 1 if some entry lies below its predecessor
@@ -54,7 +39,7 @@ __global__ __launch_bounds__(256) void coalesce_look_kernel(const P *__restrict_
     if (e >= nnz) return;
     const int32_t a = ci[e - 1], b = ci[e];
     if (a < b) return;
-    const int64_t r = co_row_of(rp, nrows, e);
+    const int64_t r = last_at_or_below(rp, 0, (int64_t)nrows - 1, e);      // the row that holds e (nrows >= 1, rp[0] = 0 <= e)
     if ((int64_t)rp[r] == e) return;                  // starts a row
     atomicMin(res, (int32_t)r);
     if (b < a) atomicOr(res + 1, 1);
@@ -100,19 +85,8 @@ __global__ __launch_bounds__(256) void coalesce_flag_kernel(const P *__restrict_
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nnz) return;
     bool head = true;
-    if (e > 0 && ci[e] == ci[e - 1]) head = (int64_t)rp[co_row_of(rp, nrows, e)] == e;
+    if (e > 0 && ci[e] == ci[e - 1]) head = (int64_t)rp[last_at_or_below(rp, 0, (int64_t)nrows - 1, e)] == e;
     flags[e] = head ? 1 : 0;
-}
-
-// result row pointers: pos[rowptr[r]], or rowptr[r] itself for a copy (pos = NULL)
-template <class P, class C, class PO>
-__global__ __launch_bounds__(256) void coalesce_rowptr_kernel(const P *__restrict__ rp, int32_t nrows, const C *__restrict__ pos,
-                                                             PO *__restrict__ orp)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > nrows) return;
-    const int64_t s = (int64_t)rp[r];
-    orp[r] = (PO)(pos ? (int64_t)pos[s] : s);
 }
 
 // ---- PLACE ------------------------------------------------------------------------------------------------------------------
@@ -180,44 +154,11 @@ __global__ __launch_bounds__(256) void coalesce_place_kernel(const CoArgs g)
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-static int fail_hip(Matrix *t, hipError_t e)
-{
-    set_error("coalesce failed: %s", hipGetErrorString(e));
-    delete t;
-    return CSRK_ERR_HIP;
-}
-
 static void mark_canonical(Matrix *t)
 {
     t->canonical = 1;
     t->noncanonical_row = -1;
     t->nondescending = 1;
-}
-
-static int empty_coalesced(Matrix *m, Matrix **out)
-{
-    Matrix *t = nullptr;
-    CSRK_TRY(new_matrix(m->nrows, m->ncols, 0, 0, m->val_type, &t));
-    const hipError_t e = hipMemset(t->d_rowptrs, 0, (size_t)(m->nrows + 1) * 4);
-    if (e != hipSuccess) return fail_hip(t, e);
-    *out = t;
-    return CSRK_OK;
-}
-
-template <class P, class C, class PO>
-static void launch_rowptr_as(const Matrix *m, const C *pos, Matrix *t)
-{
-    coalesce_rowptr_kernel<P, C, PO><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256>>>((const P *)m->d_rowptrs, m->nrows, pos,
-                                                                                           (PO *)t->d_rowptrs);
-}
-
-template <class P, class C>
-static void launch_rowptr(const Matrix *m, const C *pos, Matrix *t)
-{
-    if (t->ptr64)
-        launch_rowptr_as<P, C, int64_t>(m, pos, t);
-    else
-        launch_rowptr_as<P, C, int32_t>(m, pos, t);
 }
 
 // route 0: a device copy (the row pointers narrowed where h's are wider than the result needs)
@@ -226,13 +167,12 @@ static int copy_impl(Matrix *m, Matrix **out)
 {
     Matrix *t = nullptr;
     CSRK_TRY(new_matrix(m->nrows, m->ncols, m->nnz, m->nnz > INT32_MAX, m->val_type, &t));
-    launch_rowptr<P, int32_t>(m, (const int32_t *)nullptr, t);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(t->d_colinds, m->d_colinds, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, nullptr);
-    if (e == hipSuccess && m->val_type != CSRK_VAL_NONE)
-        e = hipMemcpyAsync(t->d_values, m->d_values, (size_t)m->nnz * m->val_bytes(), hipMemcpyDeviceToDevice, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail_hip(t, e);
+    write_rowptrs_through<P, int32_t>(m, nullptr, t);
+    // (a copy that cannot be issued is the thread's last error, like a launch that cannot: finish_result reports either)
+    (void)hipMemcpyAsync(t->d_colinds, m->d_colinds, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice, nullptr);
+    if (m->val_type != CSRK_VAL_NONE)
+        (void)hipMemcpyAsync(t->d_values, m->d_values, (size_t)m->nnz * m->val_bytes(), hipMemcpyDeviceToDevice, nullptr);
+    CSRK_TRY(finish_result(t, "coalesce"));
     *out = t;
     return CSRK_OK;
 }
@@ -245,30 +185,21 @@ static int merge_impl(Matrix *m, const int32_t *ci, const void *vs, int vti, int
     const unsigned grid = (unsigned)ceil_div(nnz, 256);
     DevBuf pos;
     CSRK_TRY(pos.alloc((size_t)(nnz + 1) * sizeof(C)));
-    // the device drains before `pos` goes back to the pool, on every way out
-    struct DrainOnExit {
-        ~DrainOnExit() { (void)hipDeviceSynchronize(); }
-    } drain_on_exit;
+    DrainOnExit drain_on_exit;      // (before `pos` goes back to the pool)
     coalesce_flag_kernel<P, C><<<grid, 256>>>((const P *)m->d_rowptrs, ci, m->nrows, nnz, pos.as<C>());
     CSRK_LAUNCH_CHECK();
-    if (sizeof(C) == 8)
-        CSRK_TRY(exclusive_scan_i64((const int64_t *)pos.p, (int64_t *)pos.p, nnz, nullptr));
-    else
-        CSRK_TRY(exclusive_scan_i32((const int32_t *)pos.p, (int32_t *)pos.p, nnz, nullptr));
     C total = 0;
-    CSRK_HIP(hipMemcpy(&total, pos.as<C>() + nnz, sizeof(C), hipMemcpyDeviceToHost));
+    CSRK_TRY(scan_total(pos.as<C>(), nnz, &total));
     Matrix *t = nullptr;
     CSRK_TRY(new_matrix(m->nrows, m->ncols, (int64_t)total, (int64_t)total > INT32_MAX, m->val_type, &t));
-    launch_rowptr<P, C>(m, pos.as<C>(), t);
+    write_rowptrs_through<P, C>(m, pos.as<C>(), t);
     CoArgs g{};
     g.ci = ci, g.vs = vs, g.pos = pos.p;
     g.vti = vti, g.vto = m->val_type, g.dup = dup, g.pos64 = sizeof(C) == 8;
     g.nnz = nnz;
     g.oc = t->d_colinds, g.ov = t->d_values;
     coalesce_place_kernel<<<grid, 256>>>(g);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail_hip(t, e);
+    CSRK_TRY(finish_result(t, "coalesce"));
     *out = t;
     return CSRK_OK;
 }
@@ -323,7 +254,7 @@ int csrk_coalesce(csrk_handle_t h, int dup, csrk_handle_t *out)
     Matrix *t = nullptr;
     int route = 0;
     if (m->nrows == 0 || m->nnz == 0)                 // an empty result; nothing is launched
-        CSRK_TRY(empty_coalesced(m, &t));
+        CSRK_TRY(empty_matrix(m->nrows, m->ncols, m->val_type, "coalesce", &t));
     else
         CSRK_TRY(coalesce_impl(m, dup, &route, &t));
     mark_canonical(t);

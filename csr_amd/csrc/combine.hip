@@ -19,7 +19,7 @@
 //   0 .. CB_WAVE_MAX     one WAVEFRONT per row, in chunks of 64 entries (no LDS, no barrier)
 //   above                one CB_THREADS-thread WORKGROUP per listed row, in chunks of CB_THREADS entries, one barrier each
 // Column indices are compared and copied, never used as addresses.
-#include "common.h"
+#include "result.h"
 #include "wave.h"
 
 #include <functional>
@@ -43,11 +43,6 @@ struct CbArgs {
     int32_t *oc;
     void *ov;
 };
-
-__device__ __forceinline__ int64_t cb_ptr(const void *rp, int is64, int64_t i)
-{
-    return is64 ? ((const int64_t *)rp)[i] : (int64_t)((const int32_t *)rp)[i];
-}
 
 // a value as the arithmetic sees it: float32 widened exactly, 1.0 for a structure-only operand
 __device__ __forceinline__ double cb_val(const void *v, int vt, int64_t e)
@@ -82,8 +77,8 @@ __device__ __forceinline__ void cb_row(const CbArgs &g, int64_t r, int t, uint32
 #pragma clang fp contract(off)
     const int lane = t & (WAVE - 1), w = t / WAVE;
     const unsigned long long below = lane ? (~0ull >> (WAVE - lane)) : 0ull;
-    const int64_t spa = cb_ptr(g.rpa, g.pa64, r), spb = cb_ptr(g.rpb, g.pb64, r);
-    const uint32_t la = (uint32_t)(cb_ptr(g.rpa, g.pa64, r + 1) - spa), lb = (uint32_t)(cb_ptr(g.rpb, g.pb64, r + 1) - spb);
+    const int64_t spa = load_ptr(g.rpa, g.pa64, r), spb = load_ptr(g.rpb, g.pb64, r);
+    const uint32_t la = (uint32_t)(load_ptr(g.rpa, g.pa64, r + 1) - spa), lb = (uint32_t)(load_ptr(g.rpb, g.pb64, r + 1) - spb);
     const int32_t *__restrict__ ca = g.ca + spa;
     const int32_t *__restrict__ cb = g.cb + spb;
     const int op = g.op;
@@ -186,8 +181,8 @@ __global__ __launch_bounds__(256) void combine_wave_kernel(const CbArgs g)
 {
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     if (r >= g.nrows) return;                         // (whole wavefronts leave together)
-    const int64_t len = (cb_ptr(g.rpa, g.pa64, r + 1) - cb_ptr(g.rpa, g.pa64, r)) +
-                        (cb_ptr(g.rpb, g.pb64, r + 1) - cb_ptr(g.rpb, g.pb64, r));
+    const int64_t len = (load_ptr(g.rpa, g.pa64, r + 1) - load_ptr(g.rpa, g.pa64, r)) +
+                        (load_ptr(g.rpb, g.pb64, r + 1) - load_ptr(g.rpb, g.pb64, r));
     if (len > CB_WAVE_MAX) return;                    // the workgroup kernel's
     cb_row<WAVE, PLACE>(g, r, threadIdx.x & (WAVE - 1), nullptr);
 }
@@ -204,8 +199,8 @@ __global__ __launch_bounds__(256) void combine_class_kernel(const CbArgs g, int3
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= g.nrows) return;
-    const int64_t la = cb_ptr(g.rpa, g.pa64, r + 1) - cb_ptr(g.rpa, g.pa64, r);
-    const int64_t lb = cb_ptr(g.rpb, g.pb64, r + 1) - cb_ptr(g.rpb, g.pb64, r);
+    const int64_t la = load_ptr(g.rpa, g.pa64, r + 1) - load_ptr(g.rpa, g.pa64, r);
+    const int64_t lb = load_ptr(g.rpb, g.pb64, r + 1) - load_ptr(g.rpb, g.pb64, r);
     if (la < 0 || la > INT32_MAX || lb < 0 || lb > INT32_MAX) atomicOr(bad, 1);
     is_long[r] = la + lb > CB_WAVE_MAX ? 1 : 0;
 }
@@ -214,30 +209,9 @@ __global__ __launch_bounds__(256) void combine_list_kernel(const CbArgs g, const
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= g.nrows) return;
-    const int64_t len = (cb_ptr(g.rpa, g.pa64, r + 1) - cb_ptr(g.rpa, g.pa64, r)) +
-                        (cb_ptr(g.rpb, g.pb64, r + 1) - cb_ptr(g.rpb, g.pb64, r));
+    const int64_t len = (load_ptr(g.rpa, g.pa64, r + 1) - load_ptr(g.rpa, g.pa64, r)) +
+                        (load_ptr(g.rpb, g.pb64, r + 1) - load_ptr(g.rpb, g.pb64, r));
     if (len > CB_WAVE_MAX) list[pos[r]] = (int32_t)r;
-}
-
-template <class PO>
-__global__ __launch_bounds__(256) void combine_ptr_kernel(const int64_t *__restrict__ off, int64_t nr, PO *__restrict__ orp)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= nr) orp[i] = (PO)off[i];
-}
-
-static int empty_result(int32_t nrows, int32_t ncols, int vt, Matrix **out)
-{
-    Matrix *t = nullptr;
-    CSRK_TRY(new_matrix(nrows, ncols, 0, 0, vt, &t));
-    hipError_t e = hipMemset(t->d_rowptrs, 0, (size_t)(nrows + 1) * 4);
-    if (e != hipSuccess) {
-        set_error("combine failed: %s", hipGetErrorString(e));
-        delete t;
-        return CSRK_ERR_HIP;
-    }
-    *out = t;
-    return CSRK_OK;
 }
 
 static int combine_impl(Matrix *a, Matrix *b, int op, double alpha, double beta, int vt, Matrix **out)
@@ -249,10 +223,7 @@ static int combine_impl(Matrix *a, Matrix *b, int op, double alpha, double beta,
     CSRK_TRY(lpos.alloc((size_t)(nrows + 1) * 4));
     CSRK_TRY(cnt.alloc((size_t)(nrows + 1) * 8));
     CSRK_TRY(bad.alloc(4));
-    // the device drains before the buffers above go back to the pool, on every way out
-    struct DrainOnExit {
-        ~DrainOnExit() { (void)hipDeviceSynchronize(); }
-    } drain_on_exit;
+    DrainOnExit drain_on_exit;      // (before the buffers above go back to the pool)
     CbArgs g{};
     g.rpa = a->d_rowptrs, g.rpb = b->d_rowptrs;
     g.ca = a->d_colinds, g.cb = b->d_colinds;
@@ -264,9 +235,8 @@ static int combine_impl(Matrix *a, Matrix *b, int op, double alpha, double beta,
     CSRK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
     combine_class_kernel<<<gr, 256>>>(g, lpos.as<int32_t>(), bad.as<int32_t>());
     CSRK_LAUNCH_CHECK();
-    CSRK_TRY(exclusive_scan_i32(lpos.as<int32_t>(), lpos.as<int32_t>(), nrows, nullptr));
     int32_t n_long = 0, is_bad = 0;
-    CSRK_HIP(hipMemcpy(&n_long, lpos.as<int32_t>() + nrows, 4, hipMemcpyDeviceToHost));
+    CSRK_TRY(scan_total(lpos.as<int32_t>(), nrows, &n_long));
     CSRK_HIP(hipMemcpy(&is_bad, bad.p, 4, hipMemcpyDeviceToHost));
     if (is_bad) {
         set_error("combine: a row holds more than 2^31 - 1 entries");
@@ -282,16 +252,11 @@ static int combine_impl(Matrix *a, Matrix *b, int op, double alpha, double beta,
     }
     combine_wave_kernel<false><<<gw, 256>>>(g);
     CSRK_LAUNCH_CHECK();
-    CSRK_TRY(exclusive_scan_i64(cnt.as<int64_t>(), cnt.as<int64_t>(), nrows, nullptr));
     int64_t total = 0;
-    CSRK_HIP(hipMemcpy(&total, cnt.as<int64_t>() + nrows, 8, hipMemcpyDeviceToHost));
+    CSRK_TRY(scan_total(cnt.as<int64_t>(), nrows, &total));
     Matrix *t = nullptr;
     CSRK_TRY(new_matrix(nrows, a->ncols, total, total > INT32_MAX, vt, &t));
-    const unsigned gp = (unsigned)ceil_div((int64_t)nrows + 1, 256);
-    if (t->ptr64)
-        combine_ptr_kernel<int64_t><<<gp, 256>>>(cnt.as<int64_t>(), nrows, (int64_t *)t->d_rowptrs);
-    else
-        combine_ptr_kernel<int32_t><<<gp, 256>>>(cnt.as<int64_t>(), nrows, (int32_t *)t->d_rowptrs);
+    write_rowptrs(cnt.as<int64_t>(), nrows, t);
     if (total > 0) {
         g.off = cnt.as<int64_t>();
         g.cnt = nullptr;
@@ -300,13 +265,7 @@ static int combine_impl(Matrix *a, Matrix *b, int op, double alpha, double beta,
         if (n_long > 0) combine_block_kernel<true><<<(unsigned)n_long, CB_THREADS>>>(g);
         combine_wave_kernel<true><<<gw, 256>>>(g);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        set_error("combine failed: %s", hipGetErrorString(e));
-        delete t;
-        return CSRK_ERR_HIP;
-    }
+    CSRK_TRY(finish_result(t, "combine"));
     *out = t;
     return CSRK_OK;
 }
@@ -350,7 +309,7 @@ int csrk_combine(csrk_handle_t ah, csrk_handle_t bh, int op, double alpha, doubl
     const int vt = mask ? a->val_type : CSRK_VAL_F64;
     Matrix *t = nullptr;
     if (a->nrows == 0 || (a->nnz == 0 && b->nnz == 0)) {      // an empty result; nothing is launched
-        CSRK_TRY(empty_result(a->nrows, a->ncols, vt, &t));
+        CSRK_TRY(empty_matrix(a->nrows, a->ncols, vt, "combine", &t));
         *out = to_handle(t);
         return CSRK_OK;
     }

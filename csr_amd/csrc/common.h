@@ -173,8 +173,24 @@ int exclusive_scan_i32_to_i64(const int32_t *in, int64_t *out, int64_t n, hipStr
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Row-pointer load that works for both widths.
-template <class P> struct PtrTraits;
-template <> struct PtrTraits<int32_t> { static constexpr int is64 = 0; };
-template <> struct PtrTraits<int64_t> { static constexpr int is64 = 1; };
+__device__ __forceinline__ int64_t load_ptr(const void *rp, int is64, int64_t i)
+{
+    return is64 ? ((const int64_t *)rp)[i] : (int64_t)((const int32_t *)rp)[i];
+}
+
+// Row search over offsets: the largest r in [lo, hi] with p[r] <= e (p non-descending, p[lo] <= e; repeated offsets --
+// empty rows -- give the last of them: the row that holds entry e).
+template <class P>
+__device__ __forceinline__ int64_t last_at_or_below(const P *__restrict__ p, int64_t lo, int64_t hi, int64_t e)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((int64_t)p[mid] <= e)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
 
 }  // namespace csrk

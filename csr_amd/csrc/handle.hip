@@ -3,6 +3,7 @@
 // protocol (csr/kernels/numba/__init__.py:16-44; csr/kernels/mkl/handle.py:61-148) and
 // row_extent / row_nnzs (csr/_rows.py:9-13, csr/csr.py:432-441).
 #include "common.h"
+#include "result.h"
 
 #include <cstring>
 #include <ctime>
@@ -309,6 +310,47 @@ int new_matrix(int32_t nrows, int32_t ncols, int64_t nnz, int ptr64, int val_typ
     }
     *out = m;
     return CSRK_OK;
+}
+
+// ---- the other steps of building a result matrix (result.h) ------------------------------------
+template <class PO>
+__global__ __launch_bounds__(256) void offsets_to_rowptrs_kernel(const int64_t *__restrict__ off, int64_t nr, PO *__restrict__ orp)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= nr) orp[i] = (PO)off[i];
+}
+
+void write_rowptrs(const int64_t *off, int64_t nr, Matrix *t)
+{
+    const unsigned grid = (unsigned)ceil_div(nr + 1, 256);
+    if (t->ptr64)
+        offsets_to_rowptrs_kernel<int64_t><<<grid, 256>>>(off, nr, (int64_t *)t->d_rowptrs);
+    else
+        offsets_to_rowptrs_kernel<int32_t><<<grid, 256>>>(off, nr, (int32_t *)t->d_rowptrs);
+}
+
+int empty_matrix(int32_t nrows, int32_t ncols, int val_type, const char *what, Matrix **out)
+{
+    Matrix *t = nullptr;
+    CSRK_TRY(new_matrix(nrows, ncols, 0, 0, val_type, &t));
+    const hipError_t e = hipMemset(t->d_rowptrs, 0, (size_t)(nrows + 1) * 4);
+    if (e != hipSuccess) {
+        set_error("%s failed: %s", what, hipGetErrorString(e));
+        delete t;
+        return CSRK_ERR_HIP;
+    }
+    *out = t;
+    return CSRK_OK;
+}
+
+int finish_result(Matrix *t, const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) return CSRK_OK;
+    set_error("%s failed: %s", what, hipGetErrorString(e));
+    delete t;
+    return CSRK_ERR_HIP;
 }
 
 template <class P>

@@ -60,11 +60,6 @@ __device__ __forceinline__ int re_slot(const uint64_t *__restrict__ sk, const in
     return lo;
 }
 
-__device__ __forceinline__ int64_t re_ptr(const void *__restrict__ rp, int ptr64, int64_t row)
-{
-    return ptr64 ? ((const int64_t *)rp)[row] : (int64_t)((const int32_t *)rp)[row];
-}
-
 template <class T, bool WIDE>
 __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__restrict__ seen_rp, int seen_ptr64,
                                                                  const int32_t *__restrict__ seen_ci, const void *__restrict__ test_rp,
@@ -88,7 +83,7 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
     const int lane = tid & (WAVE - 1), w = tid / WAVE;
     const int64_t r0 = (int64_t)blockIdx.x * TS_ROWS;             // the block's first row, relative to row_begin
     const int64_t nvalid = (int64_t)nrows - r0 < TS_ROWS ? (int64_t)nrows - r0 : TS_ROWS;
-    const int64_t base = re_ptr(test_rp, test_ptr64, row_begin);
+    const int64_t base = load_ptr(test_rp, test_ptr64, row_begin);
 
     if (tid == 0) s_nsw = 0;
     __syncthreads();
@@ -96,11 +91,11 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
         int64_t t0 = 0, t1 = 0, e0 = 0, e1 = 0;
         if (tid < nvalid) {
             const int64_t row = (int64_t)row_begin + r0 + tid;
-            t0 = re_ptr(test_rp, test_ptr64, row);
-            t1 = re_ptr(test_rp, test_ptr64, row + 1);
+            t0 = load_ptr(test_rp, test_ptr64, row);
+            t1 = load_ptr(test_rp, test_ptr64, row + 1);
             if (seen_rp) {
-                e0 = re_ptr(seen_rp, seen_ptr64, row);
-                e1 = re_ptr(seen_rp, seen_ptr64, row + 1);
+                e0 = load_ptr(seen_rp, seen_ptr64, row);
+                e1 = load_ptr(seen_rp, seen_ptr64, row + 1);
             }
         }
         if (t1 < t0) t1 = t0;

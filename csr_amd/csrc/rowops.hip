@@ -19,7 +19,7 @@
 //                                row is then 245 workgroups instead of one (one workgroup per long row: 1.9 ms of the
 //                                former 4.0 ms of kernels on the headline matrix, bound by its longest row on one CU).
 // HBM traffic: values 1 read + 1 write (A, B), 2 reads + 1 write (C); row pointers once; norms once.
-#include "common.h"
+#include "result.h"
 
 #include <atomic>
 
@@ -558,13 +558,7 @@ static int row_stat(Matrix *m, void *out_host, void *out_dev)
     std::lock_guard<std::mutex> side_lk(*side.turn);
     // declared after every DevBuf above: on ANY early return the device drains (both streams) before the buffers go back to
     // the pool (the normal path ends in a synchronisation of its own and disarms this one)
-    struct DrainOnExit {
-        bool armed = true;
-        ~DrainOnExit()
-        {
-            if (armed) (void)hipDeviceSynchronize();
-        }
-    } drain_on_exit;
+    DrainOnExit drain_on_exit;
 #define GO(P, T)                                                                                                       \
     do {                                                                                                               \
         row_class_count_kernel<P><<<ga, 256>>>((const P *)m->d_rowptrs, m->nrows, n_waves, counts.as<int32_t>());       \
@@ -670,43 +664,26 @@ __global__ void nz_compact_kernel(const int32_t *__restrict__ ci, const double *
 }
 
 template <class P, class C>
-__global__ void nz_rowptr_kernel(const P *__restrict__ rp, int32_t nrows, const C *__restrict__ pos, P *__restrict__ orp)
-{
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r <= nrows) orp[r] = (P)pos[rp[r]];
-}
-
-template <class P, class C>
 static int filter_impl(Matrix *m, Matrix **out)
 {
     const int64_t nnz = m->nnz;
     DevBuf pos;
     CSRK_TRY(pos.alloc((size_t)(nnz + 1) * sizeof(C)));
+    DrainOnExit drain_on_exit;      // (before `pos` goes back to the pool)
     if (nnz > 0) {
         nz_flag_kernel<C><<<(unsigned)ceil_div(nnz, 256), 256>>>((const double *)m->d_values, nnz, pos.as<C>());
         CSRK_LAUNCH_CHECK();
     }
-    if (sizeof(C) == 8)
-        CSRK_TRY(exclusive_scan_i64((const int64_t *)pos.p, (int64_t *)pos.p, nnz, nullptr));
-    else
-        CSRK_TRY(exclusive_scan_i32((const int32_t *)pos.p, (int32_t *)pos.p, nnz, nullptr));
     C total = 0;
-    CSRK_HIP(hipMemcpy(&total, pos.as<C>() + nnz, sizeof(C), hipMemcpyDeviceToHost));
+    CSRK_TRY(scan_total(pos.as<C>(), nnz, &total));
     Matrix *f = nullptr;
-    CSRK_TRY(new_matrix(m->nrows, m->ncols, (int64_t)total, m->ptr64, CSRK_VAL_F64, &f));
+    CSRK_TRY(new_matrix(m->nrows, m->ncols, (int64_t)total, m->ptr64, CSRK_VAL_F64, &f));      // the input's pointer width
     if (nnz > 0) {
         nz_compact_kernel<C><<<(unsigned)ceil_div(nnz, 256), 256>>>(m->d_colinds, (const double *)m->d_values, nnz,
                                                                     pos.as<C>(), f->d_colinds, (double *)f->d_values);
     }
-    nz_rowptr_kernel<P, C><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256>>>((const P *)m->d_rowptrs, m->nrows,
-                                                                                    pos.as<C>(), (P *)f->d_rowptrs);
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("filter_zeros kernels failed: %s", hipGetErrorString(e));
-        delete f;
-        return CSRK_ERR_HIP;
-    }
+    write_rowptrs_through<P, C>(m, pos.as<C>(), f);
+    CSRK_TRY(finish_result(f, "filter_zeros kernels"));
     *out = f;
     return CSRK_OK;
 }
@@ -756,6 +733,8 @@ __global__ __launch_bounds__(256) void pick_copy_kernel(const P *__restrict__ rp
         // last picked row whose offset is <= the workgroup's first (threadIdx 0) / last (1) entry
         int64_t o = threadIdx.x == 0 ? base : base + 256 * PICK_EPT - 1;
         o = o < nnz - 1 ? o : nnz - 1;
+        // (last_at_or_below of common.h, written out here and below: through the helper the compiler orders both loops'
+        // instructions differently)
         int64_t lo = 0, hi = nr - 1;
         while (lo < hi) {
             const int64_t mid = (lo + hi + 1) >> 1;
@@ -786,38 +765,28 @@ __global__ __launch_bounds__(256) void pick_copy_kernel(const P *__restrict__ rp
     }
 }
 
-template <class PO>
-__global__ void pick_ptr_kernel(const int64_t *__restrict__ off, int64_t nr, PO *__restrict__ orp)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= nr) orp[i] = (PO)off[i];
-}
-
 template <class P, class T>
 static int pick_impl(Matrix *m, const int32_t *d_rows, int64_t nr, int vt, Matrix **out)
 {
     DevBuf len, bad;
     CSRK_TRY(len.alloc((size_t)(nr + 2) * 8));
     CSRK_TRY(bad.alloc(4));
+    DrainOnExit drain_on_exit;      // (before the buffers above go back to the pool)
     CSRK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
     pick_len_kernel<P><<<(unsigned)ceil_div(nr + 1, 256), 256>>>((const P *)m->d_rowptrs, d_rows, nr, m->nrows,
                                                                 len.as<int64_t>(), bad.as<int32_t>());
     CSRK_LAUNCH_CHECK();
-    CSRK_TRY(exclusive_scan_i64(len.as<int64_t>(), len.as<int64_t>(), nr, nullptr));
     int64_t nnz = 0;
     int32_t is_bad = 0;
-    CSRK_HIP(hipMemcpy(&nnz, len.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost));
+    CSRK_TRY(scan_total(len.as<int64_t>(), nr, &nnz));
     CSRK_HIP(hipMemcpy(&is_bad, bad.p, 4, hipMemcpyDeviceToHost));
     CSRK_REQUIRE(!is_bad, "pick_rows: row index out of range [0, %d)", m->nrows);
     const int p64 = nnz > INT32_MAX;
     Matrix *t = nullptr;
     CSRK_TRY(new_matrix((int32_t)nr, m->ncols, nnz, p64, vt, &t));
-    const unsigned gp = (unsigned)ceil_div(nr + 1, 256), grid = (unsigned)ceil_div(nnz, 256 * PICK_EPT);
+    const unsigned grid = (unsigned)ceil_div(nnz, 256 * PICK_EPT);
     const T *vs = vt == CSRK_VAL_NONE ? (const T *)nullptr : (const T *)m->d_values;
-    if (p64)
-        pick_ptr_kernel<int64_t><<<gp, 256>>>(len.as<int64_t>(), nr, (int64_t *)t->d_rowptrs);
-    else
-        pick_ptr_kernel<int32_t><<<gp, 256>>>(len.as<int64_t>(), nr, (int32_t *)t->d_rowptrs);
+    write_rowptrs(len.as<int64_t>(), nr, t);
     if (nnz > 0) {
         if (p64)
             pick_copy_kernel<P, int64_t, T><<<grid, 256>>>((const P *)m->d_rowptrs, m->d_colinds, vs, d_rows, nr,
@@ -826,13 +795,7 @@ static int pick_impl(Matrix *m, const int32_t *d_rows, int64_t nr, int vt, Matri
             pick_copy_kernel<P, int32_t, T><<<grid, 256>>>((const P *)m->d_rowptrs, m->d_colinds, vs, d_rows, nr,
                                                           len.as<int64_t>(), nnz, t->d_colinds, (T *)t->d_values);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();      // `len` goes back to the pool on return
-    if (e != hipSuccess) {
-        set_error("pick_rows failed: %s", hipGetErrorString(e));
-        delete t;
-        return CSRK_ERR_HIP;
-    }
+    CSRK_TRY(finish_result(t, "pick_rows"));
     *out = t;
     return CSRK_OK;
 }

@@ -26,7 +26,7 @@
 // selected twice; rows that keep fewer (threshold) are then closed up by one copy of the RESULT (k entries per row, not
 // the input).  When every row keeps its bound the bounded arrays ARE the result.
 // No float atomic, no unordered append decides a winner or its place: the result is a function of the inputs.
-#include "common.h"
+#include "result.h"
 #include "wave.h"
 
 namespace csrk {
@@ -370,13 +370,6 @@ __global__ __launch_bounds__(NT) void topk_long_kernel(const P *__restrict__ rp,
 }
 
 // ---- closing up: rows that kept fewer entries than their bound ---------------------------------------------------------
-template <class PO>
-__global__ __launch_bounds__(256) void topk_ptr_kernel(const int64_t *__restrict__ off, int64_t nr, PO *__restrict__ orp)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= nr) orp[i] = (PO)off[i];
-}
-
 // one thread per entry of the result: its row is the last one whose offset is <= the entry (empty rows repeat an offset)
 template <class T>
 __global__ __launch_bounds__(256) void topk_close_kernel(const int64_t *__restrict__ ooff, const int64_t *__restrict__ boff,
@@ -386,8 +379,8 @@ __global__ __launch_bounds__(256) void topk_close_kernel(const int64_t *__restri
 {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= total) return;
-    int64_t lo = 0, hi = nr - 1;
-    while (lo < hi) {
+    int64_t lo = 0, hi = nr - 1;      // last_at_or_below (common.h), written out: through the helper the compiler orders
+    while (lo < hi) {                 // this loop's instructions differently
         const int64_t mid = (lo + hi + 1) >> 1;
         if (ooff[mid] <= o)
             lo = mid;
@@ -412,10 +405,7 @@ static int topk_impl(Matrix *m, int64_t k, double minv, int by_value, Matrix **o
     CSRK_TRY(kept.alloc((size_t)nrows * 4));
     CSRK_TRY(ooff.alloc((size_t)(nrows + 1) * 8));
     CSRK_TRY(bad.alloc(4));
-    // the device drains before the buffers above go back to the pool, on every way out
-    struct DrainOnExit {
-        ~DrainOnExit() { (void)hipDeviceSynchronize(); }
-    } drain_on_exit;
+    DrainOnExit drain_on_exit;      // (before the buffers above go back to the pool)
     CSRK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
     topk_bound_kernel<P><<<gr, 256>>>(rp, nrows, k, boff.as<int64_t>(), mpos.as<int32_t>(), lpos.as<int32_t>(), bad.as<int32_t>());
     CSRK_LAUNCH_CHECK();
@@ -467,33 +457,20 @@ static int topk_impl(Matrix *m, int64_t k, double minv, int by_value, Matrix **o
     CSRK_TRY(exclusive_scan_i32_to_i64(kept.as<int32_t>(), ooff.as<int64_t>(), nrows, nullptr));
     int64_t total = 0;
     CSRK_HIP(hipMemcpy(&total, ooff.as<int64_t>() + nrows, 8, hipMemcpyDeviceToHost));
-    const unsigned gp = (unsigned)ceil_div((int64_t)nrows + 1, 256);
     Matrix *res = nullptr;
     if (total == btotal) {      // every row kept its bound: the bounded arrays are the result
         res = t;
-        if (res->ptr64)
-            topk_ptr_kernel<int64_t><<<gp, 256>>>(boff.as<int64_t>(), nrows, (int64_t *)res->d_rowptrs);
-        else
-            topk_ptr_kernel<int32_t><<<gp, 256>>>(boff.as<int64_t>(), nrows, (int32_t *)res->d_rowptrs);
+        write_rowptrs(boff.as<int64_t>(), nrows, res);
         CSRK_LAUNCH_CHECK();
     } else {
         CSRK_TRY(new_matrix(nrows, m->ncols, total, total > INT32_MAX, m->val_type, &res));
-        if (res->ptr64)
-            topk_ptr_kernel<int64_t><<<gp, 256>>>(ooff.as<int64_t>(), nrows, (int64_t *)res->d_rowptrs);
-        else
-            topk_ptr_kernel<int32_t><<<gp, 256>>>(ooff.as<int64_t>(), nrows, (int32_t *)res->d_rowptrs);
+        write_rowptrs(ooff.as<int64_t>(), nrows, res);
         if (total > 0)
             topk_close_kernel<T><<<(unsigned)ceil_div(total, 256), 256>>>(ooff.as<int64_t>(), boff.as<int64_t>(), nrows, total,
                                                                          t->d_colinds, (const T *)t->d_values,
                                                                          res->d_colinds, (T *)res->d_values);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        set_error("topk_rows failed: %s", hipGetErrorString(e));
-        if (res != t) delete res;
-        return CSRK_ERR_HIP;
-    }
+    CSRK_TRY(finish_result(res != t ? res : nullptr, "topk_rows"));      // (t_own deletes the bounded arrays)
     if (res == t) t_own.p = nullptr;
     *out = res;
     return CSRK_OK;
@@ -526,13 +503,7 @@ int csrk_topk_rows(csrk_handle_t h, int64_t k, double min_value, int order, csrk
     std::lock_guard<std::mutex> lk(m->mu);
     Matrix *t = nullptr;
     if (m->nrows == 0 || m->nnz == 0) {      // an empty result; nothing is launched
-        CSRK_TRY(new_matrix(m->nrows, m->ncols, 0, 0, m->val_type, &t));
-        hipError_t e = hipMemset(t->d_rowptrs, 0, (size_t)(m->nrows + 1) * 4);
-        if (e != hipSuccess) {
-            set_error("topk_rows failed: %s", hipGetErrorString(e));
-            delete t;
-            return CSRK_ERR_HIP;
-        }
+        CSRK_TRY(empty_matrix(m->nrows, m->ncols, m->val_type, "topk_rows", &t));
         *out = to_handle(t);
         return CSRK_OK;
     }

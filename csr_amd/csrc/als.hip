@@ -204,7 +204,7 @@ __global__ __launch_bounds__(GT_THREADS) void als_kernel(const void *__restrict_
 static int solve_check(int64_t n, int32_t k, int64_t ldb, int64_t ldx)
 {
     CSRK_REQUIRE(n >= 0, "n must not be negative (n=%lld)", (long long)n);
-    CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
+    CSRK_CHECK_K("", k);
     CSRK_REQUIRE(ldb >= k && ldx >= k, "bad geometry k=%d ldb=%lld ldx=%lld", k, (long long)ldb, (long long)ldx);
     if (k > GT_K_MAX) {
         set_error("csrk_solve_blocks: k=%d is above the largest supported k=%d (csrk_als_limits)", k, GT_K_MAX);
@@ -237,9 +237,11 @@ static int solve_device(int64_t n, int32_t k, const double *dG, const double *db
 static int als_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldv, int32_t k, int panel_type, int scale, int rhs_mode,
                      int64_t ldo)
 {
-    CSRK_TRY(gt_check_geometry(ldv, k));
+    CSRK_CHECK_K("", k);
+    CSRK_CHECK_ONE_PANEL(k, ldv);
     CSRK_REQUIRE(ldo >= k, "bad output geometry k=%d ldo=%lld", k, (long long)ldo);
-    CSRK_TRY(gt_check_kinds(panel_type, scale));
+    CSRK_CHECK_PANEL_TYPE("", panel_type);
+    CSRK_CHECK_SCALE(scale);
     CSRK_REQUIRE(rhs_mode == CSRK_ALS_RHS_ONES || rhs_mode == CSRK_ALS_RHS_VALUES || rhs_mode == CSRK_ALS_RHS_ONE_PLUS,
                  "rhs_mode must be CSRK_ALS_RHS_ONES, _VALUES or _ONE_PLUS, not %d", rhs_mode);
     return gt_check_rows("csrk_als", m, row_begin, row_end, k);
@@ -251,14 +253,11 @@ static int als_device(Matrix *m, int32_t row_begin, int32_t row_end, const void 
     CSRK_TRY(als_check(m, row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, ldo));
     if (row_begin == row_end) return CSRK_OK;
     CSRK_REQUIRE(dout && (dV || m->nnz == 0), "V or out is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dV % es) == 0 && ((uintptr_t)dout % 8) == 0 && ((uintptr_t)dbase % 8) == 0 && ((uintptr_t)dinfo % 4) == 0,
                  "V, base, out or info is not aligned to its element size");
-    {
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (s) m->used_user_stream = true;
-    }
-    const bool wide = gt_panel_wide(dV, ldv, k, es);
+    mark_user_stream(m, s);
+    const bool wide = panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
     const bool stored = m->val_type != CSRK_VAL_NONE;               // (a structure-only matrix: every value is 1.0)
     const bool scaled = scale && stored;
     const void *vals = stored && (scaled || rhs_mode != CSRK_ALS_RHS_ONES) ? m->d_values : nullptr;
@@ -324,13 +323,12 @@ int csrk_solve_blocks(int64_t n, int32_t k, const double *G, const double *b, in
     CSRK_HIP(hipGetDevice(&dev));                                           // (no handle vouches for a device here)
     DevBuf dG, dB, dX, dI;
     CSRK_TRY(dG.alloc(ng));
-    CSRK_TRY(dB.alloc(nv));
     CSRK_TRY(dX.alloc(nv));
     CSRK_TRY(dI.alloc((size_t)n * 4));
     CSRK_HIP(hipMemcpy(dG.p, G, ng, hipMemcpyHostToDevice));
-    CSRK_HIP(hipMemcpy2D(dB.p, (size_t)k * 8, b, (size_t)ldb * 8, (size_t)k * 8, (size_t)n, hipMemcpyHostToDevice));
+    CSRK_TRY(pack_panel(dB, b, ldb, k, 8, n));
     CSRK_TRY(solve_device(n, k, dG.as<double>(), dB.as<double>(), k, dX.as<double>(), k, dI.as<int32_t>(), nullptr));
-    CSRK_HIP(hipMemcpy2D(x, (size_t)ldx * 8, dX.p, (size_t)k * 8, (size_t)k * 8, (size_t)n, hipMemcpyDeviceToHost));
+    CSRK_TRY(unpack_panel(x, ldx, dX, k, 8, n));
     if (info) CSRK_HIP(hipMemcpy(info, dI.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return CSRK_OK;
 }
@@ -356,7 +354,7 @@ int csrk_als_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const voi
     CSRK_REQUIRE(out && (V || m->nnz == 0), "V or out is NULL");
     const size_t n = (size_t)(row_end - row_begin);
     DevBuf dV, dB, dO, dI;
-    CSRK_TRY(gt_pack_panel(dV, V, ldv, k, panel_type == CSRK_VAL_F64 ? 8 : 4, m->ncols));
+    CSRK_TRY(pack_panel(dV, V, ldv, k, panel_es(panel_type), m->ncols));
     CSRK_TRY(dO.alloc(n * k * 8));
     CSRK_TRY(dI.alloc(n * 4));
     if (base) {
@@ -365,7 +363,7 @@ int csrk_als_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const voi
     }
     CSRK_TRY(als_device(m, row_begin, row_end, dV.p, k, k, panel_type, scale, rhs_mode, base ? dB.as<double>() : nullptr, lam_n,
                         dO.as<double>(), k, dI.as<int32_t>(), nullptr));
-    CSRK_HIP(hipMemcpy2D(out, (size_t)ldo * 8, dO.p, (size_t)k * 8, (size_t)k * 8, n, hipMemcpyDeviceToHost));
+    CSRK_TRY(unpack_panel(out, ldo, dO, k, 8, n));
     if (info) CSRK_HIP(hipMemcpy(info, dI.p, n * 4, hipMemcpyDeviceToHost));
     return CSRK_OK;
 }

@@ -79,8 +79,10 @@ __global__ __launch_bounds__(GT_THREADS) void gram_kernel(const void *__restrict
 
 static int gram_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldv, int32_t k, int panel_type, int scale)
 {
-    CSRK_TRY(gt_check_geometry(ldv, k));
-    CSRK_TRY(gt_check_kinds(panel_type, scale));
+    CSRK_CHECK_K("", k);
+    CSRK_CHECK_ONE_PANEL(k, ldv);
+    CSRK_CHECK_PANEL_TYPE("", panel_type);
+    CSRK_CHECK_SCALE(scale);
     return gt_check_rows("csrk_gram", m, row_begin, row_end, k);
 }
 
@@ -90,14 +92,11 @@ static int gram_device(Matrix *m, int32_t row_begin, int32_t row_end, const void
     CSRK_TRY(gram_check(m, row_begin, row_end, ldv, k, panel_type, scale));
     if (row_begin == row_end) return CSRK_OK;
     CSRK_REQUIRE(dout && (dV || m->nnz == 0), "V or out is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dV % es) == 0 && ((uintptr_t)dout % 8) == 0 && ((uintptr_t)dbase % 8) == 0,
                  "V, base or out is not aligned to its element size");
-    {
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (s) m->used_user_stream = true;
-    }
-    const bool wide = gt_panel_wide(dV, ldv, k, es);
+    mark_user_stream(m, s);
+    const bool wide = panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
     const bool scaled = scale && m->val_type != CSRK_VAL_NONE;      // (a structure-only matrix: w = 1.0, as scale = 0)
     const int64_t n = (int64_t)row_end - row_begin;
 #define GR_GO(T, W, CLS, SC)                                                                                            \
@@ -162,7 +161,7 @@ int csrk_gram_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const vo
     CSRK_REQUIRE(out && (V || m->nnz == 0), "V or out is NULL");
     const size_t nout = (size_t)(row_end - row_begin) * k * k * 8;
     DevBuf dV, dB, dO;
-    CSRK_TRY(gt_pack_panel(dV, V, ldv, k, panel_type == CSRK_VAL_F64 ? 8 : 4, m->ncols));
+    CSRK_TRY(pack_panel(dV, V, ldv, k, panel_es(panel_type), m->ncols));
     CSRK_TRY(dO.alloc(nout));
     if (base) {
         CSRK_TRY(dB.alloc((size_t)k * k * 8));

@@ -3,7 +3,7 @@
 // in 4 x 4 register tiles, and with RHS the right-hand side b = sum c_e v_j beside it.  One definition of the k classes, the
 // panel loads, the team fence, the tile numbering, the staging pipeline and the multiply-add loop, so that an als_rows row
 // and a gram_rows row are the same arithmetic (include/csrk.h, rule A) because they are the same code; and the host-side
-// argument checks and panel handling of the two entries.
+// refusal of a k above the classes.  (Panel checks, the 16-B predicate and packing: panel.h.)
 //
 // Work split.  A TEAM of threads owns a row: 16 lanes for k <= 16, a wavefront for k <= 40, a 256-thread workgroup above.
 // The lower triangle is cut into 4 x 4 register tiles (tile (bp, bq), bq <= bp, holds p = 4 bp .. 4 bp + 3, q = 4 bq ..
@@ -16,6 +16,7 @@
 // pieces, else element by element: the same bits.
 #pragma once
 #include "common.h"
+#include "panel.h"
 
 namespace csrk {
 
@@ -174,47 +175,14 @@ __device__ __forceinline__ void gt_accumulate(int64_t e0, int64_t e1, const int3
     }
 }
 
-// ---- host side: what csrk_gram_rows and csrk_als_rows check and do alike -------------------------------------------------
-// The checks come in the order both entries report them; als.hip puts its own (ldo, rhs_mode) between the pieces.
-static int gt_check_geometry(int64_t ldv, int32_t k)
-{
-    CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
-    CSRK_REQUIRE(ldv >= k, "bad panel geometry k=%d ldv=%lld", k, (long long)ldv);
-    return CSRK_OK;
-}
-
-static int gt_check_kinds(int panel_type, int scale)
-{
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64, "panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d",
-                 panel_type);
-    CSRK_REQUIRE(scale == 0 || scale == 1, "scale must be 0 or 1, not %d", scale);
-    return CSRK_OK;
-}
-
-// stem: "csrk_gram" or "csrk_als", for the names the UNSUPPORTED message gives
+// ---- host side: the row range and the k classes' limit; stem, "csrk_gram" or "csrk_als", is what the UNSUPPORTED message names
 static int gt_check_rows(const char *stem, const Matrix *m, int32_t row_begin, int32_t row_end, int32_t k)
 {
-    CSRK_REQUIRE(row_begin >= 0 && row_begin <= row_end && row_end <= m->nrows, "bad row range [%d, %d) of %d rows", row_begin,
-                 row_end, m->nrows);
+    CSRK_CHECK_ROW_RANGE("", row_begin, row_end, m->nrows);
     if (k > GT_K_MAX) {
         set_error("%s_rows: k=%d is above the largest supported k=%d (%s_limits)", stem, k, GT_K_MAX, stem);
         return CSRK_ERR_UNSUPPORTED;
     }
-    return CSRK_OK;
-}
-
-// 16-B loads when every piece of every panel row is whole and 16-B aligned; else element loads: the same bits
-static bool gt_panel_wide(const void *dV, int64_t ldv, int32_t k, size_t es)
-{
-    const int64_t per16 = (int64_t)(16 / es);
-    return ((uintptr_t)dV & 15) == 0 && ldv % per16 == 0 && k % per16 == 0;
-}
-
-// the panel travels packed (ld = k): the bits do not depend on the stride
-static int gt_pack_panel(DevBuf &dV, const void *V, int64_t ldv, int32_t k, size_t es, int64_t ncols)
-{
-    CSRK_TRY(dV.alloc((size_t)ncols * k * es));
-    if (ncols && V) CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, ncols, hipMemcpyHostToDevice));
     return CSRK_OK;
 }
 

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "panel.h"
 #include "score_tile.h"
 
 namespace csrk {
@@ -266,11 +267,10 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
 // the refusals that need no handle come first: they are answered whatever the handles are
 static int re_scalars(int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t k, int panel_type)
 {
-    CSRK_REQUIRE(k >= 1, "rank_entries: k must be at least 1 (k=%d)", k);
-    CSRK_REQUIRE(ldu >= k && ldv >= k, "rank_entries: bad panel geometry k=%d ldu=%lld ldv=%lld", k, (long long)ldu, (long long)ldv);
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64,
-                 "rank_entries: panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d", panel_type);
-    CSRK_REQUIRE(row_begin >= 0 && row_begin <= row_end, "rank_entries: bad row range [%d, %d)", row_begin, row_end);
+    CSRK_CHECK_K("rank_entries: ", k);
+    CSRK_CHECK_TWO_PANELS("rank_entries: ", k, ldu, ldv);
+    CSRK_CHECK_PANEL_TYPE("rank_entries: ", panel_type);
+    CSRK_CHECK_ROW_ORDER("rank_entries: ", row_begin, row_end);
     if (k > RE_K_MAX) {
         set_error("csrk_rank_entries: k=%d is above the largest supported k=%d (csrk_rank_entries_limits)", k, RE_K_MAX);
         return CSRK_ERR_UNSUPPORTED;
@@ -288,7 +288,7 @@ static int re_check(csrk_handle_t seen_h, csrk_handle_t test_h, int32_t row_begi
     }
     test = from_handle(test_h);
     if (!test) return CSRK_ERR_INVALID;
-    CSRK_REQUIRE(row_end <= test->nrows, "rank_entries: bad row range [%d, %d) of %d rows", row_begin, row_end, test->nrows);
+    CSRK_CHECK_ROW_RANGE("rank_entries: ", row_begin, row_end, test->nrows);
     if (seen) {
         CSRK_REQUIRE(seen->nrows == test->nrows && seen->ncols == test->ncols, "rank_entries: seen is %d x %d but test is %d x %d",
                      seen->nrows, seen->ncols, test->nrows, test->ncols);
@@ -310,20 +310,12 @@ static int re_device(Matrix *seen, Matrix *test, int32_t row_begin, int32_t row_
 {
     CSRK_REQUIRE(dranks, "rank_entries: ranks is NULL");
     CSRK_REQUIRE(dU && dV, "rank_entries: U or V is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 && ((uintptr_t)dranks % 4) == 0,
                  "rank_entries: U, V, ranks or scores is not aligned to its element size");
-    if (s) {
-        if (seen) {
-            std::lock_guard<std::mutex> lk(seen->mu);
-            seen->used_user_stream = true;
-        }
-        std::lock_guard<std::mutex> lk(test->mu);
-        test->used_user_stream = true;
-    }
-    // 16-B loads when every piece of every row of both panels is whole and 16-B aligned; else element loads: the same bits
-    const int64_t per16 = (int64_t)(16 / es);
-    const bool wide = ((uintptr_t)dU & 15) == 0 && ((uintptr_t)dV & 15) == 0 && ldu % per16 == 0 && ldv % per16 == 0 && k % per16 == 0;
+    mark_user_stream(seen, s);
+    mark_user_stream(test, s);
+    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
     const char *env = getenv("CSRK_RANK_ENTRIES_COUNT");          // diagnostic: "0" times the product alone (the outputs are not written)
     const int count = !(env && env[0] == '0' && !env[1]);
     const int32_t n = row_end - row_begin;
@@ -366,8 +358,7 @@ int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, int32_t row
     CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
     CSRK_TRY(re_check(seen, test, row_begin, row_end, &ms, &mt));
     if (row_begin == row_end || mt->nnz == 0) return CSRK_OK;
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
-    const void *u0 = d_U ? (const char *)d_U + (size_t)row_begin * (size_t)ldu * es : nullptr;
+    const void *u0 = panel_rows_from(d_U, row_begin, ldu, panel_es(panel_type));
     return re_device(ms, mt, row_begin, row_end, u0, ldu, d_V, ldv, k, panel_type, d_ranks, d_scores, (hipStream_t)stream);
 }
 
@@ -394,19 +385,15 @@ int csrk_rank_entries(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin,
     if (e[1] <= e[0]) return CSRK_OK;
     CSRK_REQUIRE(ranks, "rank_entries: ranks is NULL");
     CSRK_REQUIRE(U && V, "rank_entries: U or V is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)U % es) == 0 && ((uintptr_t)V % es) == 0 && ((uintptr_t)scores % 8) == 0 && ((uintptr_t)ranks % 4) == 0,
                  "rank_entries: U, V, ranks or scores is not aligned to its element size");
     const size_t n = (size_t)(row_end - row_begin), ne = (size_t)(e[1] - e[0]), n_items = (size_t)mt->ncols;
-    // the panels travel packed (ld = k): the bits do not depend on the stride
     DevBuf dU, dV, dR, dS;
-    CSRK_TRY(dU.alloc(n * k * es));
-    CSRK_TRY(dV.alloc(n_items * k * es));
+    CSRK_TRY(pack_panel(dU, panel_rows_from(U, row_begin, ldu, es), ldu, k, es, n));
+    CSRK_TRY(pack_panel(dV, V, ldv, k, es, n_items));
     CSRK_TRY(dR.alloc(ne * 4));
     if (scores) CSRK_TRY(dS.alloc(ne * 8));
-    CSRK_HIP(hipMemcpy2D(dU.p, (size_t)k * es, (const char *)U + (size_t)row_begin * (size_t)ldu * es, (size_t)ldu * es, (size_t)k * es, n,
-                         hipMemcpyHostToDevice));
-    if (n_items) CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, n_items, hipMemcpyHostToDevice));
     CSRK_TRY(re_device(ms, mt, row_begin, row_end, dU.p, k, dV.p, k, k, panel_type, dR.as<int32_t>(), scores ? dS.as<double>() : nullptr,
                        nullptr));
     CSRK_HIP(hipMemcpy(ranks, dR.p, ne * 4, hipMemcpyDeviceToHost));

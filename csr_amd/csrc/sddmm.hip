@@ -27,6 +27,7 @@
 // + ... in that fixed shape).  With scale = 1 the value (float32 widened, 1.0 when there are none) multiplies the sum
 // once, after it.
 #include "common.h"
+#include "panel.h"
 #include "wave.h"
 
 namespace csrk {
@@ -256,27 +257,28 @@ __global__ __launch_bounds__(SD_THREADS) void sddmm_kernel(const P *__restrict__
     }
 }
 
+static int sddmm_check(int64_t ldu, int64_t ldv, int32_t k, int panel_type, int scale)
+{
+    CSRK_CHECK_K("", k);
+    CSRK_CHECK_TWO_PANELS("", k, ldu, ldv);
+    CSRK_CHECK_PANEL_TYPE("", panel_type);
+    CSRK_CHECK_SCALE(scale);
+    return CSRK_OK;
+}
+
 static int sddmm_device(Matrix *m, const void *dU, int64_t ldu, const void *dV, int64_t ldv, int32_t k, int panel_type,
                         int scale, double *dout, hipStream_t s)
 {
-    CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
-    CSRK_REQUIRE(ldu >= k && ldv >= k, "bad panel geometry k=%d ldu=%lld ldv=%lld", k, (long long)ldu, (long long)ldv);
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64, "panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d",
-                 panel_type);
-    CSRK_REQUIRE(scale == 0 || scale == 1, "scale must be 0 or 1, not %d", scale);
+    CSRK_TRY(sddmm_check(ldu, ldv, k, panel_type, scale));
     if (m->nnz == 0 || m->nrows == 0) return CSRK_OK;
     CSRK_REQUIRE(dU && dV && dout, "U, V or out is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dout % 8) == 0,
                  "U, V or out is not aligned to its element size");
-    {
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (s) m->used_user_stream = true;
-    }
+    mark_user_stream(m, s);
     // 16-B loads when every lane's four columns start 16-B aligned: base pointers 16-B aligned, strides a multiple of
     // 16 B.  Otherwise element loads (8 B for float64, 4 B for float32): the same products in the same order.
-    const int64_t per16 = (int64_t)(16 / es);
-    const bool wide = ((uintptr_t)dU & 15) == 0 && ((uintptr_t)dV & 15) == 0 && ldu % per16 == 0 && ldv % per16 == 0;
+    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es);
     const int vt = scale ? m->val_type : CSRK_VAL_NONE;
     const int64_t groups = ceil_div(m->nnz, SD_RUN);
     const unsigned grid = (unsigned)ceil_div(groups, (int64_t)(SD_THREADS / WAVE) * SD_GROUPS);
@@ -330,22 +332,14 @@ int csrk_sddmm(csrk_handle_t h, const void *U, int64_t ldu, const void *V, int64
     Matrix *m = from_handle(h);
     if (!m) return CSRK_ERR_INVALID;
     // argument checks first, with the caller's pointers (the device call below sees packed copies)
-    CSRK_REQUIRE(k >= 1, "k must be at least 1 (k=%d)", k);
-    CSRK_REQUIRE(ldu >= k && ldv >= k, "bad panel geometry k=%d ldu=%lld ldv=%lld", k, (long long)ldu, (long long)ldv);
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64, "panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d",
-                 panel_type);
-    CSRK_REQUIRE(scale == 0 || scale == 1, "scale must be 0 or 1, not %d", scale);
+    CSRK_TRY(sddmm_check(ldu, ldv, k, panel_type, scale));
     if (m->nnz == 0 || m->nrows == 0) return CSRK_OK;
     CSRK_REQUIRE(U && V && out, "U, V or out is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
-    // the panels travel packed (ld = k): the bits do not depend on the strides
+    const size_t es = panel_es(panel_type);
     DevBuf dU, dV, dO;
-    CSRK_TRY(dU.alloc((size_t)m->nrows * k * es));
-    CSRK_TRY(dV.alloc((size_t)m->ncols * k * es));
+    CSRK_TRY(pack_panel(dU, U, ldu, k, es, m->nrows));
+    CSRK_TRY(pack_panel(dV, V, ldv, k, es, m->ncols));
     CSRK_TRY(dO.alloc((size_t)m->nnz * 8));
-    CSRK_HIP(hipMemcpy2D(dU.p, (size_t)k * es, U, (size_t)ldu * es, (size_t)k * es, m->nrows, hipMemcpyHostToDevice));
-    if (m->ncols)
-        CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, m->ncols, hipMemcpyHostToDevice));
     CSRK_TRY(sddmm_device(m, dU.p, k, dV.p, k, k, panel_type, scale, dO.as<double>(), nullptr));
     CSRK_HIP(hipMemcpy(out, dO.p, (size_t)m->nnz * 8, hipMemcpyDeviceToHost));
     return CSRK_OK;

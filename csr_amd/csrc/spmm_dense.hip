@@ -18,6 +18,7 @@
 // round trips (segment -> row pointer -> entries -> B rows -> store) that only wavefront count hid.  Segment
 // partial panels are combined in segment order by a second kernel -- no float atomics, bitwise reproducible.
 #include "common.h"
+#include "panel.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1037,12 +1038,10 @@ int csrk_spmm_dense(csrk_handle_t h, const double *B, int32_t k, int64_t ldb, do
     CSRK_REQUIRE(k >= 0 && ldb >= k && ldc >= k, "bad panel geometry");
     if (m->nrows == 0 || k == 0) return CSRK_OK;
     DevBuf dB, dC;
-    CSRK_TRY(dB.alloc((size_t)m->ncols * k * 8));
+    CSRK_TRY(pack_panel(dB, B, ldb, k, 8, m->ncols));
     CSRK_TRY(dC.alloc((size_t)m->nrows * k * 8));
-    if (m->ncols)
-        CSRK_HIP(hipMemcpy2D(dB.p, (size_t)k * 8, B, (size_t)ldb * 8, (size_t)k * 8, m->ncols, hipMemcpyHostToDevice));
     CSRK_TRY(spmm_device(m, dB.as<double>(), k, k, dC.as<double>(), k, nullptr));
-    CSRK_HIP(hipMemcpy2D(C, (size_t)ldc * 8, dC.p, (size_t)k * 8, (size_t)k * 8, m->nrows, hipMemcpyDeviceToHost));
+    CSRK_TRY(unpack_panel(C, ldc, dC, k, 8, m->nrows));
     return CSRK_OK;
 }
 

@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "panel.h"
 #include "score_tile.h"
 
 namespace csrk {
@@ -242,18 +243,17 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_kernel(const void *__r
 static int ts_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t n_items, int32_t k, int panel_type,
                     int32_t n_top, double min_score, int64_t ldi, int64_t lds)
 {
-    CSRK_REQUIRE(k >= 1, "topk_scores: k must be at least 1 (k=%d)", k);
+    CSRK_CHECK_K("topk_scores: ", k);
     CSRK_REQUIRE(n_top >= 1, "topk_scores: n_top must be at least 1 (n_top=%d)", n_top);
     CSRK_REQUIRE(n_items >= 0, "topk_scores: n_items must not be negative (n_items=%d)", n_items);
-    CSRK_REQUIRE(ldu >= k && ldv >= k, "topk_scores: bad panel geometry k=%d ldu=%lld ldv=%lld", k, (long long)ldu, (long long)ldv);
+    CSRK_CHECK_TWO_PANELS("topk_scores: ", k, ldu, ldv);
     CSRK_REQUIRE(ldi >= n_top && lds >= n_top, "topk_scores: bad output geometry n_top=%d ldi=%lld lds=%lld", n_top, (long long)ldi,
                  (long long)lds);
-    CSRK_REQUIRE(panel_type == CSRK_VAL_F32 || panel_type == CSRK_VAL_F64,
-                 "topk_scores: panel_type must be CSRK_VAL_F32 or CSRK_VAL_F64, not %d", panel_type);
+    CSRK_CHECK_PANEL_TYPE("topk_scores: ", panel_type);
     CSRK_REQUIRE(min_score == min_score, "topk_scores: min_score is NaN");
-    CSRK_REQUIRE(row_begin >= 0 && row_begin <= row_end, "topk_scores: bad row range [%d, %d)", row_begin, row_end);
+    CSRK_CHECK_ROW_ORDER("topk_scores: ", row_begin, row_end);
     if (m) {
-        CSRK_REQUIRE(row_end <= m->nrows, "topk_scores: bad row range [%d, %d) of %d rows", row_begin, row_end, m->nrows);
+        CSRK_CHECK_ROW_RANGE("topk_scores: ", row_begin, row_end, m->nrows);
         CSRK_REQUIRE(n_items == m->ncols, "topk_scores: n_items=%d but seen has %d columns", n_items, m->ncols);
         std::lock_guard<std::mutex> lk(m->mu);
         CSRK_TRY(look_at_rows(m));                                // (remembered: a device pass only the first time a handle is asked)
@@ -282,17 +282,12 @@ static int ts_device(Matrix *m, int32_t row_begin, int32_t row_end, const void *
     CSRK_REQUIRE(ditems && dscores, "topk_scores: items or scores is NULL");
     CSRK_REQUIRE(dU, "topk_scores: U is NULL");
     CSRK_REQUIRE(dV || n_items == 0, "topk_scores: V is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 &&
                      ((uintptr_t)ditems % 4) == 0 && ((uintptr_t)dcounts % 4) == 0,
                  "topk_scores: U, V, items, scores or counts is not aligned to its element size");
-    if (m && s) {
-        std::lock_guard<std::mutex> lk(m->mu);
-        m->used_user_stream = true;
-    }
-    // 16-B loads when every piece of every row of both panels is whole and 16-B aligned; else element loads: the same bits
-    const int64_t per16 = (int64_t)(16 / es);
-    const bool wide = ((uintptr_t)dU & 15) == 0 && ((uintptr_t)dV & 15) == 0 && ldu % per16 == 0 && ldv % per16 == 0 && k % per16 == 0;
+    mark_user_stream(m, s);
+    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
     const char *env = getenv("CSRK_TOPK_SCORES_SELECT");          // diagnostic: "0" times the product alone (the outputs are not written)
     const int select = !(env && env[0] == '0' && !env[1]);
     const int32_t n = row_end - row_begin;
@@ -343,8 +338,7 @@ int csrk_topk_scores_device(csrk_handle_t seen, int32_t row_begin, int32_t row_e
         if (!m) return CSRK_ERR_INVALID;
     }
     CSRK_TRY(ts_check(m, row_begin, row_end, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds));
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
-    const void *u0 = d_U ? (const char *)d_U + (size_t)row_begin * (size_t)ldu * es : nullptr;
+    const void *u0 = panel_rows_from(d_U, row_begin, ldu, panel_es(panel_type));
     return ts_device(m, row_begin, row_end, u0, ldu, d_V, ldv, n_items, k, panel_type, n_top, min_score, d_items, ldi, d_scores, lds,
                      d_counts, (hipStream_t)stream);
 }
@@ -364,25 +358,20 @@ int csrk_topk_scores(csrk_handle_t seen, int32_t row_begin, int32_t row_end, con
     CSRK_REQUIRE(items && scores, "topk_scores: items or scores is NULL");
     CSRK_REQUIRE(U, "topk_scores: U is NULL");
     CSRK_REQUIRE(V || n_items == 0, "topk_scores: V is NULL");
-    const size_t es = panel_type == CSRK_VAL_F64 ? 8 : 4;
+    const size_t es = panel_es(panel_type);
     const size_t n = (size_t)(row_end - row_begin);
     int dev = 0;
     CSRK_HIP(hipGetDevice(&dev));                                           // (without a handle nothing vouches for a device)
-    // the panels travel packed (ld = k): the bits do not depend on the stride
     DevBuf dU, dV, dI, dS, dC;
-    CSRK_TRY(dU.alloc(n * k * es));
-    CSRK_TRY(dV.alloc((size_t)n_items * k * es));
+    CSRK_TRY(pack_panel(dU, panel_rows_from(U, row_begin, ldu, es), ldu, k, es, n));
+    CSRK_TRY(pack_panel(dV, V, ldv, k, es, n_items));
     CSRK_TRY(dI.alloc(n * n_top * 4));
     CSRK_TRY(dS.alloc(n * n_top * 8));
     CSRK_TRY(dC.alloc(n * 4));
-    CSRK_HIP(hipMemcpy2D(dU.p, (size_t)k * es, (const char *)U + (size_t)row_begin * (size_t)ldu * es, (size_t)ldu * es, (size_t)k * es, n,
-                         hipMemcpyHostToDevice));
-    if (n_items)
-        CSRK_HIP(hipMemcpy2D(dV.p, (size_t)k * es, V, (size_t)ldv * es, (size_t)k * es, (size_t)n_items, hipMemcpyHostToDevice));
     CSRK_TRY(ts_device(m, row_begin, row_end, dU.p, k, dV.p, k, n_items, k, panel_type, n_top, min_score, dI.as<int32_t>(), n_top,
                        dS.as<double>(), n_top, dC.as<int32_t>(), nullptr));
-    CSRK_HIP(hipMemcpy2D(items, (size_t)ldi * 4, dI.p, (size_t)n_top * 4, (size_t)n_top * 4, n, hipMemcpyDeviceToHost));
-    CSRK_HIP(hipMemcpy2D(scores, (size_t)lds * 8, dS.p, (size_t)n_top * 8, (size_t)n_top * 8, n, hipMemcpyDeviceToHost));
+    CSRK_TRY(unpack_panel(items, ldi, dI, n_top, 4, n));
+    CSRK_TRY(unpack_panel(scores, lds, dS, n_top, 8, n));
     if (counts) CSRK_HIP(hipMemcpy(counts, dC.p, n * 4, hipMemcpyDeviceToHost));
     return CSRK_OK;
 }

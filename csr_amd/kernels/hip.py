@@ -42,6 +42,7 @@ where a stale copy cannot go unseen:
     counts with its SpMV / SpMM plans) and whenever a library call runs out of device memory (retried once).
 """
 import ctypes as C
+import numbers
 import os
 import collections
 import threading
@@ -601,10 +602,26 @@ def filter_zeros(h):
 _TOPK_ORDERS = {'descending': _lib.TOPK_BY_VALUE, 'storage': _lib.TOPK_STORAGE}
 
 
+def _is_int(v):
+    "an integer (a bool is none)"
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _is_real(v):
+    "a real number (a bool is none)"
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def _limits(fn, n):
+    "the n compile-time constants a csrk_*_limits entry reports, as a tuple"
+    out = (C.c_int64 * n)()
+    check(fn(out, n))
+    return tuple(out)
+
+
 def topk_args(k, min_value, order):
     "(k, min_value, order code) as the library takes them; ValueError for anything it would refuse"
-    import numbers
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+    if not _is_int(k):
         raise ValueError(f'k must be an integer, not {k!r}')
     if k < 1:
         raise ValueError(f'k must be at least 1, not {k}')
@@ -631,9 +648,7 @@ def topk_rows(h, k, min_value=None, order='descending'):
 
 def topk_limits():
     "(longest row ranked by one wavefront, winners a large-class workgroup orders in LDS, its threads, longest medium row)"
-    out = (C.c_int64 * 4)()
-    check(lib.csrk_topk_limits(out, 4))
-    return tuple(out)
+    return _limits(lib.csrk_topk_limits, 4)
 
 
 _COMBINE_OPS = {'add': _lib.COMBINE_ADD, 'multiply': _lib.COMBINE_MUL, 'keep': _lib.COMBINE_KEEP, 'drop': _lib.COMBINE_DROP}
@@ -644,11 +659,10 @@ def combine_args(a, b, op, alpha=1.0, beta=1.0):
     (op code, alpha, beta) as the library takes them; ValueError for an unknown op, a non-real alpha or beta, or operands
     (handles or CSRs: anything with nrows and ncols) of different shapes
     """
-    import numbers
     if not isinstance(op, str) or op not in _COMBINE_OPS:
         raise ValueError(f"op must be 'add', 'multiply', 'keep' or 'drop', not {op!r}")
     for name, v in (('alpha', alpha), ('beta', beta)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+        if not _is_real(v):
             raise ValueError(f'{name} must be a real number, not {v!r}')
     if (a.nrows, a.ncols) != (b.nrows, b.ncols):
         raise ValueError(f'operands of different shapes: {a.nrows} x {a.ncols} and {b.nrows} x {b.ncols}')
@@ -676,9 +690,7 @@ def combine(a_h, b_h, op, alpha=1.0, beta=1.0):
 
 def combine_limits():
     "(entries a wavefront takes per step, entries a workgroup takes per step, largest len_a + len_b of the wavefront class)"
-    out = (C.c_int64 * 3)()
-    check(lib.csrk_combine_limits(out, 3))
-    return tuple(out)
+    return _limits(lib.csrk_combine_limits, 3)
 
 
 _DUPLICATES = {'sum': _lib.DUP_SUM, 'first': _lib.DUP_FIRST, 'last': _lib.DUP_LAST, 'max': _lib.DUP_MAX, 'min': _lib.DUP_MIN}
@@ -753,6 +765,40 @@ def mult_dense(h, B):
 _PANEL_CODES = {np.dtype('f4'): _lib.VAL_F32, np.dtype('f8'): _lib.VAL_F64}
 
 
+def _panel_pair(U, V, dtype_error=None):
+    """
+    what two panels must agree on: both 2-D, one dtype, one k >= 1.  dtype_error: the caller's words for a shared dtype that
+    is no panel dtype, raised where that caller has always raised them (once the dtypes are known to agree, before the
+    columns are compared); None leaves the dtype to _panel.
+    """
+    if U.ndim != 2 or V.ndim != 2:
+        raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
+    if U.dtype != V.dtype:
+        raise ValueError(f'U and V must have the same dtype, not {U.dtype} and {V.dtype}')
+    if dtype_error and U.dtype not in _PANEL_CODES:
+        raise ValueError(f'{dtype_error}, not {U.dtype}')
+    if U.shape[1] != V.shape[1]:
+        raise ValueError(f'U and V have {U.shape[1]} and {V.shape[1]} columns')
+    if U.shape[1] == 0:
+        raise ValueError('panels have no columns (k = 0)')
+
+
+def _row_range(rows, nrows):
+    "(begin, end) from rows = None (all of the nrows rows) or a pair of integers that is a range within them"
+    if rows is None:
+        return 0, int(nrows)
+    try:
+        rb, re_ = rows
+    except (TypeError, ValueError):
+        raise ValueError(f'rows must be (begin, end), not {rows!r}') from None
+    if not (_is_int(rb) and _is_int(re_)):
+        raise ValueError(f'rows must be two integers, not {rows!r}')
+    rb, re_ = int(rb), int(re_)
+    if not 0 <= rb <= re_ <= nrows:
+        raise ValueError(f'rows ({rb}, {re_}) is not a range within the {nrows} rows')
+    return rb, re_
+
+
 def _panel(P, rows, name):
     "a 2-D float32 / float64 panel of `rows` rows as (array, ld): a row-major view with unit column stride keeps its row stride"
     if P.ndim != 2:
@@ -776,14 +822,7 @@ def sddmm(h, U, V, scale=False):
     (include/csrk.h).  Not a reference entry point.
     """
     U, V = np.asarray(U), np.asarray(V)
-    if U.ndim != 2 or V.ndim != 2:
-        raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
-    if U.dtype != V.dtype:
-        raise ValueError(f'U and V must have the same dtype, not {U.dtype} and {V.dtype}')
-    if U.shape[1] != V.shape[1]:
-        raise ValueError(f'U and V have {U.shape[1]} and {V.shape[1]} columns')
-    if U.shape[1] == 0:
-        raise ValueError('panels have no columns (k = 0)')
+    _panel_pair(U, V)      # (their dtype is left to _panel: "U must be float32 or float64")
     U, ldu = _panel(U, h.nrows, 'U')
     V, ldv = _panel(V, h.ncols, 'V')
     k = U.shape[1]
@@ -794,9 +833,7 @@ def sddmm(h, U, V, scale=False):
 
 def gram_limits():
     "(largest k, entries staged per step, largest k of the 16-lane class, of the wavefront class, of the one-tile workgroup class)"
-    out = (C.c_int64 * 5)()
-    check(lib.csrk_gram_limits(out, 5))
-    return tuple(out)
+    return _limits(lib.csrk_gram_limits, 5)
 
 
 def gram_args(h, V, rows=None, base=None):
@@ -804,7 +841,6 @@ def gram_args(h, V, rows=None, base=None):
     (V, ldv, k, panel code, row_begin, row_end, base) as the library takes them; ValueError for anything it would refuse
     as invalid.  h is anything with nrows and ncols (a handle or a CSR); no library call is made.
     """
-    import numbers
     V = np.asarray(V)
     if V.ndim != 2:
         raise ValueError(f'V must be 2-D, not of shape {V.shape}')
@@ -814,19 +850,7 @@ def gram_args(h, V, rows=None, base=None):
         raise ValueError('V has no columns (k = 0)')
     V, ldv = _panel(V, h.ncols, 'V')
     k = V.shape[1]
-    if rows is None:
-        rb, re_ = 0, int(h.nrows)
-    else:
-        try:
-            rb, re_ = rows
-        except (TypeError, ValueError):
-            raise ValueError(f'rows must be (begin, end), not {rows!r}') from None
-        for v in (rb, re_):
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-                raise ValueError(f'rows must be two integers, not {rows!r}')
-        rb, re_ = int(rb), int(re_)
-        if not 0 <= rb <= re_ <= h.nrows:
-            raise ValueError(f'rows ({rb}, {re_}) is not a range within the {h.nrows} rows')
+    rb, re_ = _row_range(rows, h.nrows)
     if base is not None:
         base = np.asarray(base)
         if base.dtype != np.float64 or base.shape != (k, k):
@@ -851,9 +875,7 @@ def gram_rows(h, V, scale=False, rows=None, base=None):
 
 def als_limits():
     "(largest k, entries staged per step, largest k of the 16-lane class, of the wavefront class, of the one-tile workgroup class)"
-    out = (C.c_int64 * 5)()
-    check(lib.csrk_als_limits(out, 5))
-    return tuple(out)
+    return _limits(lib.csrk_als_limits, 5)
 
 
 _RHS_CODES = {'ones': _lib.ALS_RHS_ONES, 'values': _lib.ALS_RHS_VALUES, 'one_plus_values': _lib.ALS_RHS_ONE_PLUS}
@@ -887,11 +909,10 @@ def solve_blocks(G, b):
 
 def als_args(h, V, rhs='values', base=None, lam_n=0.0, rows=None):
     "gram_args' tuple + (rhs code, lam_n); ValueError for anything the library would refuse as invalid.  No library call."
-    import numbers
     args = gram_args(h, V, rows, base)
     if not isinstance(rhs, str) or rhs not in _RHS_CODES:
         raise ValueError(f'rhs must be one of {sorted(_RHS_CODES)}, not {rhs!r}')
-    if isinstance(lam_n, bool) or not isinstance(lam_n, numbers.Real):
+    if not _is_real(lam_n):
         raise ValueError(f'the per-entry ridge must be one real number, not {lam_n!r}')
     return args + (_RHS_CODES[rhs], float(lam_n))
 
@@ -915,9 +936,7 @@ def als_rows(h, V, scale=False, rhs='values', base=None, lam_n=0.0, rows=None):
 
 def topk_scores_limits():
     "(largest k, largest n, rows per workgroup, items per tile, factors per LDS chunk, list entries per row for n <= 32)"
-    out = (C.c_int64 * 6)()
-    check(lib.csrk_topk_scores_limits(out, 6))
-    return tuple(out)
+    return _limits(lib.csrk_topk_scores_limits, 6)
 
 
 def topk_scores_args(h, U, V, n, min_score=None, rows=None):
@@ -926,46 +945,24 @@ def topk_scores_args(h, U, V, n, min_score=None, rows=None):
     anything it would refuse as invalid.  h is anything with nrows and ncols (a handle or a CSR: the seen pairs) or None
     (nothing seen: U's rows and V's rows give the shape); no library call is made.
     """
-    import numbers
     U, V = np.asarray(U), np.asarray(V)
-    if U.ndim != 2 or V.ndim != 2:
-        raise ValueError(f'panels must be 2-D, not of shapes {U.shape} and {V.shape}')
-    if U.dtype != V.dtype:
-        raise ValueError(f'U and V must have the same dtype, not {U.dtype} and {V.dtype}')
-    if U.dtype not in _PANEL_CODES:
-        raise ValueError(f'U and V must be float32 or float64, not {U.dtype}')
-    if U.shape[1] != V.shape[1]:
-        raise ValueError(f'U and V have {U.shape[1]} and {V.shape[1]} columns')
-    if U.shape[1] == 0:
-        raise ValueError('panels have no columns (k = 0)')
+    _panel_pair(U, V, 'U and V must be float32 or float64')
     nrows = U.shape[0] if h is None else int(h.nrows)
     n_items = V.shape[0] if h is None else int(h.ncols)
     if nrows > np.iinfo('i4').max or n_items > np.iinfo('i4').max:
         raise ValueError(f'{nrows} rows or {n_items} items are more than 32-bit indices hold')
     U, ldu = _panel(U, nrows, 'U')
     V, ldv = _panel(V, n_items, 'V')
-    if isinstance(n, bool) or not isinstance(n, numbers.Integral):
+    if not _is_int(n):
         raise ValueError(f'n must be an integer, not {n!r}')
     if n < 1:
         raise ValueError(f'n must be at least 1, not {n}')
-    if isinstance(min_score, bool) or not (min_score is None or isinstance(min_score, numbers.Real)):
+    if not (min_score is None or _is_real(min_score)):
         raise ValueError(f'min_score must be one real number or None, not {min_score!r}')
     ms = -np.inf if min_score is None else float(min_score)
     if ms != ms:
         raise ValueError('min_score is NaN')
-    if rows is None:
-        rb, re_ = 0, nrows
-    else:
-        try:
-            rb, re_ = rows
-        except (TypeError, ValueError):
-            raise ValueError(f'rows must be (begin, end), not {rows!r}') from None
-        for v in (rb, re_):
-            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-                raise ValueError(f'rows must be two integers, not {rows!r}')
-        rb, re_ = int(rb), int(re_)
-        if not 0 <= rb <= re_ <= nrows:
-            raise ValueError(f'rows ({rb}, {re_}) is not a range within the {nrows} rows')
+    rb, re_ = _row_range(rows, nrows)
     return U, ldu, V, ldv, n_items, U.shape[1], _PANEL_CODES[U.dtype], min(int(n), np.iinfo('i4').max), ms, rb, re_
 
 
@@ -994,9 +991,7 @@ def topk_scores(h, U, V, n, min_score=None, rows=None):
 
 def rank_entries_limits():
     "(largest k, rows per workgroup, items per tile, factors per LDS chunk, test entries of a row per sweep)"
-    out = (C.c_int64 * 5)()
-    check(lib.csrk_rank_entries_limits(out, 5))
-    return tuple(out)
+    return _limits(lib.csrk_rank_entries_limits, 5)
 
 
 def rank_entries_args(seen_h, test_h, U, V, rows=None):
@@ -1086,9 +1081,7 @@ def spgemm_last_stats():
 
 def spgemm_limits():
     "the compile-time constants the general product routes its rows by, as a dict (include/csrk.h, csrk_spgemm_limits)"
-    out = (C.c_int64 * len(SPGEMM_LIMITS))()
-    check(lib.csrk_spgemm_limits(out, len(SPGEMM_LIMITS)))
-    return dict(zip(SPGEMM_LIMITS, (int(v) for v in out)))
+    return dict(zip(SPGEMM_LIMITS, _limits(lib.csrk_spgemm_limits, len(SPGEMM_LIMITS))))
 
 
 def set_spmv_algo(h, name):

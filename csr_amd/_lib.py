@@ -107,6 +107,12 @@ SIGNATURES = {
     'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,
                                        _i64, _vp, _vp]),
     'csrk_topk_scores_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_topk_scores_for': (_int, [handle_t, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,
+                                    _i64, _vp, _i32]),
+    'csrk_topk_scores_for_device': (_int, [handle_t, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64,
+                                           _vp, _i64, _vp, _i32, _vp, _i64, _vp]),
+    'csrk_topk_scores_for_workspace': (_int, [_i64, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
+    'csrk_topk_scores_for_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_rank_entries': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp]),
     'csrk_rank_entries_device': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp, _vp]),
     'csrk_rank_entries_limits': (_int, [C.POINTER(_i64), _int]),

@@ -460,6 +460,26 @@ class CSR:
         with releasing(K.to_handle(self), K) as h:
             return fn(h, U, V, n, min_score, rows)
 
+    def topk_scores_for(self, users, U, V, n, *, min_score=None, exclude=True, splits=None):
+        """
+        topk_scores for a list of rows -- serving: (items int32 [m, n], scores float64 [m, n], counts int32 [m]) with
+        m = len(users), row r of the result for row users[r].  users is a 1-D array of integer row indices in any order,
+        repeats allowed; an index outside [0, nrows) is a ValueError naming its position.  Scores, candidates, order and
+        padding are topk_scores', bit for bit: for users = arange(b, e) the result equals topk_scores(rows=(b, e)).  The
+        items are cut into `splits` ranges that run side by side so that a few rows still fill the card (None: chosen from
+        the number of rows; K.topk_scores_for_workspace tells); no bit depends on it (include/csrk.h,
+        csrk_topk_scores_for).  Only the listed rows of U are sent.  This matrix must be canonical; its values are not read.
+        Runs on the device only.  Not a reference entry point.
+        """
+        K, fn = self._ext('topk_scores_for')
+        K.topk_scores_for_args(self, users, U, V, n, min_score, splits)
+        if not exclude:      # (the panels have this matrix's shape: checked above)
+            return fn(None, users, U, V, n, min_score, splits)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            return fn(h, users, U, V, n, min_score, splits)
+
     def rank_entries(self, U, V, test, *, rows=None, exclude=True, return_scores=False):
         """
         Offline evaluation of a factor model, with this matrix as the pairs already seen and `test`, a CSR of the same

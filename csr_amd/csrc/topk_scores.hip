@@ -30,58 +30,10 @@
 
 #include "common.h"
 #include "panel.h"
+#include "score_list.h"
 #include "score_tile.h"
 
 namespace csrk {
-
-constexpr int TS_PASS = TS_TILE / TS_B;         // most survivors a row takes in one pass
-constexpr int TS_K_MAX = 1024;
-constexpr int TS_NTOP_SMALL = 32;
-constexpr int TS_NTOP_MAX = 128;
-
-template <int CLS> struct TsClass;
-template <> struct TsClass<0> { static constexpr int NTOP = TS_NTOP_SMALL, CAP = TS_NTOP_SMALL + TS_PASS; };
-template <> struct TsClass<1> { static constexpr int NTOP = TS_NTOP_MAX, CAP = TS_NTOP_MAX + TS_PASS; };
-
-// one wavefront orders the list of one row and cuts it to n_top (every lane of the wavefront calls it)
-template <int CAP>
-__device__ __forceinline__ void ts_compact(uint64_t *__restrict__ sc, int32_t *__restrict__ it, int32_t *__restrict__ cnt,
-                                           uint64_t *__restrict__ thr, int n_top, int lane)
-{
-    constexpr int EPL = (CAP + WAVE - 1) / WAVE;                  // entries per lane
-    const int n = *cnt;
-    uint64_t bits[EPL], key[EPL];
-    int32_t item[EPL];
-    int rank[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-        const int x = lane + e * WAVE;
-        bits[e] = x < n ? sc[x] : 0;
-        item[e] = x < n ? it[x] : 0;
-        key[e] = topk_key(__longlong_as_double((long long)bits[e]));
-        rank[e] = 0;
-    }
-    for (int j = 0; j < n; j++) {
-        const uint64_t kj = topk_key(__longlong_as_double((long long)sc[j]));
-        const int32_t ij = it[j];
-#pragma unroll
-        for (int e = 0; e < EPL; e++) rank[e] += (kj > key[e] || (kj == key[e] && ij < item[e])) ? 1 : 0;
-    }
-    // the wavefront has read the list before any lane rewrites it (LDS operations of one wavefront complete in issue order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#pragma unroll
-    for (int e = 0; e < EPL; e++) {
-        const int x = lane + e * WAVE;
-        if (x < n && rank[e] < n_top) {
-            sc[rank[e]] = bits[e];
-            it[rank[e]] = item[e];
-            if (rank[e] == n_top - 1) *thr = key[e];
-        }
-    }
-    if (lane == 0) *cnt = n < n_top ? n : n_top;
-}
 
 template <class T, bool WIDE, int CLS>
 __global__ __launch_bounds__(TS_THREADS) void topk_scores_kernel(const void *__restrict__ rp, int ptr64, const int32_t *__restrict__ ci,

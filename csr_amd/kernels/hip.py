@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
-is_canonical, topk_scores, rank_entries.
+is_canonical, topk_scores, topk_scores_for, rank_entries.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -986,6 +986,79 @@ def topk_scores(h, U, V, n, min_score=None, rows=None):
     items, scores, counts = np.empty((m, n), np.int32), np.empty((m, n), np.float64), np.zeros(m, np.int32)
     _call(lib.csrk_topk_scores, 0 if h is None else _live(h), rb, re_, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, ptr(items),
           n, ptr(scores), n, ptr(counts))
+    return items, scores, counts
+
+
+def topk_scores_for_limits():
+    "(most splits, workgroups that fill the card for n <= 32, above that, workspace bytes per (row, split) at n = 1, per further unit of n)"
+    return _limits(lib.csrk_topk_scores_for_limits, 5)
+
+
+def _splits(splits):
+    "the library's splits argument (0: automatic) from None or an integer >= 1"
+    if splits is None:
+        return 0
+    if not _is_int(splits) or splits < 1:
+        raise ValueError(f'splits must be None or an integer that is at least 1, not {splits!r}')
+    return min(int(splits), np.iinfo('i4').max)
+
+
+def topk_scores_for_workspace(n_rows, n_items, n, splits=None):
+    """
+    (splits_used, bytes): into how many ranges topk_scores_for cuts the items for n_rows listed rows, n_items items and
+    lists of n (splits=None: as many as fill the card), and the bytes of the workspace the device form needs for it (0 for
+    one range).  From the library's constants alone: no device is touched.
+    """
+    for name, v in (('n_rows', n_rows), ('n_items', n_items), ('n', n)):
+        if not _is_int(v):
+            raise ValueError(f'{name} must be an integer, not {v!r}')
+    if n_items > np.iinfo('i4').max:
+        raise ValueError(f'{n_items} items are more than 32-bit indices hold')
+    used, nbytes = C.c_int32(0), C.c_int64(0)
+    check(lib.csrk_topk_scores_for_workspace(int(n_rows), int(n_items), min(int(n), np.iinfo('i4').max), _splits(splits), C.byref(used),
+                                             C.byref(nbytes)))
+    return used.value, nbytes.value
+
+
+def topk_scores_for_args(h, users, U, V, n, min_score=None, splits=None):
+    """
+    (users int32, U, ldu, V, ldv, n_items, k, panel code, n, min_score, splits, u_rows) as the library takes them; ValueError
+    for anything it would refuse as invalid.  h is as in topk_scores_args; users is a 1-D array of integer row indices in any
+    order, repeats allowed; no library call is made.
+    """
+    U, ldu, V, ldv, n_items, k, code, n, ms, _, nrows = topk_scores_args(h, U, V, n, min_score, None)
+    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
+    if users.ndim != 1:
+        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
+    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
+        raise ValueError(f'users must hold integers, not {users.dtype}')
+    bad = np.flatnonzero((users < 0) | (users >= nrows))
+    if len(bad):
+        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
+    return np.ascontiguousarray(users, dtype=np.int32), U, ldu, V, ldv, n_items, k, code, n, ms, _splits(splits), nrows
+
+
+def topk_scores_for(h, users, U, V, n, min_score=None, splits=None):
+    """
+    topk_scores for a list of rows: (items int32 [m, n], scores float64 [m, n], counts int32 [m]) with m = len(users), row r
+    of the result for row users[r] of U and of the handle's matrix.  users may be in any order and repeat a row.  The items
+    are cut into `splits` ranges that run side by side (None: as many as fill the card), which changes no bit: for
+    users = arange(b, e) the result is topk_scores' for rows = (b, e) (include/csrk.h, csrk_topk_scores_for).  Only the listed
+    rows of U are sent.  Not a reference entry point.
+    """
+    users, U, ldu, V, ldv, n_items, k, code, n, ms, sp, nrows = topk_scores_for_args(h, users, U, V, n, min_score, splits)
+    m = len(users)
+    H = 0 if h is None else _live(h)
+    lim = topk_scores_limits()
+    if k > lim[0] or n > lim[1]:      # the library's refusal, before any result array is made
+        one = np.zeros(1, np.int32)
+        check(lib.csrk_topk_scores_for(H, ptr(one), 1, nrows, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, None, n, None, n, None, sp))
+        raise ValueError(f'k = {k} or n = {n} is above the limits {lim[:2]}')
+    items, scores, counts = np.empty((m, n), np.int32), np.empty((m, n), np.float64), np.zeros(m, np.int32)
+    if m == 0:
+        return items, scores, counts
+    _call(lib.csrk_topk_scores_for, H, ptr(users), m, nrows, ptr(U), ldu, ptr(V), ldv, n_items, k, code, n, ms, ptr(items), n, ptr(scores),
+          n, ptr(counts), sp)
     return items, scores, counts
 
 

@@ -609,8 +609,8 @@ CSRK_API int csrk_is_canonical(csrk_handle_t h, int *canonical, int32_t *first_b
  *   8. Device form.  Allocates nothing and does not synchronise the host, with one exception: the first call that asks a
  *      handle whether it is canonical looks at its rows (rule 1; csrk_is_canonical beforehand takes that look).  One
  *      workgroup takes a block of rows across all items and keeps the rows' running lists on the chip: no scratch memory.
- *      The items of a small row range are not split across workgroups.  The host form sends the panels packed (the rows of
- *      the range only) and is synchronous.
+ *      The items of a small row range are not split across workgroups (csrk_topk_scores_for splits them).  The host form
+ *      sends the panels packed (the rows of the range only) and is synchronous.
  *   9. Refusals; a refused call writes nothing.  CSRK_ERR_INVALID: k < 1, n_top < 1, n_items < 0; ldu < k, ldv < k,
  *      ldi < n_top, lds < n_top; an unknown panel_type; a NaN min_score; row_begin < 0 or row_begin > row_end; with a handle,
  *      row_end > nrows or n_items != ncols; a `seen` that is not canonical or not a handle; NULL items or scores when there
@@ -632,6 +632,68 @@ CSRK_API int csrk_topk_scores_device(csrk_handle_t seen, int32_t row_begin, int3
                                      int64_t lds, int32_t *d_counts, void *stream);
 /* Diagnostics: the six limits of rule 10, in its order;  n <= 6.  No device is touched. */
 CSRK_API int csrk_topk_scores_limits(int64_t *out, int n);
+
+/* ---- topk_scores_for: csrk_topk_scores for a list of rows, the items split across workgroups ------
+ * Not a reference entry point: serving.  A request is a list of user ids, and a handful of rows does not fill the card when
+ * one workgroup takes 64 rows across all items: here the rows are named one by one and the items are cut into S ranges that
+ * run side by side, with the partial lists in a workspace the caller supplies.  Everything not said here is
+ * csrk_topk_scores' rule of the same number.
+ *   1. Rows.  rows[r] (int32, n_rows of them) is an ABSOLUTE row index and output row r belongs to it: U[rows[r]] is the
+ *      factor row, row rows[r] of `seen` the exclusion list.  The list may be in any order and may repeat a row; each
+ *      occurrence is computed on its own and gets the same bits.  u_rows is the number of rows U holds; with a handle it
+ *      must equal the handle's nrows.  In the device form an index outside [0, u_rows) is not dereferenced: that output row
+ *      gets count -1 and padding only, and no other row is affected (csrk_rank_entries' rule for a bad column).  The host
+ *      form looks at the list first and refuses with CSRK_ERR_INVALID, naming the first bad position and its value; it
+ *      sends only the listed rows of U.
+ *   2. Score, candidates, selection, output and special values are rules 2-5 and 7 of csrk_topk_scores, word for word
+ *      (output row r where it says i - row_begin).  For rows = b, b + 1, ..., e - 1 every output bit equals that of
+ *      csrk_topk_scores(row_begin = b, row_end = e).
+ *   3. Splits.  With tile = out[3] of csrk_topk_scores_limits and T = ceil(n_items / tile), the items are cut at tile
+ *      boundaries into S contiguous ranges: range s holds the tiles [s T / S, (s + 1) T / S) (integer division).  One
+ *      workgroup takes one (row block, range) pair, keeps its rows' running lists on the chip exactly as csrk_topk_scores
+ *      does, and writes each row's final partial list (the count, then score bits and items, best first) to the workspace.
+ *      A second launch merges the S partial lists of each row: a candidate's place is its place in its own list plus the
+ *      number of entries of every other list that come before it in rule 4's order.  Places are counted, never handed out
+ *      in arrival order; places below n_top are written, the rest is padding.  No float atomics, no device-scope atomics,
+ *      and no workgroup waits for another: two launches, not a last-block-finishes scheme; neither launch can spin.  S = 1
+ *      writes the outputs directly, needs no workspace and launches once.
+ *   4. Choice of S.  splits >= 1 forces S = min(splits, T, S_max), and S = 1 when T = 0 or n_rows = 0.  splits = 0 is automatic:
+ *      S = clamp(ceil(W / ceil(n_rows / 64)), 1, min(T, S_max)), with W the workgroups that fill the card: 512 for
+ *      n_top <= 32 (two workgroups per CU for that list class, 256 CUs), 256 above that (one per CU).  S_max = 64, which
+ *      bounds the merge at 64 * 128 candidates per row.  csrk_topk_scores_for_workspace returns S and the bytes for it from
+ *      these constants alone, so a caller can size a buffer once without a device:
+ *      bytes = 0 for S = 1, else n_rows * S * (out[3] + (n_top - 1) * out[4]) of csrk_topk_scores_for_limits, rounded up to
+ *      a multiple of 16.
+ *   5. Workspace.  16-B aligned, work_bytes >= the reported size; nothing at or beyond the reported size is touched; d_work
+ *      may be NULL when the size is 0.  Its contents before and after a call mean nothing.
+ *   6. Invariance.  No output bit depends on splits, the workspace address, the order or repetition of rows, or anything in
+ *      csrk_topk_scores' rule 6.
+ *   7. Device form.  Allocates nothing and does not synchronise the host, apart from the remembered canonical look of
+ *      csrk_topk_scores' rule 8; both launches go to `stream`.  The host form allocates its own workspace and is
+ *      synchronous.
+ *   8. Refusals; a refused call writes nothing.  Every refusal of csrk_topk_scores that applies, in the same order, with
+ *      texts that begin "topk_scores_for: ".  CSRK_ERR_INVALID further: n_rows < 0; u_rows < 0; splits < 0; with a handle,
+ *      u_rows != nrows or n_items != ncols; NULL rows when n_rows > 0; a workspace that is NULL, misaligned or too small when
+ *      one is needed.  CSRK_ERR_UNSUPPORTED: k or n_top above csrk_topk_scores_limits, and more row blocks (of 64 rows) than
+ *      a grid holds (2^31 - 1).  n_rows = 0: CSRK_OK, nothing launched.
+ *   9. Limits (csrk_topk_scores_for_limits): out[0] = S_max; [1] = W for n_top <= 32; [2] = W above that; [3] = the
+ *      workspace bytes per (row, split) at n_top = 1; [4] = the further bytes per unit of n_top;  n <= 5. */
+CSRK_API int csrk_topk_scores_for(csrk_handle_t seen, const int32_t *rows, int64_t n_rows, int32_t u_rows, const void *U,
+                                  int64_t ldu, const void *V, int64_t ldv, int32_t n_items, int32_t k, int panel_type,
+                                  int32_t n_top, double min_score, int32_t *items, int64_t ldi, double *scores, int64_t lds,
+                                  int32_t *counts, int32_t splits);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream). */
+CSRK_API int csrk_topk_scores_for_device(csrk_handle_t seen, const int32_t *d_rows, int64_t n_rows, int32_t u_rows,
+                                         const void *d_U, int64_t ldu, const void *d_V, int64_t ldv, int32_t n_items,
+                                         int32_t k, int panel_type, int32_t n_top, double min_score, int32_t *d_items,
+                                         int64_t ldi, double *d_scores, int64_t lds, int32_t *d_counts, int32_t splits,
+                                         void *d_work, int64_t work_bytes, void *stream);
+/* Rule 4: *splits_used = S and *bytes = the workspace for it.  CSRK_ERR_INVALID: n_rows < 0, n_items < 0, n_top < 1,
+ * splits < 0, a NULL result pointer; CSRK_ERR_UNSUPPORTED as in rule 8.  No device is touched. */
+CSRK_API int csrk_topk_scores_for_workspace(int64_t n_rows, int32_t n_items, int32_t n_top, int32_t splits,
+                                            int32_t *splits_used, int64_t *bytes);
+/* Diagnostics: the five limits of rule 9, in its order;  n <= 5.  No device is touched. */
+CSRK_API int csrk_topk_scores_for_limits(int64_t *out, int n);
 
 /* ---- rank_entries: where each held-out entry lands among its row's unseen items --------------------
  * Not a reference entry point: offline evaluation after csrk_topk_scores.  For every entry (i, j) of `test`, the number of

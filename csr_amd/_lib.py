@@ -18,6 +18,7 @@ TOPK_BY_VALUE, TOPK_STORAGE = 0, 1
 COMBINE_ADD, COMBINE_MUL, COMBINE_KEEP, COMBINE_DROP = 0, 1, 2, 3
 DUP_SUM, DUP_FIRST, DUP_LAST, DUP_MAX, DUP_MIN = 0, 1, 2, 3, 4
 ALS_RHS_ONES, ALS_RHS_VALUES, ALS_RHS_ONE_PLUS = 0, 1, 2
+KNN_WEIGHTED_AVERAGE, KNN_SUM = 0, 1
 
 
 class CsrkError(RuntimeError):
@@ -116,6 +117,8 @@ SIGNATURES = {
     'csrk_rank_entries': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp]),
     'csrk_rank_entries_device': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp, _vp]),
     'csrk_rank_entries_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_knn_scores': (_int, [handle_t, handle_t, _vp, _i64, _i32, _i32, _int, _vp, C.POINTER(handle_t)]),
+    'csrk_knn_scores_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

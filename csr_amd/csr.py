@@ -512,6 +512,71 @@ class CSR:
         return (ranks, scores) if return_scores else ranks
 
     # ---- two matrices entry by entry -----------------------------------------------------------
+    def _knn_check(self, K, model, users, max_nbrs, min_nbrs, aggregate, offsets):
+        "knn_scores' arguments as the kernel takes them, checked before any device work; users=None: all rows"
+        if not all(hasattr(model, a) for a in ('nrows', 'ncols', 'nnz')) or isinstance(model, np.ndarray):
+            raise ValueError(f'model must be a CSR, not {type(model).__name__}')
+        users = np.arange(self.nrows, dtype=np.int32) if users is None else users
+        args = K.knn_scores_args(model, self, users, 0 if max_nbrs is None else max_nbrs, min_nbrs, aggregate, offsets)
+        for m in (self, model):
+            if m.nnz > K.max_nnz:
+                raise ValueError('CSR size {} exceeds max nnz {}'.format(m.nnz, K.max_nnz))
+        return args[0]
+
+    def knn_scores(self, model, users=None, *, max_nbrs=None, min_nbrs=1, aggregate='weighted-average', offsets=None):
+        """
+        Scores from an item-kNN model, with this matrix as the ratings [users x items]: a CSR [len(users) x model.nrows],
+        float64, canonical, row r for user users[r] (users=None: all rows; any order, repeats allowed).  `model` is a CSR
+        [targets x items] whose rows hold each target's neighbours, best first -- what multiply_topk(..., transpose=True,
+        order='descending') returns.  For each target the neighbour list is walked in storage order; the neighbours the user
+        has rated are hits, the walk ends after max_nbrs hits (None: no limit), and a target with at least min_nbrs hits is
+        stored: sum(rating * similarity) / sum(|similarity|) over the hits (aggregate='weighted-average') or
+        sum(similarity) ('sum'), plus offsets[r] when offsets is given (a user's mean after center_rows).  Every operation is
+        rounded on its own in storage order, so the result is a function of the arguments, bit for bit (include/csrk.h,
+        csrk_knn_scores).  This matrix must be canonical (sort_rows / coalesce); the model need not be.  Runs on the device
+        only.  Not a reference entry point.
+        """
+        K, fn = self._ext('knn_scores')
+        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets)
+        mx = 0 if max_nbrs is None else max_nbrs
+        with releasing(K.to_handle(model), K) as m_h:
+            with releasing(K.to_handle(self), K) as r_h:
+                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets), K) as s_h:
+                    return K.from_handle(s_h)
+
+    def knn_topk(self, model, users, n, *, exclude=True, min_value=None, **scoring):
+        """
+        Recommendations from an item-kNN model: knn_scores(model, users, **scoring) -> without the items the user has rated
+        (exclude=True) -> each row's n best scores that are not below min_value, best first (topk_rows' order), as a CSR
+        [len(users) x model.nrows].  The handle chain knn_scores -> combine 'drop' against pick_rows(ratings, users) ->
+        topk_rows stays on the device: only n entries per user cross PCIe.  exclude=True needs a model over the same items
+        as its neighbours (model.nrows == ncols).
+        """
+        K, fn = self._ext('knn_scores')
+        _, top = self._ext('topk_rows')
+        _, comb = self._ext('combine')
+        _, pick = self._ext('pick_rows')
+        bad = set(scoring) - {'max_nbrs', 'min_nbrs', 'aggregate', 'offsets'}
+        if bad:
+            raise TypeError(f'knn_topk got unexpected scoring arguments {sorted(bad)}')
+        max_nbrs, min_nbrs = scoring.get('max_nbrs'), scoring.get('min_nbrs', 1)
+        aggregate, offsets = scoring.get('aggregate', 'weighted-average'), scoring.get('offsets')
+        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets)
+        _topk_check(K, n, min_value, 'descending')
+        if exclude and model.nrows != self.ncols:
+            raise ValueError(f'exclude=True needs a model over the rated items: model has {model.nrows} rows, ratings {self.ncols} columns')
+        mx = 0 if max_nbrs is None else max_nbrs
+        with releasing(K.to_handle(model), K) as m_h:
+            with releasing(K.to_handle(self), K) as r_h:
+                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets), K) as s_h:
+                    if not exclude:
+                        with releasing(top(s_h, n, min_value, 'descending'), K) as t_h:
+                            return K.from_handle(t_h)
+                    with releasing(pick(r_h, users, False), K) as x_h:
+                        with releasing(comb(s_h, x_h, 'drop'), K) as d_h:
+                            with releasing(top(d_h, n, min_value, 'descending'), K) as t_h:
+                                return K.from_handle(t_h)
+
     def _combine(self, other, op, alpha=1.0, beta=1.0):
         """
         to_handle x 2 -> combine -> from_handle.  Above K.max_nnz both operands are cut at the same row boundaries (the

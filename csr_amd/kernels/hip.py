@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
-is_canonical, topk_scores, topk_scores_for, rank_entries.
+is_canonical, topk_scores, topk_scores_for, rank_entries, knn_scores.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -1105,6 +1105,68 @@ def rank_entries(seen_h, test_h, U, V, rows=None):
     ranks, scores = _out(m, np.int32), _out(m, np.float64)
     _call(lib.csrk_rank_entries, sh, _live(test_h), rb, re_, ptr(U), ldu, ptr(V), ldv, k, code, ptr(ranks), ptr(scores))
     return ranks, scores
+
+
+_KNN_AGGREGATES = {'weighted-average': _lib.KNN_WEIGHTED_AVERAGE, 'sum': _lib.KNN_SUM}
+
+
+def knn_scores_limits():
+    """
+    (lanes that share one target's walk, targets of a workgroup tile, entries of a rating row held in LDS, bits of the column
+    filter, most tiles per workgroup, workgroups below which a workgroup takes one tile)
+    """
+    return _limits(lib.csrk_knn_scores_limits, 6)
+
+
+def knn_scores_args(model, ratings, users, max_nbrs=0, min_nbrs=1, aggregate='weighted-average', offsets=None):
+    """
+    (users int32, max_nbrs, min_nbrs, aggregate code, offsets float64 or None) as the library takes them; ValueError for
+    anything it would refuse as invalid.  model and ratings are anything with nrows and ncols (handles or CSRs); users is a
+    1-D array of integer row indices of ratings in any order, repeats allowed; max_nbrs = 0 is no limit; offsets is None or
+    one real number per user.  No library call is made.
+    """
+    if not isinstance(aggregate, str) or aggregate not in _KNN_AGGREGATES:
+        raise ValueError(f"aggregate must be 'weighted-average' or 'sum', not {aggregate!r}")
+    if not _is_int(max_nbrs) or max_nbrs < 0:
+        raise ValueError(f'max_nbrs must be an integer that is not negative, not {max_nbrs!r}')
+    if not _is_int(min_nbrs) or min_nbrs < 1:
+        raise ValueError(f'min_nbrs must be an integer that is at least 1, not {min_nbrs!r}')
+    if int(model.ncols) != int(ratings.ncols):
+        raise ValueError(f'model is {model.nrows} x {model.ncols} but ratings is {ratings.nrows} x {ratings.ncols}: the columns differ')
+    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
+    if users.ndim != 1:
+        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
+    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
+        raise ValueError(f'users must hold integers, not {users.dtype}')
+    nrows = int(ratings.nrows)
+    bad = np.flatnonzero((users < 0) | (users >= nrows))
+    if len(bad):
+        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
+    if offsets is not None:
+        offsets = np.asarray(offsets)
+        if offsets.dtype == np.bool_ or not (np.issubdtype(offsets.dtype, np.floating) or np.issubdtype(offsets.dtype, np.integer)):
+            raise ValueError(f'offsets must hold real numbers, not {offsets.dtype}')
+        if offsets.shape != (len(users),):
+            raise ValueError(f'offsets must hold one number per user ({len(users)}), not shape {offsets.shape}')
+        offsets = np.ascontiguousarray(offsets, dtype=np.float64)
+    i4 = np.iinfo('i4').max
+    return np.ascontiguousarray(users, dtype=np.int32), min(int(max_nbrs), i4), min(int(min_nbrs), i4), _KNN_AGGREGATES[aggregate], offsets
+
+
+def knn_scores(model_h, ratings_h, users, max_nbrs=0, min_nbrs=1, aggregate='weighted-average', offsets=None):
+    """
+    Scores from an item-kNN model on the device: NEW handle [len(users) x model.nrows], float64, canonical.  For user
+    users[r] and each target i, the entries (j, s) of model row i are walked in storage order; those whose item j the user
+    has rated (value v in ratings_h) are hits, the walk ends after max_nbrs hits (0: no limit), and target i is stored when
+    it had at least min_nbrs hits: sum(v s) / sum(|s|) over the hits ('weighted-average') or sum(s) ('sum'), plus offsets[r]
+    when offsets is given.  Every operation is rounded on its own, in storage order: the result is a function of its
+    arguments, bit for bit (include/csrk.h, csrk_knn_scores).  ratings_h's matrix must be canonical, model_h's need not be.
+    Not a reference entry point.
+    """
+    users, mx, mn, code, offsets = knn_scores_args(model_h, ratings_h, users, max_nbrs, min_nbrs, aggregate, offsets)
+    out = handle_t(0)
+    _call(lib.csrk_knn_scores, _live(model_h), _live(ratings_h), ptr(users), users.size, mx, mn, code, ptr(offsets), C.byref(out))
+    return _wrap(out.value)
 
 
 def set_spgemm_order(order):

@@ -754,6 +754,58 @@ CSRK_API int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, in
 /* Diagnostics: the five limits of rule 10, in its order;  n <= 5.  No device is touched. */
 CSRK_API int csrk_rank_entries_limits(int64_t *out, int n);
 
+/* ---- knn_scores: score items from an item-kNN model's nearest rated neighbours -------------------------
+ * Not a reference entry point: the scoring side of the neighbourhood model that csrk_spgemm_abt + csrk_topk_rows build (each
+ * row of `model` holds an item's most similar items, best first).  The rule is the one of an item-item recommender: for each
+ * target item walk its neighbour list, take the first max_nbrs neighbours the user has rated and average the user's ratings
+ * weighted by similarity.  The cut at max_nbrs depends on the user, so no pruning of the model and no product reproduces it.
+ * Returns a NEW handle [n_rows x n_targets], row r for user rows[r]; `rows` and `offsets` are host arrays (as csrk_pick_rows'
+ * `rows`).
+ *   1. Operands.  model is [n_targets x n_items], ratings [n_users x n_items]: model.ncols == ratings.ncols.  ratings must
+ *      be CANONICAL (csrk_combine's word; the check is csrk_is_canonical's remembered one and the refusal names the first bad
+ *      row).  model need not be: its rows are in by-value order after csrk_topk_rows, and unsorted or repeated columns are
+ *      just more entries.  Either pointer width and any value type on either operand; float32 values are widened exactly, a
+ *      structure-only operand counts as 1.0 everywhere (csrk_sddmm's rule).  Neither handle is modified, both keep their
+ *      plans; model == ratings is allowed.  Model column indices are compared, never used as addresses.
+ *   2. The walk.  For output row r (user u = rows[r]) and target i the entries of model row i are taken in STORAGE order.
+ *      An entry (j, s) is a HIT when ratings stores (u, j), with value v.  Each hit takes one step, in this order:
+ *          t = round(v * s);  num = round(num + t);  den = round(den + |s|);  nn += 1
+ *      num and den start at +0.0; every operation is rounded on its own (no fused multiply-add).  With aggregate =
+ *      CSRK_KNN_SUM the step is num = round(num + s): v is not read and den is not formed.  With max_nbrs > 0 the walk ends
+ *      after the hit that makes nn == max_nbrs; max_nbrs = 0 is no limit.
+ *   3. What is stored.  Target i is stored in row r iff nn >= min_nbrs (min_nbrs >= 1).  Its value is round(num / den), one
+ *      correctly rounded division, for CSRK_KNN_WEIGHTED_AVERAGE (den = 0 gives NaN or Inf as IEEE says, and the value stays
+ *      stored) and num for CSRK_KNN_SUM; with offsets != NULL the value is then round(value + offsets[r]) (a user's mean put
+ *      back after csrk_center_rows).
+ *   4. Result.  [n_rows x n_targets], float64 values, every row strictly ascending in target index.  It is known to be
+ *      canonical (as csrk_coalesce's result): a following csrk_combine or csrk_is_canonical does not look at its rows again.
+ *      Row pointers are int32 unless the result holds more than 2^31 - 1 entries (csrk_pick_rows' rule).
+ *   5. Invariance.  An output entry depends only on model row i, ratings row u, max_nbrs, min_nbrs, aggregate and offsets[r]:
+ *      not on the list's order, length or repeats (a repeated row is computed on its own and gets the same bits), the pointer
+ *      widths, launch geometry, the limits below or repeated calls (csrc/knn_scores.hip: parallel over (row, target) pairs,
+ *      never inside a walk; every slot is counted, nothing appended in arrival order; no float atomics).
+ *   6. Special values.  IEEE throughout.  No path skips an explicit zero similarity or rating: a hit with s = 0.0 counts
+ *      toward nn and max_nbrs.  A created NaN has its position specified, not its sign or payload (csrk_combine's rule 7).
+ *   7. Refusals; *out = 0 on every failure.  CSRK_ERR_INVALID: a NULL out, a bad handle, model.ncols != ratings.ncols,
+ *      operands on different devices, n_rows < 0, NULL rows with n_rows > 0, max_nbrs < 0, min_nbrs < 1, an unknown aggregate,
+ *      a non-canonical ratings, or an index of rows outside [0, n_users): the list is looked at on the host before anything
+ *      is sent and the message names the first bad position and its value.  CSRK_ERR_UNSUPPORTED: a ratings or model row of
+ *      more than 2^31 - 1 entries (a canonical row holds at most ncols <= 2^31 - 1 entries, so in effect a model row).
+ *      n_rows = 0, n_targets = 0, model.nnz = 0 or ratings.nnz = 0: CSRK_OK, an empty result, nothing launched -- not
+ *      even the look at the rows of ratings, so with one of these a ratings that is not canonical is not refused (the
+ *      arguments that need no look at the device are still checked first).
+ *   8. Limits (csrk_knn_scores_limits): out[0] = the lanes that share one target's walk; [1] = the targets of a workgroup
+ *      tile; [2] = the entries of a rating row held in LDS (a longer row is searched in device memory and gives the same
+ *      bits); [3] = the bits of the filter in front of the search (a model column is searched for only when the bit of its
+ *      residue modulo [3] is set by some rated column; columns that share a residue cost a search, nothing else); [4] = the
+ *      most consecutive tiles one workgroup takes for a row, staging the rating row once; [5] = the workgroups a call is
+ *      cut into at least before a workgroup takes more than one tile (tiles per workgroup = n_rows x tiles / [5], within
+ *      1 .. [4]);  n <= 6.  No device is touched; by rule 5 none of them changes a bit. */
+enum { CSRK_KNN_WEIGHTED_AVERAGE = 0, CSRK_KNN_SUM = 1 };
+CSRK_API int csrk_knn_scores(csrk_handle_t model, csrk_handle_t ratings, const int32_t *rows, int64_t n_rows, int32_t max_nbrs,
+                             int32_t min_nbrs, int aggregate, const double *offsets, csrk_handle_t *out);
+CSRK_API int csrk_knn_scores_limits(int64_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,7 @@ SIGNATURES = {
     'csrk_spmv_algo_name': (C.c_char_p, [handle_t]),
     'csrk_spmv_plan_info': (_int, [handle_t, C.POINTER(_i64), C.POINTER(_i32)]),
     'csrk_spmv_plan_stats': (_int, [handle_t, C.POINTER(_i64), _int]),
+    'csrk_spmv_stream_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_spmv_profile_begin': (_int, [handle_t, _int]),
     'csrk_spmv_profile_every': (_int, [handle_t, _int]),
     'csrk_spmv_profile_channels': (_int, [handle_t, _int]),

@@ -1014,9 +1014,14 @@ __global__ __launch_bounds__(LS_THREADS) void spmv_lstream_kernel(
         // runs that cross lanes, tree order (any length)
         const double T = wave_segscan(ts, has_start, lane);
         const double X = wave_up1_f64(T, 0.0);               // what the lanes below carry into this lane's head
-        // ... and in the reference's own order for runs over at most LS_SEQ + 1 lanes: round k hands the
-        // exact running sum of the lane below to a lane that has not got its carry yet, which then re-adds
-        // its head entries one by one on top of it
+        // ... and in the reference's own order for a run whose sum is STORED at most LS_SEQ lanes after the lane it starts in:
+        // round k hands the exact running sum of the lane below to a lane that has not got its carry yet, which then re-adds
+        // its head entries one by one on top of it.  The lane that stores a run is the lane of the next row start (lane 63 for
+        // the tile's last run), not the lane of the run's last entry: a run over LS_SEQ + 1 lanes that ends with its last lane
+        // is stored by the lane after and gets the tree's sum, as does the matrix's last row, which the padding slots of a
+        // last tile that is not full continue up to lane 63.  So: rows of up to 8 LS_SEQ = 24 entries wherever they lie inside
+        // a tile, rows of 25 unless they start in a lane's last slot and end before the tile does; not the last row of the
+        // stream unless it starts in lanes 60 .. 63 or ends its tile (tests/lstream_cases.py, Layout.exact_rows).
         const int first = has_start ? __ffs(st) - 1 : ACC_K;    // entries before the lane's first row start
         double Tq = ts, Hq = hs;
         bool okq = has_start || lane == 0, hok = lane == 0;
@@ -1917,6 +1922,30 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
                            p->ls.round_start.p ? p->ls.stage_tiles : 0,
                            af ? (int64_t)p->acc[0]->n_wg : 0, 0, part[0], part[1], part[2], part[3], part[4]};
     for (int i = 0; i < n && i < 34; i++) out[i] = v[i];
+    // the light stream's form (launch_spmv picks the kernel by these): [34] dense layout, [35] 3-byte index words, [36] pack
+    // slots read from LDS (n_lds as launched), [37] rounds in all and [38] the most one workgroup walks -- staged rounds, or the
+    // plain kernel's one tile per wavefront --, [39] column blocks of the copy pass, [40] their width, [41] float32 values
+    const LightStream &ls = p->ls;
+    const bool rnd = ls.on && ls.n_cold && ls.round_start.p;
+    const int64_t plain_rounds = ls.on ? ceil_div(ls.n_tiles, LS_THREADS / WAVE) : 0;
+    const int64_t w[8] = {ls.on && ls.dense ? 1 : 0,
+                          ls.on && ls.idx24 ? 1 : 0,
+                          ls.on ? p->n_hot_lds : 0,
+                          rnd ? ls.n_rounds : plain_rounds,
+                          rnd ? ls.max_wg_rounds : (ls.on ? ceil_div(plain_rounds, (int64_t)ls.grid) : 0),
+                          rnd ? ls.n_stage_blk : 0,
+                          rnd ? ls.stage_w : 0,
+                          ls.on && ls.f32 ? 1 : 0};
+    for (int i = 34; i < n && i < 42; i++) out[i] = w[i - 34];
+    return CSRK_OK;
+}
+
+int csrk_spmv_stream_limits(int64_t *out, int n)
+{
+    CSRK_REQUIRE(out && n >= 0, "out is NULL");
+    const int64_t v[13] = {ACC_TILE, ACC_K, LS_THREADS / WAVE, LS_SEQ, LS_RID, LS_HOT_LDS, LS_RND_HOT, LS_RND_CAP, LS_RND_MAXTILES,
+                           LS_STAGE_WMAX, LS_STAGE_THREADS * LS_STAGE_IPT, TIERB_MIN_DEFAULT, HOT_SLOTS_MAX};
+    for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
     return CSRK_OK;
 }
 

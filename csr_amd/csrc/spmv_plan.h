@@ -109,6 +109,7 @@ struct LightStream {
     // tiles round_tile0[r] .. round_tile0[r + 1] (at most `stage_tiles`), whose staged values xg[round_start[r] ..
     // round_start[r + 1]) the workgroup copies into LDS; a cold entry's index word holds its offset inside that range
     int32_t stage_tiles = 0;
+    int32_t n_rounds = 0, max_wg_rounds = 0;      // rounds in all, and the most one workgroup walks (csrk_spmv_plan_stats)
     DevBuf round_start, round_tile0, wg_round0;
 };
 
@@ -421,7 +422,7 @@ constexpr int LS_RID = 4;        // batches of 64 run-slot row ids fetched ahead
 #ifndef CSRK_LS_SEQ
 #define CSRK_LS_SEQ 3
 #endif
-constexpr int LS_SEQ = CSRK_LS_SEQ;        // rounds of in-order carry hand-over (runs over <= LS_SEQ + 1 lanes are exact)
+constexpr int LS_SEQ = CSRK_LS_SEQ;        // rounds of in-order carry hand-over (a run stored <= LS_SEQ lanes after the one it starts in is exact)
 constexpr uint32_t LS_HOT_BIT = 1u << 31, LS_START_BIT = 1u << 30, LS_COL_MASK = (1u << 30) - 1;
 constexpr uint32_t LS_PAD = LS_COL_MASK;      // a padding slot: value 0.0, "column" 2^30 - 1 (never a real one), no flags
 // the same word in 3 bytes (LightStream::idx24, cold staging on: every column field is a pack slot or a round offset):
@@ -434,6 +435,10 @@ constexpr int LS24_START_SHIFT = 22;
 constexpr int64_t LS24_TILE_BYTES = 512 * 3;
 
 constexpr int VEC_SEG = 4096;
+// plan-time defaults that csrk_spmv_stream_limits reports beside the stream's constants: the shortest row the long-row split
+// cuts out (tier 1's threshold, CSRK_TIERB_MIN) and the pack's slots at most (build_hot_cache)
+constexpr int TIERB_MIN_DEFAULT = 128;
+constexpr int64_t HOT_SLOTS_MAX = 524288;
 
 
 // ---- cold staging ----------------------------------------------------------------------------------------------

@@ -268,7 +268,7 @@ __global__ void hot_slot_kernel(const int32_t *__restrict__ hot_cols, int32_t n_
 }
 
 static int HEAVY_MIN = 2048;      // tier 0 threshold (CSRK_HEAVY_MIN)
-static int TIERB_MIN = 128;       // tier 1 threshold (CSRK_TIERB_MIN; 0 disables tier 1)
+static int TIERB_MIN = TIERB_MIN_DEFAULT;       // tier 1 threshold (CSRK_TIERB_MIN; 0 disables tier 1)
 
 template <class P>
 __global__ void heavy_flag_kernel(const P *__restrict__ rp, int32_t nrows, int32_t *__restrict__ flag,
@@ -1198,7 +1198,7 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
     const char *env = getenv("CSRK_SPMV_HEAVY_SPLIT");
     if (env && env[0] == '0') return CSRK_OK;
     HEAVY_MIN = 2048;
-    TIERB_MIN = 128;
+    TIERB_MIN = TIERB_MIN_DEFAULT;
     // (test hooks, not tuning switches: a small matrix gets more "heavy" rows than one accumulator group holds, or no tier 1)
     if (const char *e = getenv("CSRK_HEAVY_MIN")) HEAVY_MIN = atoi(e) > 64 ? atoi(e) : 64;
     if (const char *e = getenv("CSRK_TIERB_MIN")) TIERB_MIN = atoi(e) >= 0 ? atoi(e) : 0;
@@ -1365,7 +1365,7 @@ static int build_hot_cache(Matrix *m, SpmvPlan *p, hipStream_t s)
     const bool force = env && env[0] == '1';
     if (m->nnz < 2 || m->ncols < 1) return CSRK_OK;
     PlanTrace tr;
-    int64_t HOT_SLOTS = 524288;   // 4 MiB of packed x, most popular first (light stream, LDS for the first 8192: 64k 0.340,
+    int64_t HOT_SLOTS = HOT_SLOTS_MAX;   // 4 MiB of packed x, most popular first (light stream, LDS for the first 8192: 64k 0.340,
                                   // 256k 0.308, 512k 0.302, 1M 0.297, 2M 0.297 ms, but the per-call pack costs more than that gains past 512k)
                                   // earlier sweep, tile kernel, 512 KiB of packed x (measured on the headline matrix: 16k 0.431, 64k 0.422,
                                   // 256k 0.430, 1M 0.439, 4M 0.460 ms for the tile kernel; none 0.481)
@@ -1721,6 +1721,8 @@ static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols,
     ls->idx24 = false;
     ls->n_cold = 0;
     ls->stage_tiles = 0;
+    ls->n_rounds = 0;
+    ls->max_wg_rounds = 0;
     const char *env = getenv("CSRK_LS_STAGE");
     if (env && env[0] == '0') return CSRK_OK;
     const int64_t n_words = ls->n_tiles * ACC_TILE;
@@ -1900,6 +1902,8 @@ static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols,
     }
     ls->n_cold = n_cold;
     ls->stage_tiles = stage_tiles;
+    ls->n_rounds = (int32_t)nround_ls;
+    for (size_t w = 0; w + 1 < h_wr0.size(); w++) ls->max_wg_rounds = std::max(ls->max_wg_rounds, h_wr0[w + 1] - h_wr0[w]);
     tr.lap("  cold: place, 3-byte words");
     return CSRK_OK;
 }

@@ -1219,6 +1219,28 @@ def spgemm_limits():
     return dict(zip(SPGEMM_LIMITS, _limits(lib.csrk_spgemm_limits, len(SPGEMM_LIMITS))))
 
 
+# csrk_spmv_plan_stats, slot by slot (include/csrk.h), and csrk_spmv_stream_limits
+SPMV_PLAN_STATS = ('tiles', 'tile_items', 'cut_rows', 'path_entries', 't0_tiles', 't0_blocks', 't0_min', 't0_block_width', 'split_mode',
+                   't0_rows', 't0_entries', 't1_rows', 't1_pairs', 't1_entries', 't1_min', 't1_block_width', 'n_hot', 'hot_cover_ppm',
+                   't0_acc', 'hot_slots', 'stream', 'ls_tiles', 'ls_runs', 'ls_grid', 'ls_staged', 'plan_bytes', 'ls_round_tiles',
+                   't0_workgroups', 'reserved', 'bytes_t0', 'bytes_t1', 'bytes_stream', 'bytes_staging', 'bytes_tables',
+                   'ls_dense', 'ls_idx24', 'ls_hot_lds', 'ls_rounds', 'ls_wg_rounds', 'ls_stage_blocks', 'ls_stage_width', 'ls_f32')
+SPMV_STREAM_LIMITS = ('ACC_TILE', 'ACC_K', 'LS_WAVES', 'LS_SEQ', 'LS_RID', 'LS_HOT_LDS', 'LS_RND_HOT', 'LS_RND_CAP', 'LS_RND_MAXTILES',
+                      'LS_STAGE_WMAX', 'LS_STAGE_BATCH', 'TIERB_MIN', 'HOT_SLOTS')
+
+
+def spmv_plan_stats(h):
+    "the handle's SpMV plan as a dict (include/csrk.h, csrk_spmv_plan_stats): builds the plan if the handle has none"
+    out = (C.c_int64 * len(SPMV_PLAN_STATS))()
+    check(lib.csrk_spmv_plan_stats(_live(h), out, len(SPMV_PLAN_STATS)))
+    return dict(zip(SPMV_PLAN_STATS, (int(v) for v in out)))
+
+
+def spmv_stream_limits():
+    "the compile-time constants the light stream's form is decided by, as a dict (include/csrk.h, csrk_spmv_stream_limits)"
+    return dict(zip(SPMV_STREAM_LIMITS, _limits(lib.csrk_spmv_stream_limits, len(SPMV_STREAM_LIMITS))))
+
+
 def set_spmv_algo(h, name):
     "select the SpMV kernel for this handle: 'auto' | 'merge' | 'vector' | 'scalar'"
     code = {'auto': _lib.SPMV_AUTO, 'merge': _lib.SPMV_MERGE, 'vector': _lib.SPMV_VECTOR,

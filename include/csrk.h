@@ -176,8 +176,19 @@ CSRK_API int csrk_spmv_plan_info(csrk_handle_t h, int64_t *n_tiles, int32_t *til
  * 22 non-empty rows of the light stream, 23 its workgroups, 24 light-stream entries whose x values are staged
  * per call (cold staging), 25 bytes of device memory the plan holds, 26 tiles per staging round held in LDS (0: none),
  * 27 workgroups of the tier-0 accumulator kernel, 28 0 (reserved), 29..33 the plan's bytes by part: tier 0's accumulator
- * stream, tier 1's pair panel, the light stream, cold staging + pack, tables};  n <= 34. */
+ * stream, tier 1's pair panel, the light stream, cold staging + pack, tables,
+ * the light stream's form, all 0 without a stream: 34 dense layout (every row of the view has a run: no row ids, no gaps)
+ * (0/1), 35 3-byte index words (0/1), 36 pack slots the stream kernel reads from LDS, 37 rounds in all and 38 the most one
+ * workgroup walks (staged rounds; without staging the kernel's own rounds of one tile per wavefront), 39 column blocks of
+ * the copy pass and 40 their width in columns (0 without staging), 41 float32 stored values (0/1)};  n <= 42. */
 CSRK_API int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n);
+/* The compile-time constants the light stream's form is decided by, callable without a device: out[0..n) <- {0 entries per
+ * tile (512), 1 consecutive entries per lane (8), 2 wavefronts per workgroup (8), 3 in-order carry hand-overs (3: a run whose
+ * sum is stored at most 3 lanes after the lane it starts in is summed in the reference's order), 4 batches of 64 run slots whose row ids are fetched
+ * ahead (4), 5 pack slots in LDS without staging (15360) and 6 with it (8176), 7 staged values per round at most (8192),
+ * 8 tiles per round at most (128), 9 columns per block of the copy pass at most (9984), 10 pairs per batch of its loop
+ * (8192), 11 the shortest row the forced split cuts out (128), 12 pack slots at most (524288)};  n <= 13. */
+CSRK_API int csrk_spmv_stream_limits(int64_t *out, int n);
 
 /* Kernel timing for roofline accounting: between begin and end every csrk_spmv_device call on
  * this handle brackets its streaming kernels -- [0] the tile / segment / row kernel, [1] and [2]

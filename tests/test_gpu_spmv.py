@@ -86,8 +86,10 @@ def test_spmv_cfg1(golden, algo):
     _check(y, g['y'], _abs_bound(a, g['x']))
     if algo == 'merge':
         # rows not cut by a tile boundary (2048-item merge tiles, 512-entry stream tiles) are summed in
-        # storage order, products rounded on their own: bit-identical.  (The stream hands carries over in
-        # order across up to 4 lanes = rows of up to 25 entries wherever they lie.)
+        # storage order, products rounded on their own: bit-identical.  (The stream hands a run's sum on in
+        # order to the lane that stores it if that lies at most 3 lanes on: rows of up to 24 entries wherever
+        # they lie, of 25 unless they start in a lane's last slot; the stream's last row is continued by its
+        # padding.  tests/test_gpu_lstream_forms.py checks exactly that set bit for bit; this is a count.)
         lens = np.diff(a.rowptrs)
         assert np.sum(y != g['y']) <= a.nnz // 512 + 1 + int(np.sum(lens > 25))
 

@@ -120,6 +120,10 @@ SIGNATURES = {
     'csrk_rank_entries_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_knn_scores': (_int, [handle_t, handle_t, _vp, _i64, _i32, _i32, _int, _vp, C.POINTER(handle_t)]),
     'csrk_knn_scores_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_knn_scores_reach': (_int, [handle_t, handle_t, _vp, _i64, _i32, _i32, _int, _vp, C.POINTER(handle_t)]),
+    'csrk_knn_reach_index': (_int, [handle_t, _int, C.POINTER(_i64), C.POINTER(_i64)]),
+    'csrk_knn_scores_reach_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_knn_scores_last_stats': (_int, [C.POINTER(_i64), _int]),
     'csrk_from_coo': (_int, [_i32, _i32, _i64, _vp, _vp, _vp, _int, C.POINTER(handle_t)]),
     'csrk_transpose': (_int, [handle_t, _int, C.POINTER(handle_t)]),
     'csrk_row_nnzs': (_int, [handle_t, _vp]),

@@ -512,8 +512,9 @@ class CSR:
         return (ranks, scores) if return_scores else ranks
 
     # ---- two matrices entry by entry -----------------------------------------------------------
-    def _knn_check(self, K, model, users, max_nbrs, min_nbrs, aggregate, offsets):
+    def _knn_check(self, K, model, users, max_nbrs, min_nbrs, aggregate, offsets, route='walk'):
         "knn_scores' arguments as the kernel takes them, checked before any device work; users=None: all rows"
+        K.knn_route_arg(route)
         if not all(hasattr(model, a) for a in ('nrows', 'ncols', 'nnz')) or isinstance(model, np.ndarray):
             raise ValueError(f'model must be a CSR, not {type(model).__name__}')
         users = np.arange(self.nrows, dtype=np.int32) if users is None else users
@@ -523,7 +524,7 @@ class CSR:
                 raise ValueError('CSR size {} exceeds max nnz {}'.format(m.nnz, K.max_nnz))
         return args[0]
 
-    def knn_scores(self, model, users=None, *, max_nbrs=None, min_nbrs=1, aggregate='weighted-average', offsets=None):
+    def knn_scores(self, model, users=None, *, max_nbrs=None, min_nbrs=1, aggregate='weighted-average', offsets=None, route='walk'):
         """
         Scores from an item-kNN model, with this matrix as the ratings [users x items]: a CSR [len(users) x model.nrows],
         float64, canonical, row r for user users[r] (users=None: all rows; any order, repeats allowed).  `model` is a CSR
@@ -533,15 +534,17 @@ class CSR:
         stored: sum(rating * similarity) / sum(|similarity|) over the hits (aggregate='weighted-average') or
         sum(similarity) ('sum'), plus offsets[r] when offsets is given (a user's mean after center_rows).  Every operation is
         rounded on its own in storage order, so the result is a function of the arguments, bit for bit (include/csrk.h,
-        csrk_knn_scores).  This matrix must be canonical (sort_rows / coalesce); the model need not be.  Runs on the device
-        only.  Not a reference entry point.
+        csrk_knn_scores).  This matrix must be canonical (sort_rows / coalesce); the model need not be.  route='walk'
+        visits every target for every user; route='reach' only the targets that hold one of the user's rated items -- the
+        same bits, from an index of the model's pattern that its device copy keeps (the model's columns must lie in
+        [0, ncols)).  Runs on the device only.  Not a reference entry point.
         """
         K, fn = self._ext('knn_scores')
-        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets)
+        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets, route)
         mx = 0 if max_nbrs is None else max_nbrs
         with releasing(K.to_handle(model), K) as m_h:
             with releasing(K.to_handle(self), K) as r_h:
-                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets), K) as s_h:
+                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets, route=route), K) as s_h:
                     return K.from_handle(s_h)
 
     def knn_topk(self, model, users, n, *, exclude=True, min_value=None, **scoring):
@@ -556,19 +559,20 @@ class CSR:
         _, top = self._ext('topk_rows')
         _, comb = self._ext('combine')
         _, pick = self._ext('pick_rows')
-        bad = set(scoring) - {'max_nbrs', 'min_nbrs', 'aggregate', 'offsets'}
+        bad = set(scoring) - {'max_nbrs', 'min_nbrs', 'aggregate', 'offsets', 'route'}
         if bad:
             raise TypeError(f'knn_topk got unexpected scoring arguments {sorted(bad)}')
         max_nbrs, min_nbrs = scoring.get('max_nbrs'), scoring.get('min_nbrs', 1)
         aggregate, offsets = scoring.get('aggregate', 'weighted-average'), scoring.get('offsets')
-        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets)
+        route = scoring.get('route', 'walk')
+        users = self._knn_check(K, model, users, max_nbrs, min_nbrs, aggregate, offsets, route)
         _topk_check(K, n, min_value, 'descending')
         if exclude and model.nrows != self.ncols:
             raise ValueError(f'exclude=True needs a model over the rated items: model has {model.nrows} rows, ratings {self.ncols} columns')
         mx = 0 if max_nbrs is None else max_nbrs
         with releasing(K.to_handle(model), K) as m_h:
             with releasing(K.to_handle(self), K) as r_h:
-                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets), K) as s_h:
+                with releasing(fn(m_h, r_h, users, mx, min_nbrs, aggregate, offsets, route=route), K) as s_h:
                     if not exclude:
                         with releasing(top(s_h, n, min_value, 'descending'), K) as t_h:
                             return K.from_handle(t_h)

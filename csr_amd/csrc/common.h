@@ -128,6 +128,8 @@ struct Matrix {
     int canonical = -1;            // every row strictly ascending in column: 1, 0 (noncanonical_row: the first row that is not), -1 = not looked
     int32_t noncanonical_row = -1; // at yet (csrk_combine; reset like dense_panel: order_columns rewrites the columns)
     int nondescending = -1;        // no entry below its predecessor in the row (repeats allowed): 1, 0, -1; from the same look (csrk_coalesce)
+    Matrix *knn_reach = nullptr;   // as the model of csrk_knn_scores_reach: the structure-only transpose of the pattern (knn_scores.hip), kept like
+                                   // a plan -- built under mu, counted by csrk_device_bytes, dropped by invalidate_plans, freed with the handle
     // A launch was issued on a caller's stream: the caching allocator recycles blocks in default-stream order only,
     // and a non-blocking stream is not ordered with the default one, so the handle's memory (arrays, plans, scratch)
     // goes back to the pool only after the device has drained (csrk_free, plan invalidation, scratch growth).
@@ -146,7 +148,9 @@ int64_t spmv_plan_bytes(const SpmvPlan *p);     // device memory a plan holds
 int64_t spmm_plan_bytes(const SpmmPlan *p);
 // Drop the handle's SpMV / SpMM plans (they hold re-ordered COPIES of colinds and values, so every operation
 // that changes the matrix in place -- unit_rows, center_rows, order_columns -- must call this).  Waits for the
-// device first: a launch may still be reading the plan.  Caller holds m->mu.
+// device first: a launch may still be reading the plan.  Caller holds m->mu.  The reach index (knn_reach) goes
+// with them: order_columns rewrites the columns it was built from; the in-place value operations would leave it
+// right (it holds no value) and drop it all the same -- one rule for everything the handle caches.
 void invalidate_plans(Matrix *m);
 // Wait for every stream of the device if a caller's stream ever launched on this handle (before its memory is recycled).
 void drain_user_streams(Matrix *m);

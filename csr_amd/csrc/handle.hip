@@ -225,6 +225,7 @@ Matrix::~Matrix()
 {
     if (spmv_plan) free_spmv_plan(spmv_plan);
     if (spmm_plan) free_spmm_plan(spmm_plan);
+    delete knn_reach;
     if (owns) {
         pool_free(d_rowptrs);
         pool_free(d_colinds);
@@ -262,8 +263,12 @@ void invalidate_plans(Matrix *m)
     m->dense_panel = -1;      // (order_columns may have made the rows ascending, or not)
     m->canonical = -1;        // (the same for csrk_combine's look at the rows)
     m->nondescending = -1;
-    if (!m->spmv_plan && !m->spmm_plan) return;
+    if (!m->spmv_plan && !m->spmm_plan && !m->knn_reach) return;
     (void)hipDeviceSynchronize();
+    if (m->knn_reach) {
+        delete m->knn_reach;
+        m->knn_reach = nullptr;
+    }
     if (m->spmm_plan) {                 // may hold a view into the SpMV plan: goes first
         free_spmm_plan(m->spmm_plan);
         m->spmm_plan = nullptr;
@@ -529,6 +534,7 @@ int csrk_device_bytes(csrk_handle_t h, int64_t *bytes)
     int64_t b = (int64_t)((size_t)(m->nrows + 1) * m->ptr_bytes() + (size_t)m->nnz * 4 + (size_t)m->nnz * m->val_bytes());
     if (m->spmv_plan) b += spmv_plan_bytes(m->spmv_plan);
     if (m->spmm_plan) b += spmm_plan_bytes(m->spmm_plan);
+    if (const Matrix *t = m->knn_reach) b += (int64_t)((size_t)(t->nrows + 1) * t->ptr_bytes() + (size_t)t->nnz * 4);
     *bytes = b;
     return CSRK_OK;
 }

@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
-is_canonical, topk_scores, topk_scores_for, rank_entries, knn_scores.
+is_canonical, topk_scores, topk_scores_for, rank_entries, knn_scores, knn_reach_index.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -1153,7 +1153,19 @@ def knn_scores_args(model, ratings, users, max_nbrs=0, min_nbrs=1, aggregate='we
     return np.ascontiguousarray(users, dtype=np.int32), min(int(max_nbrs), i4), min(int(min_nbrs), i4), _KNN_AGGREGATES[aggregate], offsets
 
 
-def knn_scores(model_h, ratings_h, users, max_nbrs=0, min_nbrs=1, aggregate='weighted-average', offsets=None):
+_KNN_ROUTES = ('walk', 'reach')
+KNN_STATS = ('reach', 'ranges_per_row', 'workgroups', 'count_from_marks', 'built_index', 'entries')
+KNN_REACH_LIMITS = ('range', 'lanes', 'lds_row', 'filter_bits', 'round', 'chunk', 'long_reach_row')
+
+
+def knn_route_arg(route):
+    "route as given, or ValueError: 'walk' (every target of every listed row) or 'reach' (only the targets the user's ratings reach)"
+    if not isinstance(route, str) or route not in _KNN_ROUTES:
+        raise ValueError(f"route must be 'walk' or 'reach', not {route!r}")
+    return route
+
+
+def knn_scores(model_h, ratings_h, users, max_nbrs=0, min_nbrs=1, aggregate='weighted-average', offsets=None, route='walk'):
     """
     Scores from an item-kNN model on the device: NEW handle [len(users) x model.nrows], float64, canonical.  For user
     users[r] and each target i, the entries (j, s) of model row i are walked in storage order; those whose item j the user
@@ -1161,12 +1173,42 @@ def knn_scores(model_h, ratings_h, users, max_nbrs=0, min_nbrs=1, aggregate='wei
     it had at least min_nbrs hits: sum(v s) / sum(|s|) over the hits ('weighted-average') or sum(s) ('sum'), plus offsets[r]
     when offsets is given.  Every operation is rounded on its own, in storage order: the result is a function of its
     arguments, bit for bit (include/csrk.h, csrk_knn_scores).  ratings_h's matrix must be canonical, model_h's need not be.
-    Not a reference entry point.
+    route='walk' visits every target for every user; route='reach' only the targets that hold one of the user's rated items
+    (csrk_knn_scores_reach: the same bits; model_h keeps the index the route needs, knn_reach_index; the model's columns must
+    lie in [0, ncols)).  Not a reference entry point.
     """
+    fn = lib.csrk_knn_scores_reach if knn_route_arg(route) == 'reach' else lib.csrk_knn_scores
     users, mx, mn, code, offsets = knn_scores_args(model_h, ratings_h, users, max_nbrs, min_nbrs, aggregate, offsets)
     out = handle_t(0)
-    _call(lib.csrk_knn_scores, _live(model_h), _live(ratings_h), ptr(users), users.size, mx, mn, code, ptr(offsets), C.byref(out))
+    _call(fn, _live(model_h), _live(ratings_h), ptr(users), users.size, mx, mn, code, ptr(offsets), C.byref(out))
     return _wrap(out.value)
+
+
+def knn_reach_index(model_h, build=True):
+    """
+    (entries, device bytes) of the reach index model_h holds -- the structure-only transpose of the model's pattern that
+    knn_scores(route='reach') marks its candidates from -- built first when build is true and there is none; (0, 0) when
+    there is none and build is false.  The handle keeps it until order_columns or an in-place value operation drops it.
+    """
+    entries, nbytes = C.c_int64(0), C.c_int64(0)
+    _call(lib.csrk_knn_reach_index, _live(model_h), 1 if build else 0, C.byref(entries), C.byref(nbytes))
+    return int(entries.value), int(nbytes.value)
+
+
+def knn_scores_reach_limits():
+    """
+    (targets of a range = bits of the mark bitmap, lanes that share a walk, entries of a rating row held in LDS, bits of the
+    column filter, candidates walked per round, targets per enumeration chunk, longest reach row a group of lanes marks)
+    """
+    return _limits(lib.csrk_knn_scores_reach_limits, len(KNN_REACH_LIMITS))
+
+
+def knn_scores_last_stats():
+    """
+    what this thread's last knn_scores did, as a tuple in KNN_STATS' order (include/csrk.h, csrk_knn_scores_last_stats): all
+    zero after route='walk', after a call that failed and after an empty result
+    """
+    return _limits(lib.csrk_knn_scores_last_stats, len(KNN_STATS))
 
 
 def set_spgemm_order(order):

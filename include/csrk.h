@@ -817,6 +817,40 @@ CSRK_API int csrk_knn_scores(csrk_handle_t model, csrk_handle_t ratings, const i
                              int32_t min_nbrs, int aggregate, const double *offsets, csrk_handle_t *out);
 CSRK_API int csrk_knn_scores_limits(int64_t *out, int n);
 
+/* ---- knn_scores, the reach route: walk only the targets a user's ratings reach ------------------------------
+ * csrk_knn_scores visits every target for every listed row, and nearly all (row, target) pairs have no rated neighbour.  A
+ * target i has a hit for user u exactly when some item j that u rated is stored in model row i -- when i lies in row j of
+ * the transpose of the model's pattern.  csrk_knn_scores_reach marks those targets per listed row and walks only them.
+ * Rules 1-7 of csrk_knn_scores hold word for word (the refusal texts begin "knn_scores_reach: "; same order, same status
+ * codes, same empty-result cases, in which nothing is launched, nothing is built and ratings is not looked at), and the row
+ * pointers, columns and values of the result equal csrk_knn_scores' bit for bit for every input: min_nbrs >= 1, so every
+ * stored target is a marked one, and a marked target is walked by the routine csrk_knn_scores walks with.
+ *   One further requirement: model column indices must lie in [0, ncols), as csrk_transpose requires of its operand -- the
+ *   index is built from them.  A ratings column outside [0, n_items) is never an address: it reaches nothing.
+ *   The reach index of a model is the structure-only transpose of its pattern: row j holds, ascending, the targets whose
+ *   model row stores column j, once per stored occurrence (entries = the model's nnz).  The model handle keeps it the way it
+ *   keeps its plans: built under the handle's lock by the first csrk_knn_scores_reach or by csrk_knn_reach_index(build = 1),
+ *   counted by csrk_device_bytes, dropped by everything that drops the plans -- csrk_order_columns, which rewrites the
+ *   columns, and the in-place value operations (csrk_unit_rows, csrk_center_rows ...) too, although they would leave it
+ *   right -- and freed with the handle.  csrk_knn_reach_index with build = 0 only reports: *entries = *bytes = 0 when the
+ *   handle holds no index.
+ *   Limits (csrk_knn_scores_reach_limits): out[0] = R, the targets of one range = the bits of the mark bitmap a workgroup
+ *   holds in LDS (a power of two, a multiple of 32; one workgroup takes one (listed row, range) pair); [1] = the lanes that
+ *   share a walk, [2] = the staged rating-row entries, [3] = the filter bits (csrk_knn_scores_limits' [0], [2], [3]); [4] =
+ *   the candidates a workgroup walks per round; [5] = the targets per enumeration chunk (= [0]: a range is enumerated in one
+ *   piece); [6] = a reach row with more entries than this at or above the range's base is marked by a whole wavefront
+ *   rather than by [1] lanes;  n <= 7.  No device is touched; none of them changes a bit.
+ *   Diagnostics (csrk_knn_scores_last_stats; thread-local, filled from what the host holds, like csrk_spgemm_last_stats):
+ *   out[0] = 1 when the calling thread's last scoring call took the reach route (0 after csrk_knn_scores, after a failed
+ *   call and after an empty result, and then every slot is 0); [1] = ranges per listed row = ceil(n_targets / R); [2] =
+ *   workgroups per pass; [3] = 1 when the first pass counted marks without walking (min_nbrs == 1); [4] = 1 when this call
+ *   built the index; [5] = entries stored;  n <= 6. */
+CSRK_API int csrk_knn_scores_reach(csrk_handle_t model, csrk_handle_t ratings, const int32_t *rows, int64_t n_rows,
+                                   int32_t max_nbrs, int32_t min_nbrs, int aggregate, const double *offsets, csrk_handle_t *out);
+CSRK_API int csrk_knn_reach_index(csrk_handle_t model, int build, int64_t *entries, int64_t *bytes);
+CSRK_API int csrk_knn_scores_reach_limits(int64_t *out, int n);
+CSRK_API int csrk_knn_scores_last_stats(int64_t *out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,12 @@ entry here waits for the device before it returns; median, min, max, quartiles):
   numpy    (b) the host route: a NumPy restatement of the rule over the padded model, one user at a time, on the first
            --numpy-users users of the batch; its values must equal `scores` bit for bit (checked).
 A second `scores` call must give the same bits (checked).  The parent prints one JSON line and writes it to --out.
+Both routes of knn_scores are measured, each in fresh processes that alternate -- per batch and per min_nbrs in (1, 2): 'walk'
+(every target of every user), then 'reach' (only the targets the user's ratings reach; csrk_knn_scores_reach).  The walk
+child with min_nbrs = 1 is the run described above; the others time `scores` alone.  A reach child first builds the model's
+reach index and reports that one-off time (`index`), and after its timings scores the batch by the walk route too: the two
+results must be the same bits (`routes_same_bits`).  `routes` in the result line puts the pairs side by side: the reach
+route's median against the walk route's minimum of the same session, and the calls after which the index build is paid for.
     python tools/bench_knn_scores.py [--batches 1,64,1024,16384] [--out FILE]
 """
 import argparse
@@ -142,7 +148,11 @@ def numpy_scores(mrp, mci, mvs, cols, vals, max_nbrs, offset):
     return np.flatnonzero(stored).astype(np.int32), val
 
 
-def child(path, n_users, steps, warmup, numpy_users):
+def _same_bits(a, b):
+    return bool(np.array_equal(a.rowptrs, b.rowptrs) and np.array_equal(a.colinds, b.colinds) and a.values.tobytes() == b.values.tobytes())
+
+
+def child(path, n_users, steps, warmup, numpy_users, route='walk', min_nbrs=1):
     import torch
     from csr_amd import CSR
     from csr_amd.kernels import hip as K, releasing
@@ -154,20 +164,39 @@ def child(path, n_users, steps, warmup, numpy_users):
     g = np.random.default_rng(31)
     users = g.choice(h.nrows, size=n_users, replace=False).astype(np.int32)
     off = np.ascontiguousarray(means[users], dtype=np.float64)
-    rec = {'users': n_users, 'max_nbrs': K_NBRS, 'n_top': N_TOP}
+    rec = {'users': n_users, 'max_nbrs': K_NBRS, 'n_top': N_TOP, 'route': route, 'min_nbrs': min_nbrs}
     if n_users >= 4096:
         steps = max(3, steps // 4)
     keep = []
+    if route == 'reach':                 # the one-off cost of the route: the index the model handle keeps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        entries, nbytes = K.knn_reach_index(m_h)
+        torch.cuda.synchronize()
+        rec['index'] = {'build_ms': round((time.perf_counter() - t0) * 1e3, 3), 'entries': entries, 'bytes': nbytes}
 
     def scores():
         for x in keep:
             K.release_handle(x)
-        keep[:] = [K.knn_scores(m_h, h, users, K_NBRS, 1, 'weighted-average', off)]
+        keep[:] = [K.knn_scores(m_h, h, users, K_NBRS, min_nbrs, 'weighted-average', off, route=route)]
         return keep[0]
     rec['scores'], s_h = _timed(scores, steps, warmup)
     rec['scores_nnz'] = int(s_h.nnz)
+    if route == 'reach':
+        rec['last_stats'] = dict(zip(K.KNN_STATS, K.knn_scores_last_stats()))
     small = s_h.nnz <= 50_000_000
     first = K.from_handle(s_h) if small else None
+    if route != 'walk' or min_nbrs != 1:       # `scores` alone, and for the reach route the same batch by the walk route
+        if small:
+            rec['second_call_same_bits'] = _same_bits(first, K.from_handle(scores()))
+            if route == 'reach':
+                with K_releasing(K.knn_scores(m_h, h, users, K_NBRS, min_nbrs, 'weighted-average', off)) as wh:
+                    rec['routes_same_bits'] = _same_bits(first, K.from_handle(wh))
+        rec['parity'] = {'ok': bool(rec.get('second_call_same_bits', True) and rec.get('routes_same_bits', True))}
+        for x in keep + [m_h, h]:
+            K.release_handle(x)
+        torch.cuda.synchronize()
+        return rec
 
     def topk():
         with K_releasing(K.knn_scores(m_h, h, users, K_NBRS, 1, 'weighted-average', off)) as sh:
@@ -185,9 +214,7 @@ def child(path, n_users, steps, warmup, numpy_users):
     rec['product'], pn = _timed(product, max(3, steps // 2), 1)
     rec['product_nnz'] = int(pn)
     if small:
-        again = K.from_handle(scores())
-        rec['second_call_same_bits'] = bool(np.array_equal(first.rowptrs, again.rowptrs) and np.array_equal(first.colinds, again.colinds) and
-                                            first.values.tobytes() == again.values.tobytes())
+        rec['second_call_same_bits'] = _same_bits(first, K.from_handle(scores()))
         # the host route on a sample: the first numpy_users users of the batch
         rp = np.empty(h.nrows + 1, np.int32)
         ci = np.empty(h.nnz, np.int32)
@@ -228,12 +255,15 @@ def main():
     ap.add_argument('--model-dir', default=None, help='keep the model here (and reuse one that is there)')
     ap.add_argument('--out', default=None)
     ap.add_argument('--child', default=None, help='(internal) "model" or a number of users')
+    ap.add_argument('--route', default='walk', help='(internal) the route a child measures')
+    ap.add_argument('--min-nbrs', type=int, default=1, help='(internal) min_nbrs of a child')
+    ap.add_argument('--routes', default='walk,reach', help='routes to measure, alternating per batch')
     a = ap.parse_args()
     if a.child == 'model':
         print(json.dumps(build_model(a.model_dir, a.block, a.min_sim)), flush=True)
         return
     if a.child is not None:
-        print(json.dumps(child(a.model_dir, int(a.child), a.steps, a.warmup, a.numpy_users)), flush=True)
+        print(json.dumps(child(a.model_dir, int(a.child), a.steps, a.warmup, a.numpy_users, a.route, a.min_nbrs)), flush=True)
         return
     tmp = None
     if a.model_dir is None:
@@ -242,27 +272,53 @@ def main():
     os.makedirs(a.model_dir, exist_ok=True)
     base = ['timeout', '-k', '10', str(a.child_timeout), sys.executable, os.path.abspath(__file__), '--model-dir', a.model_dir, '--steps',
             str(a.steps), '--warmup', str(a.warmup), '--numpy-users', str(a.numpy_users), '--block', str(a.block), '--min-sim', str(a.min_sim)]
-    model, results, failed = None, [], None
-    jobs = ([] if os.path.exists(os.path.join(a.model_dir, 'vs.npy')) else ['model']) + a.batches.split(',')
-    for job in jobs:
-        p = subprocess.run(base + ['--child', job], cwd=ROOT, capture_output=True, text=True)
+    model, results, others, failed = None, [], [], None
+    routes = a.routes.split(',')
+    jobs = [] if os.path.exists(os.path.join(a.model_dir, 'vs.npy')) else [('model', 'walk', 1)]
+    jobs += [(b, route, mn) for b in a.batches.split(',') for mn in (1, 2) for route in routes]
+    for job, route, mn in jobs:
+        p = subprocess.run(base + ['--child', job, '--route', route, '--min-nbrs', str(mn)], cwd=ROOT, capture_output=True, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
         if p.returncode != 0 or not lines:
-            failed = {'job': job, 'returncode': p.returncode, 'stderr': p.stderr[-2000:]}
+            failed = {'job': job, 'route': route, 'min_nbrs': mn, 'returncode': p.returncode, 'stderr': p.stderr[-2000:]}
             break                      # a child that failed ends the run: nothing more is started on the GPU
         r = json.loads(lines[-1])
         if job == 'model':
             model = r
             print(f'[bench_knn_scores] model: {r}', file=sys.stderr, flush=True)
             continue
-        results.append(r)
-        print(f'[bench_knn_scores] {r["users"]} users: scores {r["scores"]["median_ms"]} ms ({r["scores_nnz"]} entries), topk '
-              f'{r["topk"]["median_ms"]} ms, product {r["product"]["median_ms"]} ms ({r["product_nnz"]} entries), numpy per user '
-              f'{r.get("numpy_per_user", {}).get("median_ms")} ms, parity {r["parity"]["ok"]}', file=sys.stderr, flush=True)
+        if route == 'walk' and mn == 1:
+            results.append(r)
+            print(f'[bench_knn_scores] {r["users"]} users: scores {r["scores"]["median_ms"]} ms ({r["scores_nnz"]} entries), topk '
+                  f'{r["topk"]["median_ms"]} ms, product {r["product"]["median_ms"]} ms ({r["product_nnz"]} entries), numpy per user '
+                  f'{r.get("numpy_per_user", {}).get("median_ms")} ms, parity {r["parity"]["ok"]}', file=sys.stderr, flush=True)
+        else:
+            others.append(r)
+            print(f'[bench_knn_scores] {r["users"]} users, {route}, min_nbrs {mn}: scores {r["scores"]["median_ms"]} ms '
+                  f'({r["scores_nnz"]} entries), index {r.get("index")}, parity {r["parity"]["ok"]}', file=sys.stderr, flush=True)
+    # the routes side by side, per batch and min_nbrs
+    table = []
+    by = {(r['users'], r['min_nbrs'], r['route']): r for r in results + others}
+    for (users, mn, route), r in sorted(by.items()):
+        w = by.get((users, mn, 'walk'))
+        if route != 'reach' or w is None:
+            continue
+        row = {'users': users, 'min_nbrs': mn, 'walk': w['scores'], 'reach': r['scores'], 'scores_nnz': r['scores_nnz'],
+               'same_entries': r['scores_nnz'] == w['scores_nnz'], 'routes_same_bits': r.get('routes_same_bits'),
+               'index_build_ms': r['index']['build_ms'], 'reach_median_below_walk_min': r['scores']['median_ms'] < w['scores']['min_ms'],
+               'walk_median_over_reach_median': round(w['scores']['median_ms'] / r['scores']['median_ms'], 3)}
+        gain = w['scores']['median_ms'] - r['scores']['median_ms']
+        row['calls_to_pay_for_the_index'] = None if gain <= 0 else int(np.ceil(r['index']['build_ms'] / gain))
+        product = by.get((users, 1, 'walk'), {}).get('product')
+        if product:
+            row['product_median_ms'] = product['median_ms']
+        table.append(row)
+    every = results + others
     line = json.dumps({'bench': 'knn_scores', 'workload': 'synth.movielens_like() centred per user; item-kNN model of 20 neighbours from '
                        'unit item rows (mult_abt -> filter_zeros -> drop diagonal -> topk_rows); max_nbrs 20, min_nbrs 1, weighted '
-                       'average, offsets = user means; wall-clock per call', 'model': model, 'results': results, 'failed': failed,
-                       'parity_ok': failed is None and all(r['parity']['ok'] for r in results)})
+                       'average, offsets = user means; wall-clock per call', 'model': model, 'results': results, 'other_runs': others,
+                       'routes': table, 'failed': failed,
+                       'parity_ok': failed is None and all(r['parity']['ok'] for r in every) and all(t['same_entries'] for t in table)})
     print(line, flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

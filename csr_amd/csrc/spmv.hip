@@ -62,7 +62,7 @@ void spmv_plan_bytes_by_part(const SpmvPlan *p, int64_t out[5])
     auto add = [&](int part, std::initializer_list<const DevBuf *> bufs) {
         for (const DevBuf *b : bufs) out[part] += (int64_t)b->bytes;
     };
-    for (const AccPanel *ap : p->acc) add(0, {&ap->row_list, &ap->vals, &ap->idx, &ap->tile_row0, &ap->segs, &ap->wg_seg, &ap->partial, &ap->z});
+    for (const AccPanel *ap : p->acc) add(0, {&ap->row_list, &ap->vals, &ap->idx, &ap->tile_row0, &ap->segs, &ap->wg_seg, &ap->partial, &ap->z, &ap->wg_map});
     const Panel &t = p->tier1;
     add(1, {&t.row_list, &t.rp, &t.ci, &t.vs, &t.tile, &t.group, &t.carry_row, &t.carry_val, &t.y, &t.crp, &t.cidx});
     const LightStream *l = &p->ls;
@@ -341,12 +341,15 @@ __global__ void hot_pack_kernel(const XT *__restrict__ x, const int32_t *__restr
 // Tier 0's reduce as extra workgroups of the pair kernel's launch.  The accumulator kernel has finished when the pair kernel
 // starts (stream order) and the pair kernel waits on L1 line fills, not on HBM: the 33 MB of partials are read beside
 // it, the epilogue only scatters the 15 936 sums (z -> y[row_list]) instead of reading them.  Workgroups
-// [first, first + ceil(H / 64)) of the launch; first = the launch's size when nothing rides along.
+// [first, first + ceil(H / 64)) of the launch; first = the launch's size when nothing rides along.  The groups of one
+// accumulator launch (accgroups::MAX_GROUPS at most) ride one behind the other: group q takes the workgroups from
+// first + start[q] on (start[0] = 0; INT32_MAX for a group that is not there), each row's sum over its OWN group's workgroups
+// in their order -- column ranges ascending, as for one group.
 struct PanelRider {
     int64_t first;
-    const double *partial;      // [n_wg][H]: the accumulator kernel's per-workgroup sums
-    double *z;                  // [H]
-    int32_t H, n_wg;
+    const double *partial[accgroups::MAX_GROUPS];      // [n_wg][H]: the accumulator kernel's per-workgroup sums
+    double *z[accgroups::MAX_GROUPS];                  // [H]
+    int32_t H[accgroups::MAX_GROUPS], n_wg[accgroups::MAX_GROUPS], start[accgroups::MAX_GROUPS];
 };
 
 template <class PP, int PT, bool R32 = false, class XT = double>
@@ -370,20 +373,34 @@ __global__ __launch_bounds__(PT) void spmv_panel_kernel(
         // Tier 0's ordered reduce rides along (PanelRider): this workgroup sums the accumulator kernel's partials of 64
         // heavy rows -- wavefront g the workgroups [g * per, (g + 1) * per), joined in order through LDS -- into z[h].
         constexpr int G = PT / WAVE;
-        const int h = (int)((int64_t)blockIdx.x - rider.first) * WAVE + lane;
-        const int per = (rider.n_wg + G - 1) / G;
-        const int w0 = wv * per, w1 = w0 + per < rider.n_wg ? w0 + per : rider.n_wg;
+        int rb = (int)((int64_t)blockIdx.x - rider.first);
+        const double *__restrict__ partial = rider.partial[0];
+        double *__restrict__ z = rider.z[0];
+        int32_t H = rider.H[0], n_wg = rider.n_wg[0], start = 0;
+#pragma unroll
+        for (int q = 1; q < accgroups::MAX_GROUPS; q++)
+            if (rb >= rider.start[q]) {
+                partial = rider.partial[q];
+                z = rider.z[q];
+                H = rider.H[q];
+                n_wg = rider.n_wg[q];
+                start = rider.start[q];
+            }
+        rb -= start;
+        const int h = rb * WAVE + lane;
+        const int per = (n_wg + G - 1) / G;
+        const int w0 = wv * per, w1 = w0 + per < n_wg ? w0 + per : n_wg;
         double acc = 0.0;
-        if (h < rider.H) {
+        if (h < H) {
 #pragma unroll 8
-            for (int w = w0; w < w1; w++) acc += rider.partial[(int64_t)w * rider.H + h];
+            for (int w = w0; w < w1; w++) acc += partial[(int64_t)w * H + h];
         }
         s_buf[wv * WAVE + lane] = acc;
         __syncthreads();
-        if (wv == 0 && h < rider.H) {
+        if (wv == 0 && h < H) {
             double tot = s_buf[lane];
             for (int u = 1; u < G; u++) tot += s_buf[u * WAVE + lane];
-            rider.z[h] = tot;
+            z[h] = tot;
         }
         return;
     }
@@ -509,13 +526,26 @@ __global__ __launch_bounds__(PT) void spmv_panel_kernel(
 }
 
 template <int CB, int PT, bool R32 = false, class SV = double, class XT = double>
-__global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pvals, const uint16_t *__restrict__ pidx,
-                                                     const int32_t *__restrict__ tile_row0,
-                                                     const XT *__restrict__ x, int32_t ncols,
-                                                     const AccSeg *__restrict__ segs, const int32_t *__restrict__ wg_seg,
-                                                     int32_t H, double *__restrict__ partial, int32_t fx_g)
+__global__ __launch_bounds__(PT) void spmv_acc_kernel(const AccLaunchArgs L, const XT *__restrict__ x, int32_t ncols)
 {
-    // fx_g: the grid exponent of a fix56 stream's values (SV = fix56::Packed; the other streams ignore it)
+    // One launch serves up to accgroups::MAX_GROUPS row groups side by side: this block is workgroup `wg` of group `grp`
+    // (L.wg_map; without a map the launch has one group and block b is its workgroup b) and works on that group's arrays
+    // alone -- its own accumulators, its own rows of partial[] -- so no workgroup waits for another.
+    uint32_t grp = 0, wg = blockIdx.x;
+    if (L.wg_map) {
+        const uint32_t id = L.wg_map[blockIdx.x];
+        grp = id >> 16;
+        wg = id & 0xffffu;
+    }
+    const AccGroupArgs &A = L.g[grp];
+    const SV *__restrict__ pvals = (const SV *)A.vals;
+    const uint16_t *__restrict__ pidx = A.idx;
+    const int32_t *__restrict__ tile_row0 = A.tile_row0;
+    const AccSeg *__restrict__ segs = A.segs;
+    const int32_t *__restrict__ wg_seg = A.wg_seg;
+    double *__restrict__ partial = A.partial;
+    const int32_t H = A.H;
+    const int32_t fx_g = A.fx_g;      // the grid exponent of a fix56 stream's values (SV = fix56::Packed; the other streams ignore it)
     extern __shared__ __align__(16) unsigned char acc_smem[];
     double *s_x = (double *)acc_smem;                     // CB + 2 (slot CB = 0.0 for padding entries)
     double *s_acc = s_x + CB + 2;                         // Hpad
@@ -531,7 +561,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pva
     const unsigned long long upto = below | (1ull << lane);                       // lanes <= lane
 
     int cur_blk = -1;
-    const int sb = wg_seg[blockIdx.x], se = wg_seg[blockIdx.x + 1];
+    const int sb = wg_seg[wg], se = wg_seg[wg + 1];
     for (int si = sb; si < se; si++) {
         const AccSeg sg = segs[si];
         if (sg.blk != cur_blk) {
@@ -565,7 +595,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pva
         u32x4_t ix, ixn;                  // eight 16-bit index words per lane
         int32_t tr0 = 0, tr0n = 0;        // heavy-row index of the tile's first entry
         int t = wv;
-        const int64_t pstep = (int64_t)gridDim.x;      // the workgroups' tiles are interleaved (acc_phys_tile)
+        const int64_t pstep = (int64_t)A.n_wg;      // the group's workgroups' tiles are interleaved (acc_phys_tile)
         if (t < nt) {
             const u32x4_t *ip = (const u32x4_t *)(pidx + (sg.ptile0 + t * pstep) * ACC_TILE);
             v.load(pvals + (sg.ptile0 + t * pstep) * ACC_TILE, lane);
@@ -674,7 +704,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const SV *__restrict__ pva
         }
     }
     __syncthreads();
-    for (int h = tid; h < H; h += PT) partial[(int64_t)blockIdx.x * H + h] = s_acc[h];
+    for (int h = tid; h < H; h += PT) partial[(int64_t)wg * H + h] = s_acc[h];
 }
 
 // The per-SpMV epilogue -- the carry fix-up of the light stream, the ordered reduce of tier 1 (over the column blocks, plus
@@ -1411,11 +1441,25 @@ static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipSt
         bool t0_rides = false;      // tier 0's reduce ran inside the pair kernel's launch: the epilogue only scatters its sums
         if (do_heavy && p->n_heavy && !p->acc.empty()) {        // tier 0, accumulator form
             KernelTimer kh(p, s, 1);
-            for (AccPanel *ap : p->acc) {
-#define ACC_LAUNCH(SV)                                                                                                 \
-    spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, SV, XT><<<(unsigned)ap->n_wg, ACC_THREADS, ap->lds, s>>>(                \
-        ap->vals.as<SV>(), ap->idx.as<uint16_t>(), ap->tile_row0.as<int32_t>(), d_x, m->ncols, ap->segs.as<AccSeg>(),  \
-        ap->wg_seg.as<int32_t>(), ap->nrow, ap->partial.as<double>(), ap->fx_g)
+            for (size_t a0 = 0; a0 < p->acc.size(); a0 += (size_t)p->acc[a0]->launch_groups) {
+                // one launch: the group p->acc[a0] and those that run side by side with it (build_acc_groups)
+                AccPanel *ap = p->acc[a0];
+                const int gb = ap->launch_groups;
+                if (gb < 1 || gb > accgroups::MAX_GROUPS || a0 + (size_t)gb > p->acc.size()) {
+                    set_error("internal: tier 0's groups and launches disagree");
+                    return CSRK_ERR_INVALID;
+                }
+                AccLaunchArgs L = {};
+                size_t lds = 0;
+                for (int g = 0; g < gb; g++) {
+                    const AccPanel *aq = p->acc[a0 + (size_t)g];
+                    L.g[g] = {aq->vals.p, aq->idx.as<uint16_t>(), aq->tile_row0.as<int32_t>(), aq->segs.as<AccSeg>(),
+                              aq->wg_seg.as<int32_t>(), aq->partial.as<double>(), aq->nrow, aq->n_wg, aq->fx_g, 0};
+                    lds = aq->lds > lds ? aq->lds : lds;
+                }
+                L.wg_map = gb > 1 ? ap->wg_map.as<uint32_t>() : nullptr;
+                const unsigned n_blocks = (unsigned)(gb > 1 ? ap->launch_wgs : ap->n_wg);
+#define ACC_LAUNCH(SV) spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, SV, XT><<<n_blocks, ACC_THREADS, lds, s>>>(L, d_x, m->ncols)
                 if (ap->f32) ACC_LAUNCH(float);
                 else if (ap->fix56) ACC_LAUNCH(fix56::Packed);
                 else ACC_LAUNCH(double);
@@ -1431,16 +1475,25 @@ static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipSt
     pn->rp.as<PP>(), pn->ci.as<int32_t>(), pn->vs.as<double>(), d_x, m->ncols, pn->y.as<double>(),                    \
         pn->tile.as<PanelTile>(), pn->group.as<PanelGroup>(), pn->rows, pn->carry_row.as<int32_t>(),                  \
         pn->carry_val.as<double>(), pn->nnz, pn->cb, rider
-            PanelRider rider = {pn->groups, nullptr, nullptr, 0, 0};
-            if (PANEL_T1 / WAVE == 4 && do_heavy && p->acc.size() == 1 && p->acc[0]->z.p) {
-                AccPanel *ap = p->acc[0];
-                rider.partial = ap->partial.as<double>();
-                rider.z = ap->z.as<double>();
-                rider.H = ap->nrow;
-                rider.n_wg = ap->n_wg;
+            PanelRider rider = {};
+            rider.first = pn->groups;
+            for (int q = 0; q < accgroups::MAX_GROUPS; q++) rider.start[q] = INT32_MAX;
+            int64_t rider_wgs = 0;
+            // (tier 0 is one launch: its groups, side by side, ride one behind the other)
+            if (PANEL_T1 / WAVE == 4 && do_heavy && !p->acc.empty() && (size_t)p->acc[0]->launch_groups == p->acc.size() &&
+                p->acc.size() <= (size_t)accgroups::MAX_GROUPS && p->acc[0]->z.p) {
+                for (size_t q = 0; q < p->acc.size(); q++) {
+                    AccPanel *ap = p->acc[q];
+                    rider.partial[q] = ap->partial.as<double>();
+                    rider.z[q] = ap->z.as<double>();
+                    rider.H[q] = ap->nrow;
+                    rider.n_wg[q] = ap->n_wg;
+                    rider.start[q] = (int32_t)rider_wgs;
+                    rider_wgs += ceil_div(ap->nrow, WAVE);
+                }
                 t0_rides = true;
             }
-            const unsigned grid = (unsigned)(pn->groups + (t0_rides ? ceil_div(rider.H, WAVE) : 0));
+            const unsigned grid = (unsigned)(pn->groups + rider_wgs);
             if (pn->p64) spmv_panel_kernel<int64_t, PANEL_T1, R32, XT><<<grid, PANEL_T1, 0, s>>>(PANEL_ARGS(int64_t));
             else spmv_panel_kernel<int32_t, PANEL_T1, R32, XT><<<grid, PANEL_T1, 0, s>>>(PANEL_ARGS(int32_t));
 #undef PANEL_ARGS
@@ -1525,15 +1578,16 @@ static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipSt
 #undef MERGE_ARGS_FULL
         }
         if (do_heavy && p->n_heavy && !p->acc.empty() && t0_rides) {
-            AccPanel *ap = p->acc[0];
-            if (epi.n == 6) CSRK_TRY(flush_epi());
-            EpiJob J = {};
-            J.kind = 2;
-            J.blocks = (int32_t)ceil_div(ap->nrow, EPI_THREADS);
-            J.partial = ap->z.as<double>();
-            J.row_list = ap->row_list.as<int32_t>();
-            J.H = ap->nrow;
-            epi.j[epi.n++] = J;
+            for (AccPanel *ap : p->acc) {
+                if (epi.n == 6) CSRK_TRY(flush_epi());
+                EpiJob J = {};
+                J.kind = 2;
+                J.blocks = (int32_t)ceil_div(ap->nrow, EPI_THREADS);
+                J.partial = ap->z.as<double>();
+                J.row_list = ap->row_list.as<int32_t>();
+                J.H = ap->nrow;
+                epi.j[epi.n++] = J;
+            }
         } else if (do_heavy && p->n_heavy && !p->acc.empty())
             for (AccPanel *ap : p->acc)
                 CSRK_TRY(add_red(ap->partial.as<double>(), ap->row_list.as<int32_t>(), ap->nrow, ap->n_wg, 4, nullptr, nullptr, nullptr));
@@ -1899,8 +1953,10 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
     CSRK_TRY(get_plan(m, nullptr, &p));
     const Panel &t1 = p->tier1;
     // tier 0: [4] tiles, [5] column blocks, [7] block width, [9] rows, [10] entries, [18] 1 (accumulator form)
-    int64_t a_tiles = 0, a_rows = 0, a_nnz = 0, a_nb = 0;
+    // (sums over the tier's groups; every group has the same column blocks)
+    int64_t a_tiles = 0, a_rows = 0, a_nnz = 0, a_nb = 0, a_wgs = 0;
     for (const AccPanel *ap : p->acc) {
+        a_wgs += ap->n_wg;
         a_tiles += ap->tiles;
         a_rows += ap->nrow;
         a_nnz += ap->nnz;
@@ -1920,7 +1976,7 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
                            p->n_hot, (int64_t)(p->hot_cover * 1e6), af ? 1 : 0, p->hot_slots,
                            p->ls.on ? 1 : 0, p->ls.n_tiles, p->ls.n_runs, p->ls.grid, p->ls.n_cold, plan_bytes,
                            p->ls.round_start.p ? p->ls.stage_tiles : 0,
-                           af ? (int64_t)p->acc[0]->n_wg : 0, 0, part[0], part[1], part[2], part[3], part[4]};
+                           a_wgs, 0, part[0], part[1], part[2], part[3], part[4]};
     for (int i = 0; i < n && i < 34; i++) out[i] = v[i];
     // the light stream's form (launch_spmv picks the kernel by these): [34] dense layout, [35] 3-byte index words, [36] pack
     // slots read from LDS (n_lds as launched), [37] rounds in all and [38] the most one workgroup walks -- staged rounds, or the

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "wave.h"
 #include "fix56.h"
+#include "acc_groups.h"
 
 #include <vector>
 
@@ -76,6 +77,12 @@ struct AccSeg {
 // Tier 0 in accumulator form: one group of <= ACC_MAXROWS heavy rows (see "long rows, accumulator form")
 struct AccPanel {
     int32_t nrow = 0, nb = 0, n_wg = 0;
+    // Groups side by side: the first group of a launch says how many groups the launch serves (`launch_groups`, this one and
+    // the next ones of SpmvPlan::acc; 0 in those) and with how many blocks; wg_map[block] = group << 16 | workgroup
+    // (accgroups::place_wgs; empty for a launch of one group, whose block b is workgroup b).  The groups of one launch
+    // hold values of one form (f32 / fix56).
+    int32_t launch_groups = 1, launch_wgs = 0;
+    DevBuf wg_map;
     int64_t tiles = 0, nnz = 0, n_segs = 0;
     size_t lds = 0;
     DevBuf row_list, vals, idx, tile_row0, segs, wg_seg, partial;      // idx: 16-bit words (column, row step)
@@ -148,6 +155,7 @@ struct SpmvPlan {
     std::vector<int32_t> t1_rows;         // tier-1 rows (ascending) and their entries: build_tiers
     int64_t t1_nnz = 0;
     std::vector<AccPanel *> acc;          // tier 0: accumulator form, groups of <= ACC_MAXROWS rows
+    int acc_groups = 1;                   // ... of which up to this many run side by side in one launch (build_heavy_split)
     std::vector<int32_t> t0_rows;         // tier-0 rows (ascending) and their lengths
     std::vector<int64_t> t0_lens;
     // vector
@@ -268,6 +276,12 @@ struct PanelGroup {
 //     bitwise reproducible, although ds_add_f64 is used for the adds.
 //   * At the end the workgroup stores its accumulators (H * 8 B) and the ordered reduce (spmv_epilogue_kernel, or the rider of tier 1's launch: PanelRider) sums the
 //     workgroups' partials in workgroup order into y.
+//   * Groups side by side (acc_groups.h): LDS holds ACC_MAXROWS accumulators, so a tier of more rows is several groups.  Up to
+//     accgroups::MAX_GROUPS of them share ONE launch: the rows are dealt to the groups round-robin by length rank (equal
+//     entries per column block: the groups advance at the same pace), the CUs are split between the groups, every group
+//     keeps its own stream, segment tables and rows of partials (sum of n_wg * H * 8 B as for one group), and the
+//     workgroups that serve the same column range in different groups sit on one XCD, where the second finds the
+//     windows the first pulled into L2.  A workgroup touches its own group's arrays only: no workgroup waits for another.
 // HBM traffic: 12 B per entry + one 32 KiB window per segment + n_wg * H * 8 B of partials (14 MB on the
 // headline matrix) -- against 12 B + 20 B per pair + windows for the pair form.
 constexpr int ACC_CB = 4096;
@@ -275,6 +289,8 @@ constexpr int ACC_K = 8;                      // consecutive entries per lane
 constexpr int ACC_TILE = WAVE * ACC_K;        // 512
 constexpr int ACC_MAXROWS = 15936;            // heavy rows per group: 124.5 KiB of accumulators + 32 KiB window + 3 KiB of head slots <= 160 KiB
 constexpr int ACC_FLOOR = 128;                // tier 0 is never extended to rows shorter than this (512 before the 10-B stream: a rank of an 8-way split ran 0.129 ms, 0.119 with 128)
+constexpr int ACC_GROUPS_DEFAULT = 2;         // groups side by side in one launch at most, where they pay (accgroups::choose_groups; CSRK_ACC_GROUPS forces a number; measured on the headline matrix, 1 / 2 / 3: 0.4958 / 0.4876 / 0.4938 ms)
+static_assert(accgroups::TILE_ENTRIES == ACC_TILE, "acc_groups.h counts the streams' tiles");
 constexpr int ACC_SEG_TILES = 256;            // head slots per segment
 constexpr int ACC_THREADS = 1024;
 // index word of the accumulator stream, 16 bits: column - block start in the low 13 (ACC_CB = the zero slot of the
@@ -285,6 +301,21 @@ constexpr int ACC_THREADS = 1024;
 constexpr int ACC_ROW_SHIFT = 13;
 constexpr uint32_t ACC_COL_MASK = (1u << ACC_ROW_SHIFT) - 1;
 constexpr int ACC_MAXSTEP = 7;
+
+// what one launch of the accumulator kernel is given, by value: the arrays of each of its groups and the blocks' map
+struct AccGroupArgs {
+    const void *vals;
+    const uint16_t *idx;
+    const int32_t *tile_row0;
+    const AccSeg *segs;
+    const int32_t *wg_seg;
+    double *partial;      // [n_wg][H]: this group's workgroups only
+    int32_t H, n_wg, fx_g, pad_;
+};
+struct AccLaunchArgs {
+    AccGroupArgs g[accgroups::MAX_GROUPS];
+    const uint32_t *wg_map;      // nullptr: one group, block b is its workgroup b
+};
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));

@@ -1022,10 +1022,14 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
 
 // Build one accumulator-form group: the listed heavy rows (<= ACC_MAXROWS, ascending) as a tiled,
 // column-block-major (value, packed index) stream plus the persistent workgroups' segment lists.
+// wg_want: the group's workgroups when it shares its launch with other groups (0: one per CU); allow_fix56 = false: the
+// raw stream whatever the values (another group of the launch could not be packed).
 template <class P, int VT>
 static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const int64_t *lens, int32_t n, int64_t nnz_rows,
-                           hipStream_t s)
+                           hipStream_t s, int32_t wg_want = 0, bool allow_fix56 = true)
 {
+    ap->fix56 = false;
+    ap->fx_g = 0;
     const P *rp = (const P *)m->d_rowptrs;
     const int32_t nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB);
     PlanTrace tr;
@@ -1074,7 +1078,7 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     // segments
     int cus = 0;
     CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    int64_t n_wg = cus > 0 ? cus : 256;
+    int64_t n_wg = wg_want > 0 ? wg_want : cus > 0 ? cus : 256;
     if (n_wg > n_tiles) n_wg = n_tiles;
     if (n_wg < 1) n_wg = 1;
     std::vector<int64_t> wg_t0((size_t)n_wg + 1);
@@ -1091,7 +1095,7 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     // the whole group: the grid test over its values, and CSRK_SPMV_FIX56=0 forbids the form (tests, measurements)
     DevBuf fx;      // int32[4]: the grid test's bad flag, lowest and highest set bit; the verification's mismatch flag
     CSRK_TRY(fx.alloc(16));
-    if (VT == CSRK_VAL_F64 && n > 0) {
+    if (VT == CSRK_VAL_F64 && n > 0 && allow_fix56) {
         const char *env = getenv("CSRK_SPMV_FIX56");
         if (!(env && env[0] == '0')) {
             int32_t h[4] = {0, INT32_MAX, INT32_MIN, 0};
@@ -1185,8 +1189,28 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     ap->tiles = n_tiles;
     ap->nnz = nnz_rows;
     ap->n_segs = (int64_t)segs.size();
+    if (tr.on)
+        fprintf(stderr, "[csrk plan]   tier 0 group: rows %d entries %lld workgroups %lld tiles %lld, %.1f per segment%s\n", n,
+                (long long)nnz_rows, (long long)n_wg, (long long)n_tiles, segs.empty() ? 0.0 : (double)n_tiles / (double)segs.size(),
+                ap->fix56 ? " (fix56)" : "");
     tr.lap("  tier 0: segments");
     return CSRK_OK;
+}
+
+// Tier 0's groups, read when a plan is built: CSRK_ACC_GROUPS = groups that share one launch of the accumulator kernel
+// (1 .. accgroups::MAX_GROUPS); CSRK_ACC_GROUP_ROWS = rows a group holds (<= ACC_MAXROWS; a test hook: small matrices
+// then fill several groups).
+static int acc_groups_knob()
+{
+    const char *e = getenv("CSRK_ACC_GROUPS");
+    const int g = e ? atoi(e) : ACC_GROUPS_DEFAULT;
+    return g < 1 ? 1 : g > accgroups::MAX_GROUPS ? accgroups::MAX_GROUPS : g;
+}
+static int32_t acc_group_rows_knob()
+{
+    const char *e = getenv("CSRK_ACC_GROUP_ROWS");
+    const int r = e ? atoi(e) : ACC_MAXROWS;
+    return r < 1 || r > ACC_MAXROWS ? ACC_MAXROWS : r;
 }
 
 // Cut the long rows out of the merge path and build their panel tiers.
@@ -1257,11 +1281,24 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
     // tier 0: accumulator form (groups of <= ACC_MAXROWS rows).  The accumulator form costs 1.8 ps per entry against 4.8 for tier 1 (measured, headline matrix), and
     // one group holds up to ACC_MAXROWS rows at no extra window traffic: when fewer rows than that reach
     // HEAVY_MIN, tier 0 is extended downwards to the ACC_MAXROWS longest rows (not below ACC_FLOOR).
+    // With G groups side by side in one launch (build_acc_groups) the tier holds G times as many rows.  G is what
+    // CSRK_ACC_GROUPS says, else as many groups (ACC_GROUPS_DEFAULT at most) as keep the segments long enough to pay
+    // (accgroups::choose_groups).
+    p->acc_groups = acc_groups_knob();
+    if (!getenv("CSRK_ACC_GROUPS")) {
+        int cus = 0;
+        CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+        const bool extend = tier1 && !getenv("CSRK_HEAVY_MIN");
+        p->acc_groups = accgroups::choose_groups(lens.data(), n_cut, ACC_GROUPS_DEFAULT, acc_group_rows_knob(),
+                                                 extend ? (int64_t)std::max(ACC_FLOOR, cut_min) : (int64_t)HEAVY_MIN,
+                                                 ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB), cus > 0 ? cus : 256);
+    }
+    const int64_t t0_cap = (int64_t)p->acc_groups * acc_group_rows_knob();
     if (tier1 && !getenv("CSRK_HEAVY_MIN")) {
         int64_t n_min = 0;
         for (int32_t c = 0; c < n_cut; c++) n_min += lens[c] >= HEAVY_MIN;
-        if (n_min < ACC_MAXROWS && n_cut > n_min) {
-            const size_t kth = (size_t)(n_cut < ACC_MAXROWS ? n_cut : ACC_MAXROWS) - 1;
+        if (n_min < t0_cap && n_cut > n_min) {
+            const size_t kth = (size_t)(n_cut < t0_cap ? n_cut : t0_cap) - 1;
             // the kth longest row's length: a histogram of the lengths below 2^16 decides it (nth_element over 10^5 rows was
             // 0.4 ms of the plan), unless the kth row is longer than that
             int64_t thr = -1;
@@ -1287,7 +1324,7 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
             // rows tied with the kth must not push the group over its capacity
             int64_t n_ge = 0;
             for (int32_t c = 0; c < n_cut; c++) n_ge += lens[c] >= thr;
-            if (n_ge > ACC_MAXROWS) thr++;
+            if (n_ge > t0_cap) thr++;
             thr = thr < ACC_FLOOR ? ACC_FLOOR : thr;
             if (thr < HEAVY_MIN) HEAVY_MIN = (int)thr;
         }
@@ -1323,25 +1360,75 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
     return CSRK_OK;
 }
 
+// Tier 0: deal its rows to groups (accgroups::deal_rows) and build them.  The groups of one launch split the CUs between
+// them, hold values of one form, and their workgroups are placed so that those of one column range share an XCD
+// (accgroups::place_wgs).  One group in a launch is built as it always was: a workgroup per CU, no map.
+template <class P, int VT>
+static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
+{
+    const std::vector<int32_t> &r0 = p->t0_rows;
+    const std::vector<int64_t> &len0 = p->t0_lens;
+    if (r0.empty()) return CSRK_OK;
+    const accgroups::Deal deal = accgroups::deal_rows(len0.data(), (int32_t)r0.size(), p->acc_groups, acc_group_rows_knob());
+    int cus = 0;
+    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    if (cus <= 0) cus = 256;
+    std::vector<int32_t> rows;
+    std::vector<int64_t> lens;
+    for (size_t j = 0; j + 1 < deal.first.size(); j++) {
+        const int k0 = deal.first[j], gb = deal.first[j + 1] - k0;
+        const size_t a0 = p->acc.size();
+        auto build = [&](int g, bool allow_fix56) -> int {
+            const std::vector<int32_t> &pos = deal.groups[(size_t)(k0 + g)];
+            rows.resize(pos.size());
+            lens.resize(pos.size());
+            int64_t gn = 0;
+            for (size_t i = 0; i < pos.size(); i++) {
+                rows[i] = r0[(size_t)pos[i]];
+                lens[i] = len0[(size_t)pos[i]];
+                gn += lens[i];
+            }
+            return build_acc_panel<P, VT>(m, p->acc[a0 + (size_t)g], rows.data(), lens.data(), (int32_t)pos.size(), gn, s,
+                                          gb > 1 ? accgroups::group_wgs(cus, gb, g) : 0, allow_fix56);
+        };
+        bool any_raw = false;
+        for (int g = 0; g < gb; g++) {
+            AccPanel *ap = new (std::nothrow) AccPanel();
+            CSRK_REQUIRE(ap, "out of host memory");
+            p->acc.push_back(ap);
+            CSRK_TRY(build(g, true));
+            any_raw = any_raw || !ap->fix56;
+        }
+        AccPanel *head = p->acc[a0];
+        if (gb == 1) continue;
+        // one kernel serves the launch: its groups hold one form of values
+        for (int g = 0; g < gb; g++)
+            if (any_raw && p->acc[a0 + (size_t)g]->fix56) CSRK_TRY(build(g, false));
+        int32_t n_wg[accgroups::MAX_GROUPS];
+        for (int g = 0; g < gb; g++) {
+            n_wg[g] = p->acc[a0 + (size_t)g]->n_wg;
+            p->acc[a0 + (size_t)g]->launch_groups = 0;
+        }
+        const std::vector<uint32_t> map = accgroups::place_wgs(n_wg, gb);
+        head->launch_groups = gb;
+        head->launch_wgs = (int32_t)map.size();
+        CSRK_TRY(head->wg_map.alloc(map.size() * 4));
+        CSRK_TRY(stage_h2d(head->wg_map.p, map.data(), map.size() * 4, s));
+        CSRK_HIP(hipStreamSynchronize(s));     // `map` is a host temporary of an async copy
+    }
+    return CSRK_OK;
+}
+
 // Build the tiers of the rows build_heavy_split cut out.
 template <class P>
 static int build_tiers(Matrix *m, SpmvPlan *p, hipStream_t s)
 {
     if (!p->n_heavy) return CSRK_OK;
-    const std::vector<int32_t> &r0 = p->t0_rows, &r1 = p->t1_rows;
-    const std::vector<int64_t> &len0 = p->t0_lens;
+    const std::vector<int32_t> &r1 = p->t1_rows;
     const int64_t nnz1 = p->t1_nnz;
 #define BUILD(VT)                                                                                                  \
     do {                                                                                                           \
-        for (size_t g0 = 0; g0 < r0.size(); g0 += ACC_MAXROWS) {                                                   \
-            const size_t g1 = g0 + ACC_MAXROWS < r0.size() ? g0 + ACC_MAXROWS : r0.size();                         \
-            int64_t gn = 0;                                                                                        \
-            for (size_t c = g0; c < g1; c++) gn += len0[c];                                                        \
-            AccPanel *ap = new (std::nothrow) AccPanel();                                                          \
-            CSRK_REQUIRE(ap, "out of host memory");                                                                \
-            p->acc.push_back(ap);                                                                                  \
-            CSRK_TRY((build_acc_panel<P, VT>(m, ap, r0.data() + g0, len0.data() + g0, (int32_t)(g1 - g0), gn, s)));  \
-        }                                                                                                          \
+        CSRK_TRY((build_acc_groups<P, VT>(m, p, s)));                                                              \
         if (!r1.empty()) CSRK_TRY((build_panel<P, VT>(m, &p->tier1, r1, nnz1, PANEL_CB1, 1, true, s)));            \
     } while (0)
     if (m->val_type == CSRK_VAL_F64) BUILD(CSRK_VAL_F64);

@@ -104,6 +104,11 @@ SIGNATURES = {
     'csrk_als_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, _vp, _i64, _vp,
                                     _vp]),
     'csrk_als_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_als_rows_cg': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, C.c_double, _i32,
+                                C.c_double, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'csrk_als_rows_cg_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, C.c_double, _i32,
+                                       C.c_double, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    'csrk_als_cg_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_topk_scores': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp, _i64,
                                 _vp]),
     'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,

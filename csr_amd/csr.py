@@ -419,6 +419,33 @@ class CSR:
                              f'{rb + int(bad[0])}, at pivot {int(info[bad[0]]) - 1} (return_info=True returns the codes)')
         return U
 
+    def als_rows_cg(self, V, *, x0=None, steps=3, weighted=False, rhs='values', base=None, reg=0.0, reg_per_entry=0.0, rows=None,
+                    tol=0.0, return_info=False):
+        """
+        One half-step of alternating least squares by conjugate gradient, float64 [n, k]: for each row i of rows =
+        (begin, end) (None: all rows) at most `steps` CG steps, started from x0's row (float64 [n, k], usually the previous
+        sweep's factors; None: from zero), on
+            (base + sum_j w_ij V[j, :]^T V[j, :] + (reg + reg_per_entry * n_i) * I) u_i = sum_j c_ij V[j, :]
+        with w, c, rhs and base as in als_rows.  The k x k block is never formed: a step is one pass over the row's V rows
+        and, with a base, one k x k matrix-vector product, so the cost grows with k n_i (+ k^2), not k^2 n_i + k^3.  A few
+        warm-started steps per sweep are the usual solver of implicit-feedback ALS; steps = 2 k from zero approaches
+        als_rows' solution.  tol is a residual 2-norm: a row stops once its residual is no longer above it.  Of base the
+        lower triangle is read and mirrored, as als_rows reads it, so both solvers see the same matrix.  Every output is
+        a fixed chain of fused multiply-adds (include/csrk.h, csrk_als_rows_cg): the same bits whatever the launch.
+        With return_info=True (U, resid, taken) comes back: the squared residual of the recurrence at each row's stop and
+        the steps it made.  Not a reference entry point.
+        """
+        K, fn = self._ext('als_rows_cg')
+        _, _, _, _, rb, re_, base, _, lam, lam_n, steps, _, x0 = K.als_cg_args(self, V, rhs, base, reg, reg_per_entry, rows, steps, x0,
+                                                                               tol)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        if base is not None:
+            base = np.tril(base) + np.tril(base, -1).T
+        with releasing(K.to_handle(self), K) as h:
+            U, resid, taken = fn(h, V, weighted, rhs, base, lam, lam_n, (rb, re_), steps, x0, tol)
+        return (U, resid, taken) if return_info else U
+
     def topk_rows(self, k, *, min_value=None, order='descending'):
         """
         Each row's k largest entries that are not below min_value (None: no threshold) as a new CSR of the same shape:

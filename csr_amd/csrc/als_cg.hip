@@ -1,0 +1,440 @@
+// The ALS half-step by conjugate gradient for libcsrk on gfx950: per row of a CSR matrix, a fixed number of CG steps on the
+// row's normal equations without ever forming the k x k block (include/csrk.h, rule C).
+//     csrk_als_rows_cg    per row i: M_i = base + sum_e w_e v_e v_e^T + (lam + lam_n n_i) I is applied, never built:
+//                         M y = base y + rho y + sum_e v_e (w_e (v_e . y)), one pass over the row's V rows per product
+// Where csrk_als_rows pays n k^2 / 2 fused multiply-adds to build the block and k^3 / 6 to factorise it, a step here is a
+// dot and an axpy per entry (4 k flops) plus, with a base, one k x k matrix-vector product.
+//
+// Work split.  ONE 16-LANE TEAM (one DPP row) PER ROW OF THE MATRIX, at every k: four rows per wavefront, sixteen per
+// workgroup.  Lane l owns the columns of csrk_sddmm's partial l (in each 64-column chunk: float64 2 l, 2 l + 1, 32 + 2 l,
+// 33 + 2 l; float32 4 l .. 4 l + 3), so a V row arrives in 16-B pieces, each load instruction of a team one contiguous
+// 256-B span, and x, r, p, q and b live in registers: 4 doubles each per chunk and lane, 8 at k = 128.  A DOT is the
+// lane's fma chain over its columns and four DPP adds; the adds form a butterfly (lane ^ 1, ^ 2, then the half-row and
+// row mirrors), so EVERY lane ends with the sum in rule C2's tree shape -- floating-point addition commutes, so the lanes
+// agree bit for bit (NaN payloads apart) -- and no broadcast follows.  CG_E entries' V rows are loaded, and their dots
+// taken, before the first is used; only the one-fma-per-entry chain into q_t is serial.  No LDS in the entry loop.
+//
+// base (k x k, read as stored: element (t, u) is base[u k + t]) is streamed per team, row u in the same 16-B pieces (the
+// sixteen teams of a workgroup walk it in near step: the CU's vector cache serves most of it), and y_u is read from k
+// doubles of LDS per team that the team published just before: teams are parts of one wavefront, so the publication needs
+// no workgroup barrier.  That is the only LDS: 16 KB per workgroup at k = 128.
+//
+// Long rows.  A row is walked by its one team, CG_E entries per round trip, steps + 1 times (steps + 2 with an x0): a
+// 250 000-entry row is the launch's tail, and on a power-law matrix most of its time (DESIGN.md section 7d has the
+// figures).  csrk_als_rows has the same tail; a long-row class is not built here.
+//
+// Divergence.  The teams of a wavefront have rows of different lengths and stop after different numbers of steps: every
+// loop is team-uniform, and nothing crosses a team (the DPP controls stay inside a row of 16 lanes).
+#include "common.h"
+#include "panel.h"
+#include "wave.h"
+
+namespace csrk {
+
+constexpr int CG_G = 16;                 // lanes per team (one DPP row)
+constexpr int CG_THREADS = 256;
+constexpr int CG_TEAMS = CG_THREADS / CG_G;
+constexpr int CG_E = 4;                  // entries in flight per team and step of the entry loop
+constexpr int CG_K_MAX = 128;            // two chunks of 64 columns (csrk_als_limits' value)
+
+// dpp_ctrl encodings (CDNA ISA): quad_perm [1, 0, 3, 2] and [2, 3, 0, 1], lanes 7 - l of a half row, 15 - l of a row
+constexpr int DPP_QUAD_X1 = 0xB1, DPP_QUAD_X2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141, DPP_ROW_MIRROR = 0x140;
+
+// Element q (0..3) of lane `sub` in a 64-column chunk: csrk_sddmm's ownership, 16-B pieces of PIECE elements.
+template <class T>
+__device__ __forceinline__ int cg_off(int sub, int q)
+{
+    constexpr int PIECE = 16 / (int)sizeof(T);
+    return (q / PIECE) * (CG_G * PIECE) + sub * PIECE + q % PIECE;
+}
+
+typedef double cg_d2 __attribute__((ext_vector_type(2)));
+typedef float cg_f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void cg_piece(const double *p, double *d)
+{
+    const cg_d2 a = *(const cg_d2 *)p;
+    d[0] = a.x, d[1] = a.y;
+}
+__device__ __forceinline__ void cg_piece(const float *p, float *d)
+{
+    const cg_f4 a = *(const cg_f4 *)p;
+    d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w;
+}
+
+// the lane's four elements of one chunk of a row (p = the chunk's first column; kk = columns left from it); columns at or
+// past k read as 0 and are never used.  WIDE: 16-B loads for whole pieces (aligned by the caller).
+template <class T, bool WIDE>
+__device__ __forceinline__ void cg_load4(const T *__restrict__ p, int sub, int kk, T d[4])
+{
+    constexpr int PIECE = 16 / (int)sizeof(T);
+#pragma unroll
+    for (int q0 = 0; q0 < 4; q0 += PIECE) {
+        const int o = cg_off<T>(sub, q0);
+        if (WIDE && o + PIECE <= kk) {
+            cg_piece(p + o, d + q0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < PIECE; i++) d[q0 + i] = o + i < kk ? p[o + i] : (T)0;
+        }
+    }
+}
+
+// rule C2's tree, in every lane of the team
+__device__ __forceinline__ double cg_team_sum(double s)
+{
+    s = __dadd_rn(s, dpp_f64<DPP_QUAD_X1>(0.0, s));
+    s = __dadd_rn(s, dpp_f64<DPP_QUAD_X2>(0.0, s));
+    s = __dadd_rn(s, dpp_f64<DPP_ROW_HALF_MIRROR>(0.0, s));
+    s = __dadd_rn(s, dpp_f64<DPP_ROW_MIRROR>(0.0, s));
+    return s;
+}
+
+// rule C2: DOT(a, b); OFFT is the panel type (it fixes which columns the lane owns)
+template <class OFFT, int NCH, class A>
+__device__ __forceinline__ double cg_dot(const A (&a)[NCH][4], const double (&b)[NCH][4], int sub, int k)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (64 * c + cg_off<OFFT>(sub, q) < k) s = __builtin_fma((double)a[c][q], b[c][q], s);
+    return cg_team_sum(s);
+}
+
+// within one wavefront LDS operations complete in issue order: order the compiler and the counters
+__device__ __forceinline__ void cg_team_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// rule C3's first two parts: q = base y (u ascending), then q_t = fma(rho, y_t, q_t).  ys: the team's k doubles of LDS.
+template <class OFFT, int NCH, bool BW>
+__device__ __forceinline__ void cg_base_part(const double *__restrict__ base, int k, int sub, const double (&y)[NCH][4],
+                                             double (&q)[NCH][4], double *ys)
+{
+    cg_team_sync();                                                         // (the last product's reads of ys are done)
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int t = 64 * c + cg_off<OFFT>(sub, i);
+            if (t < k) ys[t] = y[c][i];
+        }
+    cg_team_sync();
+#pragma unroll 2
+    for (int u = 0; u < k; u++) {
+        const double yu = ys[u];
+        double bv[NCH][4];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            if (sizeof(OFFT) == 8) {
+                cg_load4<double, BW>(base + (int64_t)u * k + 64 * c, sub, k - 64 * c, bv[c]);
+            } else {                                                        // float32 ownership: columns 4 l .. 4 l + 3, two pieces of doubles
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int o = 4 * sub + 2 * h;
+                    if (BW && o + 2 <= k - 64 * c) {
+                        cg_piece(base + (int64_t)u * k + 64 * c + o, bv[c] + 2 * h);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 2; i++) bv[c][2 * h + i] = o + i < k - 64 * c ? base[(int64_t)u * k + 64 * c + o + i] : 0.0;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) q[c][i] = __builtin_fma(bv[c][i], yu, q[c][i]);
+    }
+}
+
+// q = M y without the entries' part; the walk adds that (rule C3)
+template <class OFFT, int NCH>
+__device__ __forceinline__ void cg_head(const double *__restrict__ base, bool bwide, double rho, int k, int sub,
+                                        const double (&y)[NCH][4], double (&q)[NCH][4], double *ys)
+{
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) q[c][i] = 0.0;
+    if (base) {
+        if (bwide) cg_base_part<OFFT, NCH, true>(base, k, sub, y, q, ys);
+        else cg_base_part<OFFT, NCH, false>(base, k, sub, y, q, ys);
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) q[c][i] = __builtin_fma(rho, y[c][i], q[c][i]);
+}
+
+// One pass over the row's entries in storage order, CG_E at a time.  WANT_B: b_t = fma(c_e, v_e[t], b_t) (rule C4).
+// WANT_Q: d_e = DOT(v_e, y), g_e = round(w_e d_e) or d_e, q_t = fma(g_e, v_e[t], q_t) (rule C3's last part).
+template <class T, bool WIDE, int NCH, bool WANT_B, bool WANT_Q>
+__device__ __forceinline__ void cg_walk(int64_t e0, int64_t e1, const int32_t *__restrict__ ci, const void *__restrict__ vals, int vt,
+                                        bool scaled, int rhs_mode, const T *__restrict__ V, int64_t ldv, int k, int sub,
+                                        const double (&y)[NCH][4], double (&q)[NCH][4], double (&b)[NCH][4])
+{
+    if (e0 >= e1) return;
+    const int64_t last = e1 - 1;
+    int32_t coln[CG_E];                                                     // the next step's column indices
+#pragma unroll
+    for (int x = 0; x < CG_E; x++) coln[x] = ci[e0 + x < last ? e0 + x : last];
+    for (int64_t es = e0; es < e1; es += CG_E) {
+        T v[CG_E][NCH][4];
+        double wv[CG_E], d[CG_E];
+#pragma unroll
+        for (int x = 0; x < CG_E; x++)                                      // (past the row: its last entry again, unused)
+#pragma unroll
+            for (int c = 0; c < NCH; c++) cg_load4<T, WIDE>(V + (int64_t)coln[x] * ldv + 64 * c, sub, k - 64 * c, v[x][c]);
+#pragma unroll
+        for (int x = 0; x < CG_E; x++) {
+            const int64_t e = es + x < last ? es + x : last;
+            wv[x] = vals ? (vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e]) : 1.0;
+            const int64_t en = es + CG_E + x < last ? es + CG_E + x : last;
+            coln[x] = ci[en];
+        }
+        if (WANT_Q) {
+#pragma unroll
+            for (int x = 0; x < CG_E; x++) d[x] = cg_dot<T, NCH>(v[x], y, sub, k);
+        }
+#pragma unroll
+        for (int x = 0; x < CG_E; x++)
+            if (es + x < e1) {
+                if (WANT_Q) {
+                    const double g = scaled ? __dmul_rn(wv[x], d[x]) : d[x];
+#pragma unroll
+                    for (int c = 0; c < NCH; c++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) q[c][i] = __builtin_fma(g, (double)v[x][c][i], q[c][i]);
+                }
+                if (WANT_B) {
+                    const double cc = rhs_mode == CSRK_ALS_RHS_ONES ? 1.0 : (rhs_mode == CSRK_ALS_RHS_VALUES ? wv[x] : __dadd_rn(1.0, wv[x]));
+#pragma unroll
+                    for (int c = 0; c < NCH; c++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) b[c][i] = __builtin_fma(cc, (double)v[x][c][i], b[c][i]);
+                }
+            }
+    }
+}
+
+// NCH chunks of 64 columns: k <= 64 NCH.  vals: NULL when no value is wanted or none is stored (every one 1.0).
+template <class T, bool WIDE, int NCH>
+__global__ __launch_bounds__(CG_THREADS) void als_cg_kernel(const void *__restrict__ rp, int ptr64, const int32_t *__restrict__ ci,
+                                                            const void *__restrict__ vals, int vt, int scaled, int32_t row_begin,
+                                                            int32_t row_end, const T *__restrict__ V, int64_t ldv, int32_t k,
+                                                            int rhs_mode, const double *__restrict__ base, int bwide, double lam,
+                                                            double lam_n, int32_t steps, double tol2, const double *x0, int64_t ldx0,
+                                                            double *out, int64_t ldo, double *__restrict__ resid,
+                                                            int32_t *__restrict__ taken_out)
+{
+    __shared__ __attribute__((aligned(16))) double ysh[CG_TEAMS][NCH * 64];
+    const int team = threadIdx.x / CG_G, sub = threadIdx.x % CG_G;
+    const int64_t row = (int64_t)row_begin + (int64_t)blockIdx.x * CG_TEAMS + team;
+    if (row >= row_end) return;                                             // (a whole team; teams never meet at a barrier)
+    const int64_t e0 = load_ptr(rp, ptr64, row), e1 = load_ptr(rp, ptr64, row + 1);
+    const double rho = __builtin_fma(lam_n, (double)(e1 - e0), lam);
+    double *ys = ysh[team];
+
+    double x[NCH][4], r[NCH][4], p[NCH][4], q[NCH][4];
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[c][i] = 0.0, r[c][i] = 0.0, q[c][i] = 0.0;
+
+    // rules C4 and C5: b, and with an x0 the first product, in one walk; r holds b, then b - q
+    if (x0) {
+        const double *xr = x0 + (int64_t)(row - row_begin) * ldx0;
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int t = 64 * c + cg_off<T>(sub, i);
+                x[c][i] = t < k ? xr[t] : 0.0;
+            }
+        cg_head<T, NCH>(base, bwide != 0, rho, k, sub, x, q, ys);
+        cg_walk<T, WIDE, NCH, true, true>(e0, e1, ci, vals, vt, scaled != 0, rhs_mode, V, ldv, k, sub, x, q, r);
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) r[c][i] = __dsub_rn(r[c][i], q[c][i]);
+    } else {
+        cg_walk<T, WIDE, NCH, true, false>(e0, e1, ci, vals, vt, scaled != 0, rhs_mode, V, ldv, k, sub, x, q, r);
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) p[c][i] = r[c][i];
+    double rs = cg_dot<T, NCH>(r, r, sub, k);
+    int32_t taken = 0;
+
+    // rule C6
+    while (taken < steps && rs > tol2) {
+        cg_head<T, NCH>(base, bwide != 0, rho, k, sub, p, q, ys);
+        cg_walk<T, WIDE, NCH, false, true>(e0, e1, ci, vals, vt, scaled != 0, rhs_mode, V, ldv, k, sub, p, q, r);
+        const double pq = cg_dot<T, NCH>(p, q, sub, k);
+        const double alpha = __ddiv_rn(rs, pq);
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                x[c][i] = __builtin_fma(alpha, p[c][i], x[c][i]);
+                r[c][i] = __builtin_fma(-alpha, q[c][i], r[c][i]);
+            }
+        const double rn = cg_dot<T, NCH>(r, r, sub, k);
+        const double beta = __ddiv_rn(rn, rs);
+#pragma unroll
+        for (int c = 0; c < NCH; c++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) p[c][i] = __builtin_fma(beta, p[c][i], r[c][i]);
+        rs = rn;
+        taken++;
+    }
+
+    double *o = out + (int64_t)(row - row_begin) * ldo;
+#pragma unroll
+    for (int c = 0; c < NCH; c++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int t = 64 * c + cg_off<T>(sub, i);
+            if (t < k) o[t] = x[c][i];
+        }
+    if (sub == 0) {
+        if (resid) resid[row - row_begin] = rs;
+        if (taken_out) taken_out[row - row_begin] = taken;
+    }
+}
+
+// what can be refused without looking at the handle (the entries do, before they look: these need no device)
+static int cg_check_scalars(int32_t row_begin, int32_t row_end, int64_t ldv, int32_t k, int panel_type, int scale, int rhs_mode,
+                            int32_t steps, double tol2, bool has_x0, int64_t ldx0, int64_t ldo)
+{
+    CSRK_CHECK_K("", k);
+    CSRK_CHECK_ONE_PANEL(k, ldv);
+    CSRK_REQUIRE(ldo >= k, "bad output geometry k=%d ldo=%lld", k, (long long)ldo);
+    CSRK_CHECK_PANEL_TYPE("", panel_type);
+    CSRK_CHECK_SCALE(scale);
+    CSRK_REQUIRE(rhs_mode == CSRK_ALS_RHS_ONES || rhs_mode == CSRK_ALS_RHS_VALUES || rhs_mode == CSRK_ALS_RHS_ONE_PLUS,
+                 "rhs_mode must be CSRK_ALS_RHS_ONES, _VALUES or _ONE_PLUS, not %d", rhs_mode);
+    CSRK_REQUIRE(steps >= 0, "steps must not be negative (steps=%d)", steps);
+    CSRK_REQUIRE(tol2 >= 0.0, "tol2 must be a number that is not negative (tol2=%g)", tol2);      // (false for NaN)
+    CSRK_REQUIRE(!has_x0 || ldx0 >= k, "bad x0 geometry k=%d ldx0=%lld", k, (long long)ldx0);
+    CSRK_CHECK_ROW_ORDER("", row_begin, row_end);
+    if (k > CG_K_MAX) {
+        set_error("csrk_als_rows_cg: k=%d is above the largest supported k=%d (csrk_als_cg_limits)", k, CG_K_MAX);
+        return CSRK_ERR_UNSUPPORTED;
+    }
+    return CSRK_OK;
+}
+
+static int cg_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldv, int32_t k, int panel_type, int scale, int rhs_mode,
+                    int32_t steps, double tol2, bool has_x0, int64_t ldx0, int64_t ldo)
+{
+    CSRK_TRY(cg_check_scalars(row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, steps, tol2, has_x0, ldx0, ldo));
+    CSRK_CHECK_ROW_RANGE("", row_begin, row_end, m->nrows);
+    return CSRK_OK;
+}
+
+static int cg_device(Matrix *m, int32_t row_begin, int32_t row_end, const void *dV, int64_t ldv, int32_t k, int panel_type, int scale,
+                     int rhs_mode, const double *dbase, double lam, double lam_n, int32_t steps, double tol2, const double *dx0,
+                     int64_t ldx0, double *dout, int64_t ldo, double *dresid, int32_t *dtaken, hipStream_t s)
+{
+    CSRK_TRY(cg_check(m, row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, steps, tol2, dx0 != nullptr, ldx0, ldo));
+    if (row_begin == row_end) return CSRK_OK;
+    CSRK_REQUIRE(dout && (dV || m->nnz == 0), "V or out is NULL");
+    const size_t es = panel_es(panel_type);
+    CSRK_REQUIRE(((uintptr_t)dV % es) == 0 && ((uintptr_t)dout % 8) == 0 && ((uintptr_t)dbase % 8) == 0 && ((uintptr_t)dx0 % 8) == 0 &&
+                     ((uintptr_t)dresid % 8) == 0 && ((uintptr_t)dtaken % 4) == 0,
+                 "V, base, x0, out, resid or taken is not aligned to its element size");
+    mark_user_stream(m, s);
+    const bool wide = panel_16b(dV, ldv, es);      // a lane loads four columns at a time, as csrk_sddmm's do: no k term
+    const int bwide = dbase && panel_16b(dbase, k, 8);
+    const bool stored = m->val_type != CSRK_VAL_NONE;               // (a structure-only matrix: every value is 1.0)
+    const int scaled = scale && stored;
+    const void *vals = stored && (scaled || rhs_mode != CSRK_ALS_RHS_ONES) ? m->d_values : nullptr;
+    const int64_t n = (int64_t)row_end - row_begin;
+    const unsigned grid = (unsigned)ceil_div(n, CG_TEAMS);
+#define CG_GO(T, W, NCH)                                                                                                          \
+    als_cg_kernel<T, W, NCH><<<grid, CG_THREADS, 0, s>>>(m->d_rowptrs, m->ptr64, m->d_colinds, vals, m->val_type, scaled, row_begin, \
+                                                         row_end, (const T *)dV, ldv, k, rhs_mode, dbase, bwide, lam, lam_n, steps,  \
+                                                         tol2, dx0, ldx0, dout, ldo, dresid, dtaken)
+#define CG_NCH(T, W)                                                                                                              \
+    do {                                                                                                                          \
+        if (k <= 64) CG_GO(T, W, 1);                                                                                              \
+        else CG_GO(T, W, 2);                                                                                                      \
+    } while (0)
+    if (panel_type == CSRK_VAL_F64) {
+        if (wide) CG_NCH(double, true);
+        else CG_NCH(double, false);
+    } else {
+        if (wide) CG_NCH(float, true);
+        else CG_NCH(float, false);
+    }
+#undef CG_NCH
+#undef CG_GO
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+}  // namespace csrk
+
+using namespace csrk;
+
+extern "C" {
+
+int csrk_als_cg_limits(int64_t *out, int n)
+{
+    CSRK_REQUIRE(out && n >= 0, "csrk_als_cg_limits: out is NULL or n < 0");
+    const int64_t v[3] = {CG_K_MAX, CG_G, CG_E};
+    for (int i = 0; i < n && i < 3; i++) out[i] = v[i];
+    return CSRK_OK;
+}
+
+int csrk_als_rows_cg_device(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *d_V, int64_t ldv, int32_t k,
+                            int panel_type, int scale, int rhs_mode, const double *d_base, double lam, double lam_n, int32_t steps,
+                            double tol2, const double *d_x0, int64_t ldx0, double *d_out, int64_t ldo, double *d_resid,
+                            int32_t *d_taken, void *stream)
+{
+    CSRK_TRY(cg_check_scalars(row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, steps, tol2, d_x0 != nullptr, ldx0, ldo));
+    Matrix *m = from_handle(h);
+    if (!m) return CSRK_ERR_INVALID;
+    return cg_device(m, row_begin, row_end, d_V, ldv, k, panel_type, scale, rhs_mode, d_base, lam, lam_n, steps, tol2, d_x0, ldx0,
+                     d_out, ldo, d_resid, d_taken, (hipStream_t)stream);
+}
+
+int csrk_als_rows_cg(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *V, int64_t ldv, int32_t k, int panel_type,
+                     int scale, int rhs_mode, const double *base, double lam, double lam_n, int32_t steps, double tol2,
+                     const double *x0, int64_t ldx0, double *out, int64_t ldo, double *resid, int32_t *taken)
+{
+    CSRK_TRY(cg_check_scalars(row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, steps, tol2, x0 != nullptr, ldx0, ldo));
+    Matrix *m = from_handle(h);
+    if (!m) return CSRK_ERR_INVALID;
+    // argument checks first, with the caller's pointers (the device call below sees packed copies)
+    CSRK_TRY(cg_check(m, row_begin, row_end, ldv, k, panel_type, scale, rhs_mode, steps, tol2, x0 != nullptr, ldx0, ldo));
+    if (row_begin == row_end) return CSRK_OK;
+    CSRK_REQUIRE(out && (V || m->nnz == 0), "V or out is NULL");
+    const size_t n = (size_t)(row_end - row_begin);
+    DevBuf dV, dB, dX, dO, dR, dT;
+    CSRK_TRY(pack_panel(dV, V, ldv, k, panel_es(panel_type), m->ncols));
+    CSRK_TRY(dO.alloc(n * k * 8));
+    CSRK_TRY(dR.alloc(n * 8));
+    CSRK_TRY(dT.alloc(n * 4));
+    if (base) {
+        CSRK_TRY(dB.alloc((size_t)k * k * 8));
+        CSRK_HIP(hipMemcpy(dB.p, base, (size_t)k * k * 8, hipMemcpyHostToDevice));
+    }
+    if (x0) CSRK_TRY(pack_panel(dX, x0, ldx0, k, 8, (int64_t)n));
+    CSRK_TRY(cg_device(m, row_begin, row_end, dV.p, k, k, panel_type, scale, rhs_mode, base ? dB.as<double>() : nullptr, lam, lam_n,
+                       steps, tol2, x0 ? dX.as<double>() : nullptr, k, dO.as<double>(), k, dR.as<double>(), dT.as<int32_t>(), nullptr));
+    CSRK_TRY(unpack_panel(out, ldo, dO, k, 8, (int64_t)n));
+    if (resid) CSRK_HIP(hipMemcpy(resid, dR.p, n * 8, hipMemcpyDeviceToHost));
+    if (taken) CSRK_HIP(hipMemcpy(taken, dT.p, n * 4, hipMemcpyDeviceToHost));
+    return CSRK_OK;
+}
+
+}  // extern "C"

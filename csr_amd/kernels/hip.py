@@ -7,7 +7,7 @@ Protocol members (same names and meaning as csr/kernels/numba/__init__.py:13-67 
 csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_columns,
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
-center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, solve_blocks, topk_rows, combine, coalesce,
+center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, als_rows_cg, solve_blocks, topk_rows, combine, coalesce,
 is_canonical, topk_scores, topk_scores_for, rank_entries, knn_scores, knn_reach_index.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
@@ -932,6 +932,50 @@ def als_rows(h, V, scale=False, rhs='values', base=None, lam_n=0.0, rows=None):
     _call(lib.csrk_als_rows, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), rcode, ptr(base), lam_n, ptr(out), k,
           ptr(info))
     return out, info
+
+
+def als_cg_limits():
+    "(largest k, lanes of a row's team, entries a team has in flight per step of its entry loop)"
+    return _limits(lib.csrk_als_cg_limits, 3)
+
+
+def als_cg_args(h, V, rhs='values', base=None, lam=0.0, lam_n=0.0, rows=None, steps=3, x0=None, tol=0.0):
+    """
+    als_args' tuple (with the constant ridge lam before lam_n) + (steps, tol2, x0); ValueError for anything the library
+    would refuse as invalid.  tol is a residual 2-norm: the library takes its square.  No library call.
+    """
+    if not _is_real(lam):
+        raise ValueError(f'the ridge must be one real number, not {lam!r}')
+    V, ldv, k, code, rb, re_, base, rcode, lam_n = als_args(h, V, rhs, base, lam_n, rows)
+    if not _is_int(steps) or steps < 0 or steps > 2 ** 31 - 1:
+        raise ValueError(f'steps must be an integer that is not negative, not {steps!r}')
+    if not _is_real(tol) or not float(tol) >= 0.0:
+        raise ValueError(f'tol must be a real number that is not negative, not {tol!r}')
+    if x0 is not None:
+        x0 = np.asarray(x0)
+        if x0.dtype != np.float64 or x0.shape != (re_ - rb, k):
+            raise ValueError(f'x0 must be float64 of shape ({re_ - rb}, {k}), not {x0.dtype} of shape {x0.shape}')
+        x0 = np.ascontiguousarray(x0)
+    tol = float(tol)
+    return V, ldv, k, code, rb, re_, base, rcode, float(lam), lam_n, int(steps), tol * tol, x0
+
+
+def als_rows_cg(h, V, scale=False, rhs='values', base=None, lam=0.0, lam_n=0.0, rows=None, steps=3, x0=None, tol=0.0):
+    """
+    One ALS half-step by conjugate gradient: for each row i of rows = (begin, end) (None: all rows) at most `steps` CG steps
+    from x0's row (None: from zero) on als_rows' system with the ridge lam + lam_n n_i on the diagonal,
+        (base + sum_e w_e v_j v_j^T + (lam + lam_n n_i) I) u_i = sum_e c_e v_j
+    without forming the k x k block: (U float64 [end - begin, k], resid float64, taken int32).  A row stops early once the
+    squared residual of the recurrence is no longer above tol^2; resid is that squared residual at the stop and taken the
+    steps made.  base is read as stored, all of it (als_rows reads the lower triangle): pass a symmetric matrix.  Every
+    output is a fixed chain of fused multiply-adds (include/csrk.h, rule C).  Not a reference entry point.
+    """
+    V, ldv, k, code, rb, re_, base, rcode, lam, lam_n, steps, tol2, x0 = als_cg_args(h, V, rhs, base, lam, lam_n, rows, steps, x0, tol)
+    n = re_ - rb
+    out, resid, taken = _out((n, k), np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+    _call(lib.csrk_als_rows_cg, _live(h), rb, re_, ptr(V), ldv, k, code, int(bool(scale)), rcode, ptr(base), lam, lam_n, steps, tol2,
+          ptr(x0), k, ptr(out), k, ptr(resid), ptr(taken))
+    return out, resid, taken
 
 
 def topk_scores_limits():

@@ -426,6 +426,69 @@ CSRK_API int csrk_als_rows_device(csrk_handle_t h, int32_t row_begin, int32_t ro
 /* Diagnostics: the five limits above, in that order;  n <= 5.  No device is touched. */
 CSRK_API int csrk_als_limits(int64_t *out, int n);
 
+/* ---- the ALS half-step by conjugate gradient: no k x k block ---------------------------------------
+ * Not a reference entry point.  csrk_als_rows_cg runs at most `steps` conjugate-gradient steps per row on the system of
+ * csrk_als_rows, M_i x = b_i with M_i = base + sum_e w_e v_e v_e^T + rho_i I, warm-started from x0, WITHOUT forming M_i:
+ * a step is one pass over the row's V rows (a dot and an axpy per entry) and, with a base, one k x k matrix-vector
+ * product, where the exact route pays n_i k^2 / 2 to build the block and k^3 / 6 to factorise it.  The result is a
+ * function of the inputs, fixed below.  All arithmetic is float64; fma(a, b, c) is round(a b + c), one rounding.
+ *
+ * C. For row i of [row_begin, row_end), its entries e = (i, j_e) in storage order, n_i of them, v_e = row j_e of V
+ *    widened exactly to float64:
+ *   C1. Operands.  V, panel_type, scale, rhs_mode, ldv and ldo are csrk_als_rows'; w_e follows its scale rule (rule 1 of
+ *       csrk_gram_rows), c_e rule A3.  base is NULL or k x k float64, packed row-major, and it is read AS STORED, ALL OF
+ *       IT: the element used for (t, u) is base[u * k + t]; the caller passes a symmetric matrix.  (csrk_als_rows reads
+ *       the lower triangle only: a caller who filled just that must mirror it before calling this entry.)  lam and lam_n
+ *       are doubles; the diagonal term is rho_i = fma(lam_n, (double)n_i, lam).  steps >= 0; tol2 >= 0 and not NaN.  x0
+ *       is NULL or float64 with ldx0 >= k in elements: row i reads x0[(i - row_begin) * ldx0 + t].  resid (float64[n])
+ *       and taken (int32[n]), n = row_end - row_begin, may each be NULL.
+ *   C2. DOT(a, b) over k elements is csrk_sddmm's order for the call's panel type: 16 partials s_0 .. s_15 from +0.0;
+ *       element t belongs to partial l = (t mod 32) div 2 for float64 panels, l = (t mod 64) div 4 for float32 panels;
+ *       each partial takes its elements in ascending t, s_l = fma(a_t, b_t, s_l); then the balanced tree in index order,
+ *       (s_0 + s_1), (s_2 + s_3), ..., pairs of those, again, then the last two: every addition rounded on its own.
+ *   C3. MATVEC(y) -> q.  q_t starts at +0.0.  With a base, for u = 0 .. k-1 ascending: q_t = fma(base[u * k + t], y_u, q_t).
+ *       Then q_t = fma(rho_i, y_t, q_t).  Then for the entries in storage order: d_e = DOT(v_e, y); g_e = round(w_e d_e)
+ *       under scale = 1, else d_e; q_t = fma(g_e, v_e[t], q_t).
+ *   C4. Right-hand side.  b_t is rule A3's chain: from +0.0, b_t = fma(c_e, v_e[t], b_t) in storage order.
+ *   C5. Start.  x0 NULL: x = +0.0 and r = b; no product is formed.  Otherwise x = the x0 row, q = MATVEC(x),
+ *       r_t = round(b_t - q_t).  Then p = r, rs = DOT(r, r), taken = 0.
+ *   C6. Step.  At most `steps` times, and only while rs > tol2 is true (a NaN rs stops):
+ *           q = MATVEC(p);  pq = DOT(p, q);  alpha = round(rs / pq);
+ *           x_t = fma(alpha, p_t, x_t);  r_t = fma(-alpha, q_t, r_t);
+ *           rn = DOT(r, r);  beta = round(rn / rs);  p_t = fma(beta, p_t, r_t);  rs = rn;  taken += 1
+ *       Both divisions are correctly rounded.  No other special case: pq <= 0 or NaN goes through IEEE arithmetic.
+ *   C7. Output.  out[(i - row_begin) * ldo + t] = x_t (the other columns of out are not touched); resid[i - row_begin] =
+ *       rs, the squared 2-norm of the recurrence's residual at the stop; taken[i - row_begin] = taken.  d_x0 == d_out
+ *       with ldx0 == ldo is allowed (a row's x0 is read before its out is written, by the team that writes it); any other
+ *       overlap is undefined.
+ *   C8. A row's outputs depend only on its entries, the V rows they name, base, lam, lam_n, steps, tol2, its x0 row, k,
+ *       the panel type, scale and rhs_mode: not on the row range, the pointer width, ldv, ldx0, ldo, the alignment, the
+ *       load form, the stream, the launch geometry or repeated calls.  Parallelism is over rows and over elements t, never
+ *       inside a chain; no float atomics.  Unsorted and repeated columns are just more entries.  NaN and Inf reach only
+ *       the rows that reference them (a created NaN has its position specified, not its sign or payload).  An empty row
+ *       with x0 NULL gives x = +0.0, resid +0.0, taken 0.
+ *   C9. CSRK_ERR_INVALID: every refusal of csrk_als_rows (rule A7), steps < 0, tol2 < 0 or NaN, ldx0 < k with an x0, an
+ *       x0, resid or taken that is not aligned to its element size.  CSRK_ERR_UNSUPPORTED: k above csrk_als_cg_limits'
+ *       out[0].  What the scalars alone decide (everything but row_end > nrows, NULL pointers and alignment) is refused
+ *       before the handle is looked at.  row_begin == row_end: CSRK_OK, nothing launched.  A refused call writes nothing.  The device form
+ *       allocates nothing and never synchronises the host; h is not modified and keeps its plans.
+ *   C10. A hazard, not a special case.  With tol2 = 0 and steps far past convergence the residual walks into the
+ *       subnormals, where pq can reach 0 before rs does and IEEE gives Inf.  (k = 1, M = 12.75, b = 8 never reaches
+ *       rs = 0: after 5 steps rs = 1.7e-167.)  Callers who ask for many steps pass a tol2.
+ *   Limits (csrk_als_cg_limits): out[0] = the largest k (at least 128); [1] = the lanes of a row's team; [2] = the entries a
+ *   team has in flight per step of its entry loop;  n <= 3.  No device is touched.
+ * Host form: host pointers in and out (panels cross packed; synchronous). */
+CSRK_API int csrk_als_rows_cg(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *V, int64_t ldv, int32_t k,
+                              int panel_type, int scale, int rhs_mode, const double *base, double lam, double lam_n,
+                              int32_t steps, double tol2, const double *x0, int64_t ldx0, double *out, int64_t ldo,
+                              double *resid, int32_t *taken);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream). */
+CSRK_API int csrk_als_rows_cg_device(csrk_handle_t h, int32_t row_begin, int32_t row_end, const void *d_V, int64_t ldv,
+                                     int32_t k, int panel_type, int scale, int rhs_mode, const double *d_base, double lam,
+                                     double lam_n, int32_t steps, double tol2, const double *d_x0, int64_t ldx0,
+                                     double *d_out, int64_t ldo, double *d_resid, int32_t *d_taken, void *stream);
+CSRK_API int csrk_als_cg_limits(int64_t *out, int n);
+
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).
  * Bit-exact with the reference's stable counting sort: output rowptrs keep the input

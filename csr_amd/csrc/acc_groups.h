@@ -88,6 +88,21 @@ inline int choose_groups(const int64_t *lens, int32_t n, int g_max, int32_t cap,
     return 1;
 }
 
+// Whether a launch whose groups are packable takes the 8.5-byte entries (fix56.h, nib) instead of the 9-byte ones.  Both
+// decode exactly; the 8.5-byte form reads 256 B less per tile and spends a few more vector instructions per entry on the
+// nibble, the sign and the padding test.  The bytes are the kernel's time only where the stream is: a workgroup that walks
+// less than a tile per wavefront spends its time on the window fills, barriers and head folds of its segments, and the
+// smaller entry buys nothing there.  So without CSRK_SPMV_NIB (knob < 0) the form is taken when the launch's entries make
+// NIB_MIN_WG_TILES whole tiles per workgroup, one per wavefront of the sixteen; knob = 1 takes it whenever the groups are
+// packable, knob = 0 never.  (The headline matrix has about 1130 tiles per workgroup.)
+constexpr int64_t NIB_MIN_WG_TILES = 16;
+inline bool choose_nib(int knob, int64_t launch_entries, int32_t launch_wgs)
+{
+    if (knob >= 0) return knob != 0;
+    if (launch_wgs < 1) launch_wgs = 1;
+    return launch_entries >= 0 && launch_entries / TILE_ENTRIES >= NIB_MIN_WG_TILES * (int64_t)launch_wgs;
+}
+
 // workgroups of group g when `cus` compute units serve the gb groups of one launch: equal shares, the remainder to the
 // first groups, one at least
 inline int32_t group_wgs(int32_t cus, int gb, int g)

@@ -16,6 +16,8 @@
 //
 // The header compiles as plain C++ (the plan's host side, the host test) and as HIP device code (the product kernels,
 // the fill and verification kernels): both run the same routines.
+//
+// Namespace nib at the end: the same values in 6.5 bytes, with the sign moved into the stream's index word (8.5 B per entry).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -144,6 +146,93 @@ FIX56_HD double get(const unsigned char *tile, int e, int32_t g)
     const uint32_t w = (uint32_t)((const uint16_t *)(tile + MID_OFF))[e] | (uint32_t)tile[HI_OFF + e] << 16;
     return decode(lo, w, ebits_of(g), magic_of(g));
 }
+
+// nib: the same values in 6.5 bytes beside a 16-bit index word that carries their sign -- 8.5 B per entry of tier 0's stream
+// instead of 9.  The 56-bit form holds three bits that are always zero, and the stream's index word spends its 13th column
+// bit only on the window's zero slot (padding entries).  So per 512-entry tile:
+//     32-bit plane  M[31:0]    2048 B   as above (lo_slot)
+//     16-bit plane  M[47:32]   1024 B   as above
+//      4-bit plane  M[51:48]    256 B   a lane's eight nibbles in one dword: entry e in dword e / 8, bits 4 (e % 8) ..
+//     index word    {sign : 1, row step : 3, column in block : 12}, 1024 B, an array of its own
+// A packable set holds no -0.0, so "sign set, M = 0" is free: it marks a PADDING entry, which the reader sends to column
+// PAD_COL (the zero slot) whatever its column field says.  It decodes to -0.0, and -0.0 * 0.0 = -0.0 added to a run sum leaves
+// that sum's bits alone: a run sum starts at +0.0, +0.0 + -0.0 = +0.0 in round-to-nearest, and a sum of two doubles is -0.0
+// only when both are -- so no run sum is ever -0.0, and x + -0.0 = x for every other x.  (The raw stream's padding adds
+// +0.0 * 0.0 = +0.0, which likewise changes nothing: x + +0.0 = x unless x is -0.0.)
+namespace nib {
+
+constexpr int LO_BYTES = TILE * 4, MID_BYTES = TILE * 2, HI_BYTES = TILE / 2;
+constexpr int MID_OFF = LO_BYTES, HI_OFF = LO_BYTES + MID_BYTES;
+constexpr int TILE_BYTES = LO_BYTES + MID_BYTES + HI_BYTES;      // 3328: 6.5 B per entry, so tiles are addressed by byte offset
+constexpr int COL_BITS = 12, STEP_SHIFT = 12;
+constexpr uint32_t COL_MASK = (1u << COL_BITS) - 1, STEP_MASK = 7u, SIGN = 1u << 15;
+constexpr uint32_t PAD_COL = 1u << COL_BITS;                     // the column a padding entry reads: the window's zero slot
+constexpr uint64_t PAD_CODE = 1ull << 55;                        // encode()'s form of "sign set, M = 0"
+
+// a stream of such tiles: sizeof = 1, pointer arithmetic is in bytes
+struct Bytes {
+    unsigned char b;
+};
+
+// the index word of an entry whose value encodes as p (encode(), or PAD_CODE for a padding entry, whose column field is 0)
+FIX56_HD uint16_t index_word(uint64_t p, uint32_t col, uint32_t step)
+{
+    const bool pad = p == PAD_CODE;
+    return (uint16_t)((pad ? 0u : col & COL_MASK) | (step & STEP_MASK) << STEP_SHIFT | (uint32_t)(p >> 55) << 15);
+}
+// where entry e's nibble sits in the 4-bit plane
+FIX56_HD int hi_word(int e) { return e >> 3; }
+FIX56_HD int hi_shift(int e) { return (e & 7) * 4; }
+FIX56_HD uint32_t hi_of(uint64_t p) { return (uint32_t)(p >> 48) & 0xfu; }
+
+// a double from its two words and back, without a 64-bit integer in between (little-endian, like every target of this code)
+FIX56_HD double join(uint32_t hi, uint32_t lo)
+{
+    const uint32_t t[2] = {lo, hi};
+    double v;
+    memcpy(&v, t, 8);
+    return v;
+}
+FIX56_HD uint32_t high_of(double v)
+{
+    uint32_t t[2];
+    memcpy(t, &v, 8);
+    return t[1];
+}
+
+// The decode every reader uses.  lo = the 32-bit plane's word, hi = ebits | M[51:32] (the exponent field of 2^(52 + g) over the
+// nibble over the 16-bit plane's word: the high word of the double 2^(52 + g) + M * 2^g), word = the index word.  Returns the
+// value; col = the window slot to read (PAD_COL for a padding entry), step = the row step.
+FIX56_HD double entry(uint32_t lo, uint32_t hi, uint32_t word, double magic, uint32_t &col, uint32_t &step)
+{
+    // d = M * 2^g >= +0.0 (x - x is +0.0 in round-to-nearest): its sign bit is clear and the stored sign is or-ed in.  "Sign
+    // set, M = 0" then IS the double -0.0, which no packable set holds: one 64-bit compare finds a padding entry.
+    const double d = join(hi, lo) - magic;
+    const double a = join(high_of(d) | ((word << 16) & 0x80000000u), (uint32_t)bits_of(d));
+    col = bits_of(a) == 1ull << 63 ? PAD_COL : word & COL_MASK;
+    step = (word >> STEP_SHIFT) & STEP_MASK;
+    return a;
+}
+
+// store / fetch one entry of the value tile at `tile` and of the tile's 512 index words at `idx` (scalar forms: the host
+// test; the plan's fill kernel stores the planes the same way but ors the nibble in atomically, its lanes sharing dwords)
+FIX56_HD void put(unsigned char *tile, uint16_t *idx, int e, uint64_t p, uint32_t col, uint32_t step)
+{
+    ((uint32_t *)tile)[lo_slot(e)] = lo_of(p);
+    ((uint16_t *)(tile + MID_OFF))[e] = mid_of(p);
+    uint32_t *h = (uint32_t *)(tile + HI_OFF) + hi_word(e);
+    *h = (*h & ~(0xfu << hi_shift(e))) | hi_of(p) << hi_shift(e);
+    idx[e] = index_word(p, col, step);
+}
+FIX56_HD double get(const unsigned char *tile, const uint16_t *idx, int e, int32_t g, uint32_t &col, uint32_t &step)
+{
+    const uint32_t lo = ((const uint32_t *)tile)[lo_slot(e)];
+    const uint32_t nibble = (((const uint32_t *)(tile + HI_OFF))[hi_word(e)] >> hi_shift(e)) & 0xfu;
+    const uint32_t w = (uint32_t)((const uint16_t *)(tile + MID_OFF))[e] | nibble << 16;
+    return entry(lo, w | ebits_of(g), idx[e], magic_of(g), col, step);
+}
+
+}  // namespace nib
 
 }  // namespace fix56
 }  // namespace csrk

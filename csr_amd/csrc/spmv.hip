@@ -598,7 +598,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const AccLaunchArgs L, con
         const int64_t pstep = (int64_t)A.n_wg;      // the group's workgroups' tiles are interleaved (acc_phys_tile)
         if (t < nt) {
             const u32x4_t *ip = (const u32x4_t *)(pidx + (sg.ptile0 + t * pstep) * ACC_TILE);
-            v.load(pvals + (sg.ptile0 + t * pstep) * ACC_TILE, lane);
+            v.load(acc_tile_at(pvals, sg.ptile0 + t * pstep), lane);
             ix = __builtin_nontemporal_load(ip + lane);
             tr0 = tile_row0[sg.tile0 + t];
         }
@@ -606,14 +606,17 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const AccLaunchArgs L, con
             const bool more = t + NW < nt;
             if (more) {      // next tile's loads are in flight while this one is reduced
                 const u32x4_t *ip = (const u32x4_t *)(pidx + (sg.ptile0 + (t + NW) * pstep) * ACC_TILE);
-                vn.load(pvals + (sg.ptile0 + (t + NW) * pstep) * ACC_TILE, lane);
+                vn.load(acc_tile_at(pvals, sg.ptile0 + (t + NW) * pstep), lane);
                 ixn = __builtin_nontemporal_load(ip + lane);
                 tr0n = tile_row0[sg.tile0 + t + NW];
             }
-            const uint32_t e[ACC_K] = {ix.x & 0xffffu, ix.x >> 16, ix.y & 0xffffu, ix.y >> 16,
-                                       ix.z & 0xffffu, ix.z >> 16, ix.w & 0xffffu, ix.w >> 16};
+            uint32_t e[ACC_K] = {ix.x & 0xffffu, ix.x >> 16, ix.y & 0xffffu, ix.y >> 16,
+                                 ix.z & 0xffffu, ix.z >> 16, ix.w & 0xffffu, ix.w >> 16};
             double a[ACC_K];
-            v.get(a, fx_g);
+            // (the 8.5-byte entries keep the value's sign in the index word: their get() takes the words and leaves them as
+            // every other stream stores them)
+            if constexpr (std::is_same<SV, fix56::nib::Bytes>::value) v.get(a, fx_g, e);
+            else v.get(a, fx_g);
             double xv[ACC_K];
 #pragma unroll
             for (int j = 0; j < ACC_K; j++) xv[j] = s_x[e[j] & ACC_COL_MASK];
@@ -1307,7 +1310,11 @@ int spmv_kernel_attributes()
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed>,
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed>,
                           (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed, float>})
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed, float>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::nib::Bytes>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::nib::Bytes>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::nib::Bytes, float>,
+                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::nib::Bytes, float>})
         CSRK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
@@ -1461,6 +1468,7 @@ static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipSt
                 const unsigned n_blocks = (unsigned)(gb > 1 ? ap->launch_wgs : ap->n_wg);
 #define ACC_LAUNCH(SV) spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, SV, XT><<<n_blocks, ACC_THREADS, lds, s>>>(L, d_x, m->ncols)
                 if (ap->f32) ACC_LAUNCH(float);
+                else if (ap->nib) ACC_LAUNCH(fix56::nib::Bytes);
                 else if (ap->fix56) ACC_LAUNCH(fix56::Packed);
                 else ACC_LAUNCH(double);
 #undef ACC_LAUNCH

@@ -7,6 +7,7 @@
 #include "fix56.h"
 #include "acc_groups.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace csrk {
@@ -80,7 +81,7 @@ struct AccPanel {
     // Groups side by side: the first group of a launch says how many groups the launch serves (`launch_groups`, this one and
     // the next ones of SpmvPlan::acc; 0 in those) and with how many blocks; wg_map[block] = group << 16 | workgroup
     // (accgroups::place_wgs; empty for a launch of one group, whose block b is workgroup b).  The groups of one launch
-    // hold values of one form (f32 / fix56).
+    // hold values of one form (f32 / fix56 / nib).
     int32_t launch_groups = 1, launch_wgs = 0;
     DevBuf wg_map;
     int64_t tiles = 0, nnz = 0, n_segs = 0;
@@ -91,6 +92,9 @@ struct AccPanel {
     // vals holds fix56 tiles (fix56.h: the group's float64 values lie on the grid 2^fx_g; 9 B per entry instead of 10, decoded
     // exactly): chosen per group at plan time, checked there entry by entry against the source, CSRK_SPMV_FIX56=0 forbids it
     bool fix56 = false;
+    // ... and of those the 8.5-byte form (fix56.h, nib: 6.5-byte value tiles, the sign in the index word, 12-bit columns):
+    // taken for a launch by accgroups::choose_nib / CSRK_SPMV_NIB, checked like fix56 (values, columns and row steps)
+    bool nib = false;
     int32_t fx_g = 0;
 };
 
@@ -298,6 +302,8 @@ constexpr int ACC_THREADS = 1024;
 // ascend inside a block; 0 = same row).  A tile's first entry has step 0 and its row in tile_row0[]; a step over 7
 // is bridged by padding entries (0.0 * zero slot) of step 7.  10 B per entry instead of 12: the kernel runs at the
 // fabric's rate, so bytes are its time (16-bit columns + a row id per run, fetched by a dependent load, had not paid).
+// (The 8.5-byte form, fix56.h nib, stores {sign of the value, step : 3, column : 12} instead and marks a padding entry by
+// "sign set, mantissa 0"; AccVals<fix56::nib::Bytes>::get hands the kernel the words in the form above.)
 constexpr int ACC_ROW_SHIFT = 13;
 constexpr uint32_t ACC_COL_MASK = (1u << ACC_ROW_SHIFT) - 1;
 constexpr int ACC_MAXSTEP = 7;
@@ -408,6 +414,49 @@ template <> struct AccVals<fix56::Packed> {
         }
     }
 };
+
+// The same values in 6.5 bytes, their signs in the index words (fix56.h, nib: 8.5 B per entry): the 32-bit and 16-bit planes
+// as above, then a 4-bit plane, a lane's eight nibbles in ONE dword (a 4-B load) -- five loads per lane and tile as before,
+// 3328 B of values instead of 3584.  get() also takes the lane's eight index words {sign, step : 3, column : 12} and leaves
+// them in the stream's usual form {step : 3, column : 13}, a padding entry (sign set, M = 0) on column ACC_CB: one v_bfe_u32
+// takes the nibble, an or puts the exponent field of 2^(52 + g) over it, one v_perm_b32 sets both over their half of the
+// 16-bit plane's word, then fix56::nib::entry.
+static_assert(fix56::nib::PAD_COL == (uint32_t)ACC_CB, "a padding entry of a nib tile reads the window's zero slot");
+template <> struct AccVals<fix56::nib::Bytes> {
+    u32x4_t lo[2], mid;
+    uint32_t hi;
+    __device__ __forceinline__ void load(const fix56::nib::Bytes *tile, int lane)
+    {
+        const unsigned char *tp = (const unsigned char *)tile;
+#pragma unroll
+        for (int q = 0; q < 2; q++) lo[q] = __builtin_nontemporal_load((const u32x4_t *)tp + q * WAVE + lane);
+        mid = __builtin_nontemporal_load((const u32x4_t *)(tp + fix56::nib::MID_OFF) + lane);
+        hi = __builtin_nontemporal_load((const uint32_t *)(tp + fix56::nib::HI_OFF) + lane);
+    }
+    __device__ __forceinline__ void get(double (&a)[ACC_K], int32_t g, uint32_t (&e)[ACC_K]) const
+    {
+        const uint32_t l[ACC_K] = {lo[0].x, lo[0].y, lo[0].z, lo[0].w, lo[1].x, lo[1].y, lo[1].z, lo[1].w};
+        const uint32_t m[4] = {mid.x, mid.y, mid.z, mid.w};
+        const uint32_t ebits = fix56::ebits_of(g);
+        const double magic = fix56::magic_of(g);
+#pragma unroll
+        for (int j = 0; j < ACC_K; j++) {
+            // the high word of 2^(52 + g) + M * 2^g: {exponent field and nibble, half j & 1 of m} -- selector bytes 0..3 come
+            // from m, 4..7 from the exponent-and-nibble word
+            const uint32_t top = ((hi >> (4 * j)) & 0xfu) | ebits >> 16;
+            const uint32_t w = __builtin_amdgcn_perm(top, m[j >> 1], 0x05040000u | ((2u * (j & 1) + 1u) << 8) | (2u * (j & 1)));
+            uint32_t col, step;
+            a[j] = fix56::nib::entry(l[j], w, e[j], magic, col, step);
+            e[j] = col | step << ACC_ROW_SHIFT;
+        }
+    }
+};
+// where a group's value tile `t` starts: 512 entries of SV -- or, for the 6.5-byte tiles, a byte offset
+template <class SV> __host__ __device__ __forceinline__ SV *acc_tile_at(SV *vals, int64_t t)
+{
+    if constexpr (sizeof(SV) == 1) return vals + t * fix56::nib::TILE_BYTES;
+    else return vals + t * ACC_TILE;
+}
 
 // The merge-path tile kernel spends ~600 vector instructions per wavefront-tile on index arithmetic (clamped
 // 64-bit addresses, merge coordinates, the cut table) and four dependent memory round trips per 2048-item

@@ -628,17 +628,49 @@ __global__ __launch_bounds__(256) void acc_range_kernel(const P *__restrict__ rp
     }
 }
 
-// One value of tier 0's stream: stored by the fill kernels -- or, VERIFY (fix56 tiles only), read back from the finished tile
-// by the routine the product kernel uses (AccVals: the loads of lane el / 8, its decode) and compared with the source bit for
-// bit.
+// One entry of tier 0's stream -- value v, column `col` inside the block (ACC_CB: a padding entry, v = 0.0), row step -- stored
+// by the fill kernels; or, VERIFY (packed tiles only), read back from the finished tile by the routine the product kernel uses
+// (AccVals: the loads of lane el / 8, its decode) and compared with the source bit for bit.
+// The 8.5-byte form (fix56.h, nib) keeps the sign in the index word and eight nibbles of neighbouring entries in one dword:
+// the nibble is or-ed in atomically (the tiles are zeroed first), and VERIFY also compares the column and the step the
+// kernel would see; a padding entry must come back as -0.0 on column ACC_CB.
 template <class SV, bool VERIFY>
-__device__ __forceinline__ void acc_put(SV *__restrict__ pvals, int64_t pt, int el, double v, int32_t fx_g,
-                                        int32_t *__restrict__ mismatch)
+__device__ __forceinline__ void acc_put(SV *__restrict__ pvals, uint16_t *__restrict__ pidx, int64_t pt, int el, double v,
+                                        uint32_t col, uint32_t step, int32_t fx_g, int32_t *__restrict__ mismatch)
 {
-    if constexpr (!std::is_same<SV, fix56::Packed>::value) {
+    if constexpr (std::is_same<SV, fix56::nib::Bytes>::value) {
+        namespace nib = fix56::nib;
+        unsigned char *tile = (unsigned char *)acc_tile_at(pvals, pt);
+        const bool pad = col == (uint32_t)ACC_CB;
+        if constexpr (!VERIFY) {
+            const uint64_t p = pad ? nib::PAD_CODE : fix56::encode(v, fx_g);
+            ((uint32_t *)tile)[fix56::lo_slot(el)] = fix56::lo_of(p);
+            ((uint16_t *)(tile + nib::MID_OFF))[el] = fix56::mid_of(p);
+            if (nib::hi_of(p)) atomicOr((uint32_t *)(tile + nib::HI_OFF) + nib::hi_word(el), nib::hi_of(p) << nib::hi_shift(el));
+            pidx[pt * ACC_TILE + el] = nib::index_word(p, col, step);
+        } else {
+            AccVals<SV> t;
+            t.load((const SV *)tile, el >> 3);
+            const u32x4_t ix = *((const u32x4_t *)(pidx + pt * ACC_TILE) + (el >> 3));
+            uint32_t e[ACC_K] = {ix.x & 0xffffu, ix.x >> 16, ix.y & 0xffffu, ix.y >> 16,
+                                 ix.z & 0xffffu, ix.z >> 16, ix.w & 0xffffu, ix.w >> 16};
+            double a[ACC_K];
+            t.get(a, fx_g, e);
+            double d = a[0];
+            uint32_t w = e[0];
+#pragma unroll
+            for (int j = 1; j < ACC_K; j++) {
+                d = (el & 7) == j ? a[j] : d;
+                w = (el & 7) == j ? e[j] : w;
+            }
+            if (fix56::bits_of(d) != (pad ? 1ull << 63 : fix56::bits_of(v)) || w != (col | step << ACC_ROW_SHIFT)) *mismatch = 1;
+        }
+    } else if constexpr (!std::is_same<SV, fix56::Packed>::value) {
         pvals[pt * ACC_TILE + acc_slot_of<SV>(el)] = (SV)v;
+        pidx[pt * ACC_TILE + el] = (uint16_t)(col | step << ACC_ROW_SHIFT);
     } else if constexpr (!VERIFY) {
         fix56::put((unsigned char *)(pvals + pt * ACC_TILE), el, fix56::encode(v, fx_g));
+        pidx[pt * ACC_TILE + el] = (uint16_t)(col | step << ACC_ROW_SHIFT);
     } else {
         AccVals<SV> t;
         t.load(pvals + pt * ACC_TILE, el >> 3);
@@ -710,17 +742,16 @@ __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp,
         const int el = (int)(L % ACC_TILE);
         const int64_t pt = acc_phys_tile(t, wg_t0, n_wg);
         if (at < npad_p) {                           // padding entry k = at + 1 stands on heavy row c - g + 7k
-            acc_put<SV, VERIFY>(pvals, pt, el, 0.0, fx_g, mismatch);
+            acc_put<SV, VERIFY>(pvals, pidx, pt, el, 0.0, (uint32_t)cb, el ? (uint32_t)ACC_MAXSTEP : 0u, fx_g, mismatch);
             if (VERIFY) continue;
-            pidx[pt * ACC_TILE + el] = (uint16_t)((uint32_t)cb | ((el ? (uint32_t)ACC_MAXSTEP : 0u) << ACC_ROW_SHIFT));
             if (el == 0) tile_row0[t] = c0 + p - g_p + ACC_MAXSTEP * (at + 1);
         } else {
             const int64_t k = lo_p + (at - npad_p);
             // the pair's first entry: the step from the previous row (or the last padding entry) to this row
             const uint32_t step_in = at == npad_p ? (uint32_t)(g_p - ACC_MAXSTEP * npad_p) : 0u;
-            acc_put<SV, VERIFY>(pvals, pt, el, ValLoad<VT>::at(vs, k), fx_g, mismatch);
+            acc_put<SV, VERIFY>(pvals, pidx, pt, el, ValLoad<VT>::at(vs, k), (uint32_t)(ci[k] - b * cb), el ? step_in : 0u, fx_g,
+                                mismatch);
             if (VERIFY) continue;
-            pidx[pt * ACC_TILE + el] = (uint16_t)((uint32_t)(ci[k] - b * cb) | ((el ? step_in : 0u) << ACC_ROW_SHIFT));
             if (el == 0) tile_row0[t] = c0 + p;
         }
     }
@@ -741,8 +772,7 @@ __global__ __launch_bounds__(256) void acc_pad_kernel(const int64_t *__restrict_
     for (int64_t L = L0 + threadIdx.x; L < L1; L += blockDim.x) {      // (the tail of the block's last tile: one tile)
         const int64_t pt = acc_phys_tile(L / ACC_TILE, wg_t0, n_wg);
         const int el = (int)(L % ACC_TILE);
-        acc_put<SV, VERIFY>(pvals, pt, el, 0.0, fx_g, mismatch);
-        if (!VERIFY) pidx[pt * ACC_TILE + el] = (uint16_t)ACC_CB;
+        acc_put<SV, VERIFY>(pvals, pidx, pt, el, 0.0, (uint32_t)ACC_CB, 0u, fx_g, mismatch);
     }
 }
 
@@ -1022,13 +1052,16 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
 
 // Build one accumulator-form group: the listed heavy rows (<= ACC_MAXROWS, ascending) as a tiled,
 // column-block-major (value, packed index) stream plus the persistent workgroups' segment lists.
-// wg_want: the group's workgroups when it shares its launch with other groups (0: one per CU); allow_fix56 = false: the
-// raw stream whatever the values (another group of the launch could not be packed).
+// wg_want: the group's workgroups when it shares its launch with other groups (0: one per CU); form: what packable float64
+// values are stored as -- ACC_FORM_RAW: the raw stream whatever the values (another group of the launch could not be packed),
+// ACC_FORM_FIX56: 9-byte entries, ACC_FORM_NIB: 8.5-byte entries (the launch's choice: accgroups::choose_nib).
+enum { ACC_FORM_RAW = 0, ACC_FORM_FIX56 = 1, ACC_FORM_NIB = 2 };
 template <class P, int VT>
 static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const int64_t *lens, int32_t n, int64_t nnz_rows,
-                           hipStream_t s, int32_t wg_want = 0, bool allow_fix56 = true)
+                           hipStream_t s, int32_t wg_want = 0, int form = ACC_FORM_FIX56)
 {
     ap->fix56 = false;
+    ap->nib = false;
     ap->fx_g = 0;
     const P *rp = (const P *)m->d_rowptrs;
     const int32_t nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB);
@@ -1095,7 +1128,7 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     // the whole group: the grid test over its values, and CSRK_SPMV_FIX56=0 forbids the form (tests, measurements)
     DevBuf fx;      // int32[4]: the grid test's bad flag, lowest and highest set bit; the verification's mismatch flag
     CSRK_TRY(fx.alloc(16));
-    if (VT == CSRK_VAL_F64 && n > 0 && allow_fix56) {
+    if (VT == CSRK_VAL_F64 && n > 0 && form != ACC_FORM_RAW) {
         const char *env = getenv("CSRK_SPMV_FIX56");
         if (!(env && env[0] == '0')) {
             int32_t h[4] = {0, INT32_MAX, INT32_MIN, 0};
@@ -1110,6 +1143,7 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
             r.lo = h[1];
             r.hi = h[2];
             ap->fix56 = fix56::packable(r, ap->fx_g);
+            ap->nib = ap->fix56 && form == ACC_FORM_NIB;
             tr.lap("  tier 0: value grid test");
         }
     }
@@ -1131,18 +1165,26 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
         CSRK_LAUNCH_CHECK();                                                                                           \
     } while (0)
     if (ap->fix56) {
-        CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::TILE_BYTES));
-        ACC_FILL(fix56::Packed, false);
-        tr.lap("  tier 0: fill (fix56)");
         // the library's own proof of "exact", on every plan: every stored entry decoded as the product decodes it, against
-        // the source; a single mismatch and the group is rebuilt raw
+        // the source (the 8.5-byte form: its column and row step too); a single mismatch and the group is rebuilt raw
         int32_t mismatch = 1;
-        ACC_FILL(fix56::Packed, true);
+        if (ap->nib) {
+            CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::nib::TILE_BYTES));
+            CSRK_HIP(hipMemsetAsync(ap->vals.p, 0, (size_t)n_phys * fix56::nib::TILE_BYTES, s));      // (the nibbles are or-ed in)
+            ACC_FILL(fix56::nib::Bytes, false);
+            tr.lap("  tier 0: fill (nib)");
+            ACC_FILL(fix56::nib::Bytes, true);
+        } else {
+            CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::TILE_BYTES));
+            ACC_FILL(fix56::Packed, false);
+            tr.lap("  tier 0: fill (fix56)");
+            ACC_FILL(fix56::Packed, true);
+        }
         CSRK_TRY(stage_d2h(&mismatch, fx.as<int32_t>() + 3, 4, s));
         CSRK_HIP(hipStreamSynchronize(s));
-        tr.lap("  tier 0: verify (fix56)");
+        tr.lap(ap->nib ? "  tier 0: verify (nib)" : "  tier 0: verify (fix56)");
         if (mismatch) {
-            ap->fix56 = false;
+            ap->fix56 = ap->nib = false;
             ap->fx_g = 0;
         }
     }
@@ -1192,9 +1234,18 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     if (tr.on)
         fprintf(stderr, "[csrk plan]   tier 0 group: rows %d entries %lld workgroups %lld tiles %lld, %.1f per segment%s\n", n,
                 (long long)nnz_rows, (long long)n_wg, (long long)n_tiles, segs.empty() ? 0.0 : (double)n_tiles / (double)segs.size(),
-                ap->fix56 ? " (fix56)" : "");
+                ap->nib ? " (nib)" : ap->fix56 ? " (fix56)" : ap->f32 ? " (float32)" : " (raw)");
     tr.lap("  tier 0: segments");
     return CSRK_OK;
+}
+
+// CSRK_SPMV_NIB, read when a plan is built: 1 = packable groups take the 8.5-byte entries, 0 = never, unset (-1) = where
+// accgroups::choose_nib says they pay.  CSRK_SPMV_FIX56=0 forbids every packed form.
+static int acc_nib_knob()
+{
+    const char *env = getenv("CSRK_SPMV_NIB");
+    if (!env || !env[0]) return -1;
+    return env[0] == '0' ? 0 : 1;
 }
 
 // Tier 0's groups, read when a plan is built: CSRK_ACC_GROUPS = groups that share one launch of the accumulator kernel
@@ -1378,7 +1429,12 @@ static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
     for (size_t j = 0; j + 1 < deal.first.size(); j++) {
         const int k0 = deal.first[j], gb = deal.first[j + 1] - k0;
         const size_t a0 = p->acc.size();
-        auto build = [&](int g, bool allow_fix56) -> int {
+        // the launch's packed form: 8.5-byte entries where the stream is what the kernel's time is (accgroups::choose_nib)
+        int64_t launch_entries = 0;
+        for (int g = 0; g < gb; g++)
+            for (int32_t pos : deal.groups[(size_t)(k0 + g)]) launch_entries += len0[(size_t)pos];
+        const int packed = accgroups::choose_nib(acc_nib_knob(), launch_entries, cus) ? ACC_FORM_NIB : ACC_FORM_FIX56;
+        auto build = [&](int g, int form) -> int {
             const std::vector<int32_t> &pos = deal.groups[(size_t)(k0 + g)];
             rows.resize(pos.size());
             lens.resize(pos.size());
@@ -1389,21 +1445,21 @@ static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
                 gn += lens[i];
             }
             return build_acc_panel<P, VT>(m, p->acc[a0 + (size_t)g], rows.data(), lens.data(), (int32_t)pos.size(), gn, s,
-                                          gb > 1 ? accgroups::group_wgs(cus, gb, g) : 0, allow_fix56);
+                                          gb > 1 ? accgroups::group_wgs(cus, gb, g) : 0, form);
         };
         bool any_raw = false;
         for (int g = 0; g < gb; g++) {
             AccPanel *ap = new (std::nothrow) AccPanel();
             CSRK_REQUIRE(ap, "out of host memory");
             p->acc.push_back(ap);
-            CSRK_TRY(build(g, true));
+            CSRK_TRY(build(g, packed));
             any_raw = any_raw || !ap->fix56;
         }
         AccPanel *head = p->acc[a0];
         if (gb == 1) continue;
         // one kernel serves the launch: its groups hold one form of values
         for (int g = 0; g < gb; g++)
-            if (any_raw && p->acc[a0 + (size_t)g]->fix56) CSRK_TRY(build(g, false));
+            if (any_raw && p->acc[a0 + (size_t)g]->fix56) CSRK_TRY(build(g, ACC_FORM_RAW));
         int32_t n_wg[accgroups::MAX_GROUPS];
         for (int g = 0; g < gb; g++) {
             n_wg[g] = p->acc[a0 + (size_t)g]->n_wg;

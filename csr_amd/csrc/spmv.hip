@@ -443,11 +443,18 @@ __global__ __launch_bounds__(PT) void spmv_panel_kernel(
 
         __syncthreads();      // previous tile's LDS reads finished
         const XT *xw = x + (int64_t)pt.blk * cb;
+        // A tile of fewer than two entries has no pair of its own: its lanes re-read a NEIGHBOURING tile's pair (load_pair_clamped),
+        // which may lie in another column block, and that block's offsets (up to cb - 1) against this block's base pass the
+        // end of x when this is the last, narrower block.  The products are masked below; the addresses are kept inside the
+        // block's window here.
+        const int64_t wleft = (int64_t)ncols - (int64_t)pt.blk * cb;
+        const uint32_t wlast = (uint32_t)((wleft < cb ? wleft : (int64_t)cb) - 1);
 #pragma unroll
         for (int u = 0; u < PPAIRS; u++) {
             const int k = 2 * (tid + u * PT);
-            const double t0 = spmv_prod<R32>(p0[u], (double)xw[(uint32_t)c0[u] >> PANEL_POS_BITS]);
-            const double t1 = spmv_prod<R32>(p1[u], (double)xw[(uint32_t)c1[u] >> PANEL_POS_BITS]);
+            const uint32_t o0 = (uint32_t)c0[u] >> PANEL_POS_BITS, o1 = (uint32_t)c1[u] >> PANEL_POS_BITS;
+            const double t0 = spmv_prod<R32>(p0[u], (double)xw[o0 < wlast ? o0 : wlast]);
+            const double t1 = spmv_prod<R32>(p1[u], (double)xw[o1 < wlast ? o1 : wlast]);
             p0[u] = k < nn ? t0 : 0.0;       // masked after the multiply: 0 * inf would be NaN
             p1[u] = k + 1 < nn ? t1 : 0.0;
         }
@@ -2001,6 +2008,10 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
                           rnd ? ls.stage_w : 0,
                           ls.on && ls.f32 ? 1 : 0};
     for (int i = 34; i < n && i < 42; i++) out[i] = w[i - 34];
+    // tier 1's layout (build_panel): [42] column blocks, [43] tiles, [44] carry rows behind the partials (Panel::ncs), [45] carries
+    // listed in crp / cidx, [46] groups of the pair kernel's launch, padding included, and [47] the padding groups among them
+    const int64_t u[6] = {t1.nb, t1.tiles, t1.ncs, t1.listed, t1.groups, t1.pad_groups};
+    for (int i = 42; i < n && i < 48; i++) out[i] = u[i - 42];
     return CSRK_OK;
 }
 

@@ -65,6 +65,9 @@ struct Panel {
     // crp[h + 1])] as before (crp empty when there are none).
     int32_t ncs = 0;
     DevBuf crp, cidx;
+    // what the plan's census reports of the above (csrk_spmv_plan_stats): carries listed in cidx, and the groups of the
+    // workgroup list that are padding of an XCD stream (nt == 0; `groups` counts them too)
+    int64_t listed = 0, pad_groups = 0;
 };
 
 // one segment of an accumulator-form workgroup's tile range (see "long rows, accumulator form")

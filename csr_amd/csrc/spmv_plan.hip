@@ -1010,6 +1010,7 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
             listed = listed || cnt[(size_t)h] > ncs;
         }
         cidx.resize((size_t)crp[(size_t)n] + 1);
+        pn->listed = crp[(size_t)n];
         std::vector<int32_t> seen((size_t)n, 0);
         for (int64_t t = 0; t < n_tiles; t++) {      // ascending tiles: each row's carries come out in tile order
             PanelTile &T = ht[(size_t)t];
@@ -1028,6 +1029,8 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
         }
     }
     pn->groups = (int64_t)groups.size();
+    pn->pad_groups = 0;
+    for (const PanelGroup &gq : groups) pn->pad_groups += gq.nt == 0;
     CSRK_TRY(pn->group.alloc(groups.size() * sizeof(PanelGroup)));
     CSRK_TRY(stage_h2d(pn->group.p, groups.data(), groups.size() * sizeof(PanelGroup), s));
     CSRK_TRY(pn->carry_row.alloc((size_t)n_tiles * 4));

@@ -1310,7 +1310,8 @@ SPMV_PLAN_STATS = ('tiles', 'tile_items', 'cut_rows', 'path_entries', 't0_tiles'
                    't0_rows', 't0_entries', 't1_rows', 't1_pairs', 't1_entries', 't1_min', 't1_block_width', 'n_hot', 'hot_cover_ppm',
                    't0_acc', 'hot_slots', 'stream', 'ls_tiles', 'ls_runs', 'ls_grid', 'ls_staged', 'plan_bytes', 'ls_round_tiles',
                    't0_workgroups', 'reserved', 'bytes_t0', 'bytes_t1', 'bytes_stream', 'bytes_staging', 'bytes_tables',
-                   'ls_dense', 'ls_idx24', 'ls_hot_lds', 'ls_rounds', 'ls_wg_rounds', 'ls_stage_blocks', 'ls_stage_width', 'ls_f32')
+                   'ls_dense', 'ls_idx24', 'ls_hot_lds', 'ls_rounds', 'ls_wg_rounds', 'ls_stage_blocks', 'ls_stage_width', 'ls_f32',
+                   't1_blocks', 't1_tiles', 't1_carry_rows', 't1_listed_carries', 't1_groups', 't1_pad_groups')
 SPMV_STREAM_LIMITS = ('ACC_TILE', 'ACC_K', 'LS_WAVES', 'LS_SEQ', 'LS_RID', 'LS_HOT_LDS', 'LS_RND_HOT', 'LS_RND_CAP', 'LS_RND_MAXTILES',
                       'LS_STAGE_WMAX', 'LS_STAGE_BATCH', 'TIERB_MIN', 'HOT_SLOTS')
 

@@ -180,7 +180,10 @@ CSRK_API int csrk_spmv_plan_info(csrk_handle_t h, int64_t *n_tiles, int32_t *til
  * the light stream's form, all 0 without a stream: 34 dense layout (every row of the view has a run: no row ids, no gaps)
  * (0/1), 35 3-byte index words (0/1), 36 pack slots the stream kernel reads from LDS, 37 rounds in all and 38 the most one
  * workgroup walks (staged rounds; without staging the kernel's own rounds of one tile per wavefront), 39 column blocks of
- * the copy pass and 40 their width in columns (0 without staging), 41 float32 stored values (0/1)};  n <= 42. */
+ * the copy pass and 40 their width in columns (0 without staging), 41 float32 stored values (0/1),
+ * tier 1's layout, all 0 without the tier: 42 column blocks, 43 tiles, 44 carry rows kept behind the block partials (a row's
+ * first carries, at most 4), 45 carries listed beyond those, 46 workgroups of the pair kernel's own list (padding groups of
+ * the XCD streams included), 47 the padding groups among them};  n <= 48. */
 CSRK_API int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n);
 /* The compile-time constants the light stream's form is decided by, callable without a device: out[0..n) <- {0 entries per
  * tile (512), 1 consecutive entries per lane (8), 2 wavefronts per workgroup (8), 3 in-order carry hand-overs (3: a run whose

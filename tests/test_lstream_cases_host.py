@@ -27,7 +27,7 @@ def test_constants_are_the_librarys():
     from csr_amd.kernels import hip as K
     assert K.SPMV_STREAM_LIMITS == tuple(S.LIMITS)
     assert K.spmv_stream_limits() == S.LIMITS
-    assert len(K.SPMV_PLAN_STATS) == 42 and set(S.build('gaps').layout('staged', 256).census()) <= set(K.SPMV_PLAN_STATS)
+    assert len(K.SPMV_PLAN_STATS) == 48 and set(S.build('gaps').layout('staged', 256).census()) <= set(K.SPMV_PLAN_STATS)
     # what the module derives from them
     assert S.EXACT_LEN == 25 and S.RID_SLOTS == 256 and S.TILE == S.WAVE * S.K8
     assert S.NW * S.TILE <= S.LIMITS['LS_RND_CAP'] and S.LIMITS['HOT_SLOTS'] < S.IDX24_MAX

@@ -61,15 +61,15 @@ __device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][GT_B][GT_B], cons
                 }
             }
         if (tid == j) piv[buf] = z;
-        gt_team_sync<TEAM>();
+        team_sync<TEAM>();
         const double d = col[buf][j];
         const double rj = 1.0 / d;                                          // one correctly rounded division
         if (info == 0 && !(d > 0.0)) info = j + 1;
 #pragma unroll
         for (int r = 0; r < TPT; r++)
             if (has[r] && q0[r] + GT_B > j && p0[r] + GT_B > j) {
-                const gt_d2 a0 = *(const gt_d2 *)&col[buf][p0[r]], a1 = *(const gt_d2 *)&col[buf][p0[r] + 2];
-                const gt_d2 b0 = *(const gt_d2 *)&col[buf][q0[r]], b1 = *(const gt_d2 *)&col[buf][q0[r] + 2];
+                const f64x2_t a0 = *(const f64x2_t *)&col[buf][p0[r]], a1 = *(const f64x2_t *)&col[buf][p0[r] + 2];
+                const f64x2_t b0 = *(const f64x2_t *)&col[buf][q0[r]], b1 = *(const f64x2_t *)&col[buf][q0[r] + 2];
                 const double cp[GT_B] = {a0.x, a0.y, a1.x, a1.y}, cq[GT_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                 for (int i = 0; i < GT_B; i++) {
@@ -101,7 +101,7 @@ __device__ __forceinline__ int al_ldl_solve(double (&acc)[TPT][GT_B][GT_B], cons
                 }
             }
         if (tid == t) piv[buf] = x;
-        gt_team_sync<TEAM>();
+        team_sync<TEAM>();
         if (tid < t) x = __builtin_fma(-col[buf][tid], piv[buf], x);
     }
     zx = x;

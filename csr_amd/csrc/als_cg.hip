@@ -7,7 +7,8 @@
 //
 // Work split.  ONE 16-LANE TEAM (one DPP row) PER ROW OF THE MATRIX, at every k: four rows per wavefront, sixteen per
 // workgroup.  Lane l owns the columns of csrk_sddmm's partial l (in each 64-column chunk: float64 2 l, 2 l + 1, 32 + 2 l,
-// 33 + 2 l; float32 4 l .. 4 l + 3), so a V row arrives in 16-B pieces, each load instruction of a team one contiguous
+// 33 + 2 l; float32 4 l .. 4 l + 3: panel_off and panel_load4 in device_loads.h, the code SDDMM runs), so a V row
+// arrives in 16-B pieces, each load instruction of a team one contiguous
 // 256-B span, and x, r, p, q and b live in registers: 4 doubles each per chunk and lane, 8 at k = 128.  A DOT is the
 // lane's fma chain over its columns and four DPP adds; the adds form a butterfly (lane ^ 1, ^ 2, then the half-row and
 // row mirrors), so EVERY lane ends with the sum in rule C2's tree shape -- floating-point addition commutes, so the lanes
@@ -26,12 +27,14 @@
 // Divergence.  The teams of a wavefront have rows of different lengths and stop after different numbers of steps: every
 // loop is team-uniform, and nothing crosses a team (the DPP controls stay inside a row of 16 lanes).
 #include "common.h"
+#include "device_loads.h"
 #include "panel.h"
 #include "wave.h"
 
 namespace csrk {
 
 constexpr int CG_G = 16;                 // lanes per team (one DPP row)
+static_assert(CG_G == PANEL_G, "a team is the lanes that share a panel row (device_loads.h)");
 constexpr int CG_THREADS = 256;
 constexpr int CG_TEAMS = CG_THREADS / CG_G;
 constexpr int CG_E = 4;                  // entries in flight per team and step of the entry loop
@@ -39,46 +42,6 @@ constexpr int CG_K_MAX = 128;            // two chunks of 64 columns (csrk_als_l
 
 // dpp_ctrl encodings (CDNA ISA): quad_perm [1, 0, 3, 2] and [2, 3, 0, 1], lanes 7 - l of a half row, 15 - l of a row
 constexpr int DPP_QUAD_X1 = 0xB1, DPP_QUAD_X2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141, DPP_ROW_MIRROR = 0x140;
-
-// Element q (0..3) of lane `sub` in a 64-column chunk: csrk_sddmm's ownership, 16-B pieces of PIECE elements.
-template <class T>
-__device__ __forceinline__ int cg_off(int sub, int q)
-{
-    constexpr int PIECE = 16 / (int)sizeof(T);
-    return (q / PIECE) * (CG_G * PIECE) + sub * PIECE + q % PIECE;
-}
-
-typedef double cg_d2 __attribute__((ext_vector_type(2)));
-typedef float cg_f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void cg_piece(const double *p, double *d)
-{
-    const cg_d2 a = *(const cg_d2 *)p;
-    d[0] = a.x, d[1] = a.y;
-}
-__device__ __forceinline__ void cg_piece(const float *p, float *d)
-{
-    const cg_f4 a = *(const cg_f4 *)p;
-    d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w;
-}
-
-// the lane's four elements of one chunk of a row (p = the chunk's first column; kk = columns left from it); columns at or
-// past k read as 0 and are never used.  WIDE: 16-B loads for whole pieces (aligned by the caller).
-template <class T, bool WIDE>
-__device__ __forceinline__ void cg_load4(const T *__restrict__ p, int sub, int kk, T d[4])
-{
-    constexpr int PIECE = 16 / (int)sizeof(T);
-#pragma unroll
-    for (int q0 = 0; q0 < 4; q0 += PIECE) {
-        const int o = cg_off<T>(sub, q0);
-        if (WIDE && o + PIECE <= kk) {
-            cg_piece(p + o, d + q0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < PIECE; i++) d[q0 + i] = o + i < kk ? p[o + i] : (T)0;
-        }
-    }
-}
 
 // rule C2's tree, in every lane of the team
 __device__ __forceinline__ double cg_team_sum(double s)
@@ -99,16 +62,8 @@ __device__ __forceinline__ double cg_dot(const A (&a)[NCH][4], const double (&b)
     for (int c = 0; c < NCH; c++)
 #pragma unroll
         for (int q = 0; q < 4; q++)
-            if (64 * c + cg_off<OFFT>(sub, q) < k) s = __builtin_fma((double)a[c][q], b[c][q], s);
+            if (64 * c + panel_off<OFFT>(sub, q) < k) s = __builtin_fma((double)a[c][q], b[c][q], s);
     return cg_team_sum(s);
-}
-
-// within one wavefront LDS operations complete in issue order: order the compiler and the counters
-__device__ __forceinline__ void cg_team_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // rule C3's first two parts: q = base y (u ascending), then q_t = fma(rho, y_t, q_t).  ys: the team's k doubles of LDS.
@@ -116,15 +71,15 @@ template <class OFFT, int NCH, bool BW>
 __device__ __forceinline__ void cg_base_part(const double *__restrict__ base, int k, int sub, const double (&y)[NCH][4],
                                              double (&q)[NCH][4], double *ys)
 {
-    cg_team_sync();                                                         // (the last product's reads of ys are done)
+    team_sync<CG_G>();                                                      // (the last product's reads of ys are done)
 #pragma unroll
     for (int c = 0; c < NCH; c++)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int t = 64 * c + cg_off<OFFT>(sub, i);
+            const int t = 64 * c + panel_off<OFFT>(sub, i);
             if (t < k) ys[t] = y[c][i];
         }
-    cg_team_sync();
+    team_sync<CG_G>();
 #pragma unroll 2
     for (int u = 0; u < k; u++) {
         const double yu = ys[u];
@@ -132,13 +87,13 @@ __device__ __forceinline__ void cg_base_part(const double *__restrict__ base, in
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
             if (sizeof(OFFT) == 8) {
-                cg_load4<double, BW>(base + (int64_t)u * k + 64 * c, sub, k - 64 * c, bv[c]);
+                panel_load4<double, BW>(base + (int64_t)u * k + 64 * c, sub, k - 64 * c, bv[c]);
             } else {                                                        // float32 ownership: columns 4 l .. 4 l + 3, two pieces of doubles
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     const int o = 4 * sub + 2 * h;
                     if (BW && o + 2 <= k - 64 * c) {
-                        cg_piece(base + (int64_t)u * k + 64 * c + o, bv[c] + 2 * h);
+                        panel_piece(base + (int64_t)u * k + 64 * c + o, bv[c] + 2 * h);
                     } else {
 #pragma unroll
                         for (int i = 0; i < 2; i++) bv[c][2 * h + i] = o + i < k - 64 * c ? base[(int64_t)u * k + 64 * c + o + i] : 0.0;
@@ -190,11 +145,11 @@ __device__ __forceinline__ void cg_walk(int64_t e0, int64_t e1, const int32_t *_
 #pragma unroll
         for (int x = 0; x < CG_E; x++)                                      // (past the row: its last entry again, unused)
 #pragma unroll
-            for (int c = 0; c < NCH; c++) cg_load4<T, WIDE>(V + (int64_t)coln[x] * ldv + 64 * c, sub, k - 64 * c, v[x][c]);
+            for (int c = 0; c < NCH; c++) panel_load4<T, WIDE>(V + (int64_t)coln[x] * ldv + 64 * c, sub, k - 64 * c, v[x][c]);
 #pragma unroll
         for (int x = 0; x < CG_E; x++) {
             const int64_t e = es + x < last ? es + x : last;
-            wv[x] = vals ? (vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e]) : 1.0;
+            wv[x] = vals ? csr_stored_val(vals, vt, e) : 1.0;
             const int64_t en = es + CG_E + x < last ? es + CG_E + x : last;
             coln[x] = ci[en];
         }
@@ -254,7 +209,7 @@ __global__ __launch_bounds__(CG_THREADS) void als_cg_kernel(const void *__restri
         for (int c = 0; c < NCH; c++)
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const int t = 64 * c + cg_off<T>(sub, i);
+                const int t = 64 * c + panel_off<T>(sub, i);
                 x[c][i] = t < k ? xr[t] : 0.0;
             }
         cg_head<T, NCH>(base, bwide != 0, rho, k, sub, x, q, ys);
@@ -301,7 +256,7 @@ __global__ __launch_bounds__(CG_THREADS) void als_cg_kernel(const void *__restri
     for (int c = 0; c < NCH; c++)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const int t = 64 * c + cg_off<T>(sub, i);
+            const int t = 64 * c + panel_off<T>(sub, i);
             if (t < k) o[t] = x[c][i];
         }
     if (sub == 0) {

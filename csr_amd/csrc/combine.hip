@@ -19,6 +19,7 @@
 //   0 .. CB_WAVE_MAX     one WAVEFRONT per row, in chunks of 64 entries (no LDS, no barrier)
 //   above                one CB_THREADS-thread WORKGROUP per listed row, in chunks of CB_THREADS entries, one barrier each
 // Column indices are compared and copied, never used as addresses.
+#include "device_loads.h"
 #include "result.h"
 #include "wave.h"
 
@@ -43,14 +44,6 @@ struct CbArgs {
     int32_t *oc;
     void *ov;
 };
-
-// a value as the arithmetic sees it: float32 widened exactly, 1.0 for a structure-only operand
-__device__ __forceinline__ double cb_val(const void *v, int vt, int64_t e)
-{
-    if (vt == CSRK_VAL_F64) return ((const double *)v)[e];
-    if (vt == CSRK_VAL_F32) return (double)((const float *)v)[e];
-    return 1.0;
-}
 
 // the entries of c[0 .. n) below key (c strictly ascending); the probes stay inside [0, n) whatever c holds
 __device__ __forceinline__ uint32_t cb_lower(const int32_t *__restrict__ c, uint32_t n, int32_t key)
@@ -116,10 +109,10 @@ __device__ __forceinline__ void cb_row(const CbArgs &g, int64_t r, int t, uint32
             const uint32_t mi = M + pre;              // M(i)
             if (op == CSRK_COMBINE_ADD) {
                 const int64_t o = ob + ((int64_t)i + p - mi);
-                const double pa = g.alpha * cb_val(g.va, g.vta, spa + i);
+                const double pa = g.alpha * csr_val(g.va, g.vta, spa + i);
                 double v = pa;
                 if (m) {
-                    const double pb = g.beta * cb_val(g.vb, g.vtb, spb + p);
+                    const double pb = g.beta * csr_val(g.vb, g.vtb, spb + p);
                     v = pa + pb;
                 }
                 g.oc[o] = c;
@@ -128,7 +121,7 @@ __device__ __forceinline__ void cb_row(const CbArgs &g, int64_t r, int t, uint32
                 if (m) {
                     const int64_t o = ob + mi;
                     g.oc[o] = c;
-                    ((double *)g.ov)[o] = cb_val(g.va, g.vta, spa + i) * cb_val(g.vb, g.vtb, spb + p);
+                    ((double *)g.ov)[o] = csr_val(g.va, g.vta, spa + i) * csr_val(g.vb, g.vtb, spb + p);
                 }
             } else if (m == (op == CSRK_COMBINE_KEEP)) {      // keep: the matches; drop: the others
                 const int64_t o = ob + (op == CSRK_COMBINE_KEEP ? (int64_t)mi : (int64_t)i - mi);
@@ -169,7 +162,7 @@ __device__ __forceinline__ void cb_row(const CbArgs &g, int64_t r, int t, uint32
         if (in && !m) {
             const int64_t o = ob + ((int64_t)j + p - (MB + pre));
             g.oc[o] = c;
-            ((double *)g.ov)[o] = g.beta * cb_val(g.vb, g.vtb, spb + j);
+            ((double *)g.ov)[o] = g.beta * csr_val(g.vb, g.vtb, spb + j);
         }
         MB += tot;
     }

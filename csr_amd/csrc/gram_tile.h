@@ -1,9 +1,10 @@
 // The row accumulation that gram.hip and als.hip share: for one row of a CSR matrix, the lower triangle of
 //     G = base + sum over the row's stored entries e = (i, j), in storage order, of w_e v_j v_j^T        (k x k, float64)
 // in 4 x 4 register tiles, and with RHS the right-hand side b = sum c_e v_j beside it.  One definition of the k classes, the
-// panel loads, the team fence, the tile numbering, the staging pipeline and the multiply-add loop, so that an als_rows row
-// and a gram_rows row are the same arithmetic (include/csrk.h, rule A) because they are the same code; and the host-side
-// refusal of a k above the classes.  (Panel checks, the 16-B predicate and packing: panel.h.)
+// tile numbering, the staging pipeline and the multiply-add loop, so that an als_rows row and a gram_rows row are the same
+// arithmetic (include/csrk.h, rule A) because they are the same code; and the host-side refusal of a k above the classes.
+// (Panel checks, the 16-B predicate and packing: panel.h.  The panel loads and an entry's value: device_loads.h.  The
+// team fence: wave.h.)
 //
 // Work split.  A TEAM of threads owns a row: 16 lanes for k <= 16, a wavefront for k <= 40, a 256-thread workgroup above.
 // The lower triangle is cut into 4 x 4 register tiles (tile (bp, bq), bq <= bp, holds p = 4 bp .. 4 bp + 3, q = 4 bq ..
@@ -16,7 +17,9 @@
 // pieces, else element by element: the same bits.
 #pragma once
 #include "common.h"
+#include "device_loads.h"
 #include "panel.h"
+#include "wave.h"
 
 namespace csrk {
 
@@ -33,36 +36,6 @@ template <> struct GramClass<0> { static constexpr int TEAM = 16, KMAX = GT_K_SU
 template <> struct GramClass<1> { static constexpr int TEAM = 64, KMAX = GT_K_WAVE, TPT = 1; };
 template <> struct GramClass<2> { static constexpr int TEAM = 256, KMAX = GT_K_ONE, TPT = 1; };
 template <> struct GramClass<3> { static constexpr int TEAM = 256, KMAX = GT_K_MAX, TPT = 3; };
-
-typedef double gt_d2 __attribute__((ext_vector_type(2)));
-typedef float gt_f4 __attribute__((ext_vector_type(4)));
-
-// one unit of a panel row as float64: PER elements (a 16-B piece when PER > 1, else one element)
-template <class T, int PER> __device__ __forceinline__ void gt_load(const T *__restrict__ p, double d[PER]);
-template <> __device__ __forceinline__ void gt_load<double, 1>(const double *__restrict__ p, double d[1]) { d[0] = *p; }
-template <> __device__ __forceinline__ void gt_load<float, 1>(const float *__restrict__ p, double d[1]) { d[0] = (double)*p; }
-template <> __device__ __forceinline__ void gt_load<double, 2>(const double *__restrict__ p, double d[2])
-{
-    const gt_d2 a = *(const gt_d2 *)p;
-    d[0] = a.x, d[1] = a.y;
-}
-template <> __device__ __forceinline__ void gt_load<float, 4>(const float *__restrict__ p, double d[4])
-{
-    const gt_f4 a = *(const gt_f4 *)p;
-    d[0] = (double)a.x, d[1] = (double)a.y, d[2] = (double)a.z, d[3] = (double)a.w;
-}
-
-// the team's threads have all written their LDS words before any of them reads (a team never spans workgroups)
-template <int TEAM> __device__ __forceinline__ void gt_team_sync()
-{
-    if constexpr (TEAM > WAVE) {
-        __syncthreads();
-    } else {      // within one wavefront LDS operations complete in issue order: order the compiler and the counters
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-}
 
 // tile t of the lower triangle, row-major over 4 x 4 blocks: block row bp, block column bq <= bp
 __device__ __forceinline__ void gt_tile(int t, bool has, int &p0, int &q0)
@@ -113,10 +86,10 @@ __device__ __forceinline__ void gt_accumulate(int64_t e0, int64_t e1, const int3
         }
 #pragma unroll
         for (int l = 0; l < NL; l++)
-            if (ue[l] < GT_STAGE) gt_load<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
+            if (ue[l] < GT_STAGE) panel_unit<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
         if (wload) {
             const int64_t e = e0 + tid < last ? e0 + tid : last;
-            wreg = vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e];
+            wreg = csr_stored_val(vals, vt, e);
         }
 #pragma unroll
         for (int l = 0; l < NL; l++) {
@@ -136,15 +109,15 @@ __device__ __forceinline__ void gt_accumulate(int64_t e0, int64_t e1, const int3
                 for (int x = 0; x < PER; x++) sv[buf][ue[l]][uo[l] + x] = vreg[l][x];
             }
         if (wstage) sw[buf][tid] = wreg;
-        gt_team_sync<TEAM>();
+        team_sync<TEAM>();
         // the next step's V rows and weights and the column indices of the step after it, in flight while this one is used
         if (es + GT_STAGE < e1) {
 #pragma unroll
             for (int l = 0; l < NL; l++)
-                if (ue[l] < GT_STAGE) gt_load<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
+                if (ue[l] < GT_STAGE) panel_unit<T, PER>(V + (int64_t)coln[l] * ldv + uo[l], vreg[l]);
             if (wload) {
                 const int64_t e = es + GT_STAGE + tid < last ? es + GT_STAGE + tid : last;
-                wreg = vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (double)((const float *)vals)[e];
+                wreg = csr_stored_val(vals, vt, e);
             }
 #pragma unroll
             for (int l = 0; l < NL; l++) {
@@ -160,8 +133,8 @@ __device__ __forceinline__ void gt_accumulate(int64_t e0, int64_t e1, const int3
             const double c = rhs_mode == CSRK_ALS_RHS_ONES ? 1.0 : (rhs_mode == CSRK_ALS_RHS_VALUES ? wv : 1.0 + wv);
 #pragma unroll
             for (int r = 0; r < TPT; r++) {
-                const gt_d2 a0 = *(const gt_d2 *)&sv[buf][x][p0[r]], a1 = *(const gt_d2 *)&sv[buf][x][p0[r] + 2];
-                const gt_d2 b0 = *(const gt_d2 *)&sv[buf][x][q0[r]], b1 = *(const gt_d2 *)&sv[buf][x][q0[r] + 2];
+                const f64x2_t a0 = *(const f64x2_t *)&sv[buf][x][p0[r]], a1 = *(const f64x2_t *)&sv[buf][x][p0[r] + 2];
+                const f64x2_t b0 = *(const f64x2_t *)&sv[buf][x][q0[r]], b1 = *(const f64x2_t *)&sv[buf][x][q0[r] + 2];
                 const double vp[GT_B] = {a0.x, a0.y, a1.x, a1.y}, vq[GT_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                 for (int i = 0; i < GT_B; i++) {

@@ -32,6 +32,7 @@
 // bound of 4096 entries (59 KiB) would leave two workgroups per CU; rating rows above 2048 entries are rare in the data this
 // serves and the device-memory search takes them.
 // Column indices are compared, never used as addresses; every wavefront stays whole inside the loops that ballot and shuffle.
+#include "device_loads.h"
 #include "result.h"
 
 #include <functional>
@@ -68,14 +69,6 @@ struct KsArgs {
     int32_t *oc;
     double *ov;
 };
-
-// a value as the arithmetic sees it: float32 widened exactly, 1.0 for a structure-only operand
-__device__ __forceinline__ double ks_val(const void *v, int vt, int64_t e)
-{
-    if (vt == CSRK_VAL_F64) return ((const double *)v)[e];
-    if (vt == CSRK_VAL_F32) return (double)((const float *)v)[e];
-    return 1.0;
-}
 
 // The filter in front of the search: one bit per residue of the column modulo KS_BITS, set for every column of the rating
 // row.  A clear bit says the column is not rated; a set bit says "search".  (c & mask is a residue for any int32, so a
@@ -150,8 +143,8 @@ __device__ __forceinline__ void ks_fold(const KsArgs &g, const KsRow &row, const
             const bool hit = maybe[j] && col_at(lo) == c[j];
             double s = 0.0, v = 0.0;
             if (hit) {
-                s = ks_val(g.vm, g.vtm, ms[j] + e);
-                if (average) v = STAGED ? s_vals[lo] : ks_val(row.vals, g.vtr, row.start + lo);
+                s = csr_val(g.vm, g.vtm, ms[j] + e);
+                if (average) v = STAGED ? s_vals[lo] : csr_val(row.vals, g.vtr, row.start + lo);
             }
             uint32_t bits = (uint32_t)(__ballot(hit) >> gshift) & ((1u << KS_LANES) - 1);
             while (__any(bits != 0)) {                       // the whole wavefront shuffles; a group with no bit left idles
@@ -179,7 +172,7 @@ __device__ __forceinline__ void ks_fold(const KsArgs &g, const KsRow &row, const
 }
 
 // a target's value from its sums (rule 3 of the contract): one division, then the listed row's offset
-__device__ __forceinline__ double ks_value(const KsArgs &g, int64_t r, double num, double den)
+__device__ __forceinline__ double ks_score_of(const KsArgs &g, int64_t r, double num, double den)
 {
 #pragma clang fp contract(off)
     double x = g.aggregate == CSRK_KNN_WEIGHTED_AVERAGE ? num / den : num;
@@ -208,7 +201,7 @@ __device__ __forceinline__ void ks_walk(const KsArgs &g, const KsRow &row, int64
             for (int j = 0; j < KS_ILP; j++) {
                 const int q = (k * KS_ILP + j) * KS_GROUPS + grp;
                 s_flag[q] = nn[j] >= g.min_nbrs ? 1 : 0;
-                if (PLACE) s_score[q] = ks_value(g, r, num[j], den[j]);
+                if (PLACE) s_score[q] = ks_score_of(g, r, num[j], den[j]);
             }
         }
     }
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_scores_kernel(const KsArgs g, 
         atomicOr(&s_bits[ks_slot(c) >> 5], 1u << (ks_slot(c) & 31));      // (an integer OR in LDS: its order changes nothing)
         if (staged) {
             s_cols[j] = c;
-            if (average) s_vals[j] = ks_val(g.vr, g.vtr, rs + j);
+            if (average) s_vals[j] = csr_val(g.vr, g.vtr, rs + j);
         }
     }
     __syncthreads();
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_reach_kernel(const KrArgs a, i
         atomicOr(&s_bits[ks_slot(c) >> 5], 1u << (ks_slot(c) & 31));
         if (staged) {
             s_cols[j] = c;
-            if (average) s_vals[j] = ks_val(g.vr, g.vtr, rs + j);
+            if (average) s_vals[j] = csr_val(g.vr, g.vtr, rs + j);
         }
     }
     __syncthreads();
@@ -526,7 +519,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_reach_kernel(const KrArgs a, i
                 s_flag[q] = tgt[j] >= 0 && nn[j] >= g.min_nbrs ? 1 : 0;
                 if (PLACE) {
                     s_tgt[q] = (int32_t)tgt[j];
-                    s_score[q] = ks_value(g, r, num[j], den[j]);
+                    s_score[q] = ks_score_of(g, r, num[j], den[j]);
                 }
             }
         }

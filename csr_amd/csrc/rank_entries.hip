@@ -36,9 +36,6 @@ constexpr int RE_K_MAX = 1024;
 constexpr int32_t RE_BAD_ITEM = 0x7fffffff;     // listed for a test column outside [0, n_items): never dereferenced
 static_assert(RE_T <= WAVE, "one lane per listed entry");
 
-// does (key ka, item ja) come before (kb, jb) in csrk_topk_scores' order?
-__device__ __forceinline__ bool re_before(uint64_t ka, int32_t ja, uint64_t kb, int32_t jb) { return ka > kb || (ka == kb && ja < jb); }
-
 // csrk_topk_scores' rule 2 for one pair, straight from the panels
 template <class T> __device__ __forceinline__ double re_chain(const T *__restrict__ u, const T *__restrict__ v, int k)
 {
@@ -53,7 +50,7 @@ __device__ __forceinline__ int re_slot(const uint64_t *__restrict__ sk, const in
     int lo = 0, hi = n;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (re_before(ks, j, sk[mid], si[mid]))
+        if (key_before(ks, j, sk[mid], si[mid]))
             hi = mid;
         else
             lo = mid + 1;
@@ -135,7 +132,7 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
             for (int y = 0; y < n; y++) {
                 const uint64_t ky = s_key[r][y];
                 const int32_t iy = s_item[r][y];
-                rank += (re_before(ky, iy, key, item) || (ky == key && iy == item && y < lane)) ? 1 : 0;
+                rank += (key_before(ky, iy, key, item) || (ky == key && iy == item && y < lane)) ? 1 : 0;
             }
             // the wavefront has read the list before any lane rewrites it (LDS operations of one wavefront complete in issue order)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -192,8 +189,8 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
                 if (kc == TS_KC) {
 #pragma unroll
                     for (int t = 0; t < TS_KC; t++) {
-                        const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                        const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                        const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                        const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                         const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                         for (int i = 0; i < TS_B; i++)
@@ -202,8 +199,8 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
                     }
                 } else {
                     for (int t = 0; t < kc; t++) {
-                        const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                        const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                        const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                        const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                         const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                         for (int i = 0; i < TS_B; i++)
@@ -225,7 +222,7 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
                 for (int jj = 0; jj < TS_B; jj++) {
                     const int64_t j = j0 + TS_B * tx + jj;
                     const uint64_t ks = topk_key(acc[i][jj]);
-                    if (j < n_items && re_before(ks, (int32_t)j, lastk[i], lasti[i])) {
+                    if (j < n_items && key_before(ks, (int32_t)j, lastk[i], lasti[i])) {
                         const int r = TS_B * ty + i;
                         atomicAdd(&s_hist[r][re_slot(s_key[r], s_item[r], cnt[i], ks, (int32_t)j)], 1);      // (a slot < cnt[i]: it comes before the last)
                     }
@@ -244,7 +241,7 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
                     const int32_t j = seen_ci[e];
                     if (j < 0 || j >= n_items) continue;          // (no item: the sweep did not count it)
                     const uint64_t ks = topk_key(re_chain<T>(U + (r0 + r) * ldu, V + (int64_t)j * ldv, k));
-                    if (re_before(ks, j, lk, li)) atomicSub(&s_hist[r][re_slot(s_key[r], s_item[r], n, ks, j)], 1);
+                    if (key_before(ks, j, lk, li)) atomicSub(&s_hist[r][re_slot(s_key[r], s_item[r], n, ks, j)], 1);
                 }
             }
         __syncthreads();

@@ -104,7 +104,7 @@ __device__ __forceinline__ void ts_fetch_rows(TsUnits<T, PER> &u, const T *__res
         const int t = t0 + ((tid + l * TS_THREADS) % N::UPR) * PER;
 #pragma unroll
         for (int e = 0; e < PER; e++) u.d[l][e] = 0.0;
-        if (off[l] >= 0 && t < k) ts_load<T, PER>(P + off[l] + t, u.d[l]);
+        if (off[l] >= 0 && t < k) panel_unit<T, PER>(P + off[l] + t, u.d[l]);
     }
 }
 
@@ -187,8 +187,8 @@ __device__ __forceinline__ void ts_sweep(const void *__restrict__ rp, int ptr64,
             if (kc == TS_KC) {
 #pragma unroll
                 for (int t = 0; t < TS_KC; t++) {
-                    const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                    const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                    const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                    const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                     const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                     for (int i = 0; i < TS_B; i++)
@@ -197,8 +197,8 @@ __device__ __forceinline__ void ts_sweep(const void *__restrict__ rp, int ptr64,
                 }
             } else {
                 for (int t = 0; t < kc; t++) {
-                    const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                    const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                    const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                    const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                     const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                     for (int i = 0; i < TS_B; i++)

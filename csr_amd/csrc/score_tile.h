@@ -1,9 +1,12 @@
 // The score tile that topk_scores.hip and rank_entries.hip share: the constants of the register-tiled float64 product
-// (a 256-thread workgroup, 64 rows x 64 items per tile, 4 x 4 chains per thread, 16 factors per LDS chunk), the total
-// order of csrk_topk_rows as an integer key, the loads that bring a chunk of a panel into LDS transposed, and the lookup
-// of a column in a sorted row.  Both kernels run the same chains, so a score has the same bits in either.
+// (a 256-thread workgroup, 64 rows x 64 items per tile, 4 x 4 chains per thread, 16 factors per LDS chunk), the loads
+// that bring a chunk of a panel into LDS transposed, and the lookup of a column in a sorted row.  Both kernels run the
+// same chains, so a score has the same bits in either.  (The order they rank by: topk_order.h.  A unit of a panel row and
+// the sorted-row search: device_loads.h.)
 #pragma once
 #include "common.h"
+#include "device_loads.h"
+#include "topk_order.h"
 
 namespace csrk {
 
@@ -14,33 +17,6 @@ constexpr int TS_B = 4;                         // register tile edge
 constexpr int TS_KC = 16;                       // factors per LDS chunk
 constexpr int TS_LD = TS_ROWS + 2;              // doubles per staged line
 static_assert(TS_ROWS == TS_TILE && TS_ROWS * TS_TILE == TS_THREADS * TS_B * TS_B, "one 4 x 4 block of chains per thread");
-
-typedef double ts_d2 __attribute__((ext_vector_type(2)));
-typedef float ts_f4 __attribute__((ext_vector_type(4)));
-
-// csrk_topk_rows' order as an integer (topk.hip): NaN -> all ones, -0.0 -> +0.0, then the usual sign flip
-__device__ __forceinline__ uint64_t topk_key(double w)
-{
-    uint64_t b = (uint64_t)__double_as_longlong(w);
-    if (w != w) return ~0ull;                    // every NaN: above +Inf, all tied
-    if (w == 0.0) b = 0;                         // -0.0 ties with +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// one unit of a panel row as float64: PER elements (a 16-B piece when PER > 1, else one element)
-template <class T, int PER> __device__ __forceinline__ void ts_load(const T *__restrict__ p, double d[PER]);
-template <> __device__ __forceinline__ void ts_load<double, 1>(const double *__restrict__ p, double d[1]) { d[0] = *p; }
-template <> __device__ __forceinline__ void ts_load<float, 1>(const float *__restrict__ p, double d[1]) { d[0] = (double)*p; }
-template <> __device__ __forceinline__ void ts_load<double, 2>(const double *__restrict__ p, double d[2])
-{
-    const ts_d2 a = *(const ts_d2 *)p;
-    d[0] = a.x, d[1] = a.y;
-}
-template <> __device__ __forceinline__ void ts_load<float, 4>(const float *__restrict__ p, double d[4])
-{
-    const ts_f4 a = *(const ts_f4 *)p;
-    d[0] = (double)a.x, d[1] = (double)a.y, d[2] = (double)a.z, d[3] = (double)a.w;
-}
 
 // factors [t0, t0 + TS_KC) of the panel rows first .. first + 63, in two halves: ts_fetch loads this thread's units into
 // registers (rows at or beyond nvalid and factors at or beyond k become +0.0: such rows' chains are never looked at, such
@@ -62,7 +38,7 @@ __device__ __forceinline__ void ts_fetch(TsUnits<T, PER> &u, const T *__restrict
         const int x = tid + l * TS_THREADS, r = x / N::UPR, t = t0 + (x % N::UPR) * PER;
 #pragma unroll
         for (int e = 0; e < PER; e++) u.d[l][e] = 0.0;
-        if (r < nvalid && t < k) ts_load<T, PER>(P + (first + r) * ld + t, u.d[l]);      // (PER > 1: k is a whole number of pieces)
+        if (r < nvalid && t < k) panel_unit<T, PER>(P + (first + r) * ld + t, u.d[l]);      // (PER > 1: k is a whole number of pieces)
     }
 }
 
@@ -81,14 +57,7 @@ __device__ __forceinline__ void ts_put(const TsUnits<T, PER> &u, double (*__rest
 // does the sorted row ci[e0 .. e1) hold column j?  (indices are compared, never used as addresses)
 __device__ __forceinline__ bool ts_seen(const int32_t *__restrict__ ci, int64_t e0, int64_t e1, int32_t j)
 {
-    int64_t lo = e0, hi = e1;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (ci[mid] < j)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
+    const int64_t lo = first_not_below(ci, e0, e1, j);
     return lo < e1 && ci[lo] == j;
 }
 

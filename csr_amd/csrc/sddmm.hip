@@ -20,19 +20,22 @@
 // Order of addition (fixed: it depends on k and the panel dtype only -- not on the entry's position, its row's length,
 // the pointer width, the strides, the load form, the stream or the launch).  Lane l (0..15) of a group owns, in each
 // 64-column chunk c = 0, 1, ..., four panel columns (those below k): float64 64 c + {2 l, 2 l + 1, 32 + 2 l, 33 + 2 l},
-// float32 64 c + {4 l, .., 4 l + 3}.  Its partial sum starts at +0.0 and takes its columns in ascending order, one
+// float32 64 c + {4 l, .., 4 l + 3} (panel_off and panel_load4 in device_loads.h, which ALS-CG uses too).  Its partial
+// sum starts at +0.0 and takes its columns in ascending order, one
 // fused multiply-add each: s_l = fma(u_t, v_t, s_l).  (With float32 panels u_t and v_t are widened to float64 first;
 // their product is exact in float64, so each step is one rounding of s_l + u_t v_t.)  The 16 partials are then added
 // by the DPP tree of rows shifted right by 1, 2, 4, 8 (lane 15 of the row ends holding ((s_15 + s_14) + (s_13 + s_12))
 // + ... in that fixed shape).  With scale = 1 the value (float32 widened, 1.0 when there are none) multiplies the sum
 // once, after it.
 #include "common.h"
+#include "device_loads.h"
 #include "panel.h"
 #include "wave.h"
 
 namespace csrk {
 
 constexpr int SD_G = 16;                 // lanes per group (one DPP row)
+static_assert(SD_G == PANEL_G, "a group is the lanes that share a panel row (device_loads.h)");
 constexpr int SD_GROUPS = WAVE / SD_G;   // 4 groups per wavefront
 constexpr int SD_RUN = 64;               // consecutive entries per group
 constexpr int SD_THREADS = 256;
@@ -69,67 +72,14 @@ __device__ int64_t sd_find_row(const P *__restrict__ rp, int64_t lo, int64_t hi,
     return lo;
 }
 
-// A lane's four columns in a 64-column chunk are 16-B pieces of PIECE = 16 / sizeof(T) elements: float64 columns
-// 2 l, 2 l + 1, 32 + 2 l, 33 + 2 l; float32 columns 4 l .. 4 l + 3.  So each load instruction of a group reads one
-// contiguous 256-B span of a panel row.  Element q (0..3) of lane l:
-template <class T>
-__device__ __forceinline__ int sd_off(int sub, int q)
-{
-    constexpr int PIECE = 16 / (int)sizeof(T);
-    return (q / PIECE) * (SD_G * PIECE) + sub * PIECE + q % PIECE;
-}
-
-template <class T> struct SdVec;
-template <> struct SdVec<double> {
-    typedef double v2 __attribute__((ext_vector_type(2)));
-    typedef v2 v2u __attribute__((aligned(16)));
-    static __device__ __forceinline__ void piece(const double *p, double *d)
-    {
-        const v2 a = *(const v2u *)p;
-        d[0] = a.x, d[1] = a.y;
-    }
-};
-template <> struct SdVec<float> {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    typedef v4 v4u __attribute__((aligned(16)));
-    static __device__ __forceinline__ void piece(const float *p, float *d)
-    {
-        const v4 a = *(const v4u *)p;
-        d[0] = a.x, d[1] = a.y, d[2] = a.z, d[3] = a.w;
-    }
-};
-
-// the lane's four elements of one 64-column chunk of a panel row (p = the chunk's first column; kk = columns left from
-// it); columns at or past k read as 0 and are never added.  WIDE: 16-B loads for whole pieces (aligned by the caller).
-template <class T, bool WIDE>
-__device__ __forceinline__ void sd_load4(const T *__restrict__ p, int sub, int kk, T d[4])
-{
-    constexpr int PIECE = 16 / (int)sizeof(T);
-#pragma unroll
-    for (int q0 = 0; q0 < 4; q0 += PIECE) {
-        const int o = sd_off<T>(sub, q0);
-        if (WIDE && o + PIECE <= kk) {
-            SdVec<T>::piece(p + o, d + q0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < PIECE; i++) d[q0 + i] = o + i < kk ? p[o + i] : (T)0;
-        }
-    }
-}
-
 // the fixed order of addition (header comment): a lane's partial over its columns, then the group's DPP tree
 template <class T>
 __device__ __forceinline__ double sd_partial(double s, const T u[4], const T v[4], int sub, int kk)
 {
 #pragma unroll
     for (int q = 0; q < 4; q++)
-        if (sd_off<T>(sub, q) < kk) s = __builtin_fma((double)u[q], (double)v[q], s);
+        if (panel_off<T>(sub, q) < kk) s = __builtin_fma((double)u[q], (double)v[q], s);
     return s;
-}
-// the value of entry e as float64 (vt = CSRK_VAL_NONE: 1.0, nothing read)
-__device__ __forceinline__ double sd_val(const void *__restrict__ vals, int vt, int64_t e)
-{
-    return vt == CSRK_VAL_F64 ? ((const double *)vals)[e] : (vt == CSRK_VAL_F32 ? (double)((const float *)vals)[e] : 1.0);
 }
 
 __device__ __forceinline__ double sd_group_sum(double s)      // lane 15 of the group gets the sum
@@ -205,7 +155,7 @@ __global__ __launch_bounds__(SD_THREADS) void sddmm_kernel(const P *__restrict__
                 if (row[x] != prev) {                     // group-uniform: a new row's U
 #pragma unroll
                     for (int c = 0; c < NC; c++)
-                        sd_load4<T, WIDE>(U + (int64_t)row[x] * ldu + 64 * c, sub, k - 64 * c, uw[x][c]);
+                        panel_load4<T, WIDE>(U + (int64_t)row[x] * ldu + 64 * c, sub, k - 64 * c, uw[x][c]);
                 } else {
 #pragma unroll
                     for (int c = 0; c < NC; c++)
@@ -217,10 +167,10 @@ __global__ __launch_bounds__(SD_THREADS) void sddmm_kernel(const P *__restrict__
             for (int x = 0; x < UN; x++)
 #pragma unroll
                 for (int c = 0; c < NC; c++)
-                    sd_load4<T, WIDE>(V + (int64_t)col[x] * ldv + 64 * c, sub, k - 64 * c, v[x][c]);
+                    panel_load4<T, WIDE>(V + (int64_t)col[x] * ldv + 64 * c, sub, k - 64 * c, v[x][c]);
 #pragma unroll
             for (int x = 0; x < UN; x++) {
-                a[x] = sd_val(vals, vt, e + x < e1 ? e + x : e1 - 1);      // (in flight with the V rows)
+                a[x] = csr_val(vals, vt, e + x < e1 ? e + x : e1 - 1);      // (in flight with the V rows)
                 coln[x] = ci[e + UN + x < e1 ? e + UN + x : e1 - 1];
             }
 #pragma unroll
@@ -235,15 +185,15 @@ __global__ __launch_bounds__(SD_THREADS) void sddmm_kernel(const P *__restrict__
         } else {
 #pragma unroll
             for (int x = 0; x < UN; x++) {
-                a[x] = sd_val(vals, vt, e + x < e1 ? e + x : e1 - 1);      // (in flight with the V rows)
+                a[x] = csr_val(vals, vt, e + x < e1 ? e + x : e1 - 1);      // (in flight with the V rows)
                 coln[x] = ci[e + UN + x < e1 ? e + UN + x : e1 - 1];
             }
             for (int c = 0; c < nchunks; c++) {
                 T v[UN][4], w[UN][4];
 #pragma unroll
                 for (int x = 0; x < UN; x++) {
-                    sd_load4<T, WIDE>(V + (int64_t)col[x] * ldv + 64 * c, sub, k - 64 * c, v[x]);
-                    sd_load4<T, WIDE>(U + (int64_t)row[x] * ldu + 64 * c, sub, k - 64 * c, w[x]);
+                    panel_load4<T, WIDE>(V + (int64_t)col[x] * ldv + 64 * c, sub, k - 64 * c, v[x]);
+                    panel_load4<T, WIDE>(U + (int64_t)row[x] * ldu + 64 * c, sub, k - 64 * c, w[x]);
                 }
 #pragma unroll
                 for (int x = 0; x < UN; x++) acc[x] = sd_partial<T>(acc[x], w[x], v[x], sub, k - 64 * c);

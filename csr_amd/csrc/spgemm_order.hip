@@ -19,6 +19,7 @@
 // Values are not touched: each keeps the bits the product kernels gave it.  tests/test_gpu_ops.py compares the result
 // with the reference's own raw arrays (tests/golden/spgemm.npz, c*_raw_*) bit for bit.
 #include "common.h"
+#include "device_loads.h"
 
 #include <algorithm>
 #include <atomic>
@@ -111,13 +112,7 @@ __global__ __launch_bounds__(256) void so_list_rows_kernel(const int64_t *__rest
 template <class T>
 __device__ __forceinline__ int32_t so_find(const T *cols, int32_t n, int32_t k)
 {
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (cols[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return first_not_below(cols, (int32_t)0, n, k);
 }
 
 // The rows of fewer than SO_WAVE products -- 99.6 % of the rows of a sparse product: SUB lanes per row (sixteen: four rows per

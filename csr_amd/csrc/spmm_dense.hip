@@ -18,6 +18,7 @@
 // round trips (segment -> row pointer -> entries -> B rows -> store) that only wavefront count hid.  Segment
 // partial panels are combined in segment order by a second kernel -- no float atomics, bitwise reproducible.
 #include "common.h"
+#include "device_loads.h"
 #include "panel.h"
 
 #include <algorithm>
@@ -105,15 +106,6 @@ int64_t spmm_plan_bytes(const SpmmPlan *p)
     return b;
 }
 
-template <int VT>
-__device__ __forceinline__ double mm_val(const void *v, int64_t k)
-{
-    if (VT == CSRK_VAL_F64) return ((const double *)v)[k];
-    if (VT == CSRK_VAL_F32) return (double)((const float *)v)[k];
-    return 1.0;
-}
-
-
 typedef double mm_f64x2 __attribute__((ext_vector_type(2)));
 typedef mm_f64x2 MMF64x2 __attribute__((aligned(8)));
 
@@ -141,7 +133,7 @@ __device__ __forceinline__ void mm_unit(const int32_t *__restrict__ ci, const vo
     for (int base = 0; base < nmax; base += MM_G) {
         const int idx = base + sub;
         const int32_t mycol = idx < n ? ci[s + idx] : 0;
-        const double myval = idx < n ? mm_val<VT>(vs, s + idx) : 0.0;
+        const double myval = idx < n ? csr_val<VT>(vs, s + idx) : 0.0;
         const int nb = nmax - base < MM_G ? nmax - base : MM_G;
         for (int j = 0; j < nb; j += MM_UNROLL) {
             double b[MM_UNROLL][4], av[MM_UNROLL];
@@ -485,7 +477,7 @@ __global__ __launch_bounds__(256) void hr_emit_kernel(const P *__restrict__ rp, 
         const int32_t c = ci[q];
         key[o + q - s] = ((c / HR_TILE) * G + g) * HR_WAVES + w;
         payload[o + q - s] = (slot << 1) | ((c % HR_TILE) << 9);      // (see spmm_hrows_kernel)
-        val[o + q - s] = mm_val<VT>(vs, q);
+        val[o + q - s] = csr_val<VT>(vs, q);
     }
 }
 

@@ -1206,7 +1206,7 @@ __global__ __launch_bounds__(256) void spmv_vector_kernel(const P *__restrict__ 
     int64_t e = (int64_t)rp[r + 1];
     if (e > s + VEC_SEG && nseg > 1) e = s + VEC_SEG;
     double acc = 0.0;
-    for (int64_t k = s + lane; k < e; k += WAVE) acc += x[ci[k]] * ValLoad<VT>::at(vs, k);
+    for (int64_t k = s + lane; k < e; k += WAVE) acc += x[ci[k]] * csr_val<VT>(vs, k);
     acc = wave_sum(acc);
     if (lane == 0) {
         if (nseg == 1)
@@ -1238,7 +1238,7 @@ __global__ __launch_bounds__(256) void spmv_scalar_kernel(const P *__restrict__ 
     if (r >= nrows) return;
     int64_t s = rp[r], e = rp[r + 1];
     double acc = 0.0;
-    for (int64_t k = s; k < e; k++) acc += spmv_prod<R32>(ValLoad<VT>::at(vs, k), x[ci[k]]);
+    for (int64_t k = s; k < e; k++) acc += spmv_prod<R32>(csr_val<VT>(vs, k), x[ci[k]]);
     y[r] = acc;
 }
 

@@ -3,6 +3,7 @@
 // tile / stream layout constants and the slot arithmetic both sides must agree on.
 #pragma once
 #include "common.h"
+#include "device_loads.h"
 #include "wave.h"
 #include "fix56.h"
 #include "acc_groups.h"
@@ -11,18 +12,6 @@
 #include <vector>
 
 namespace csrk {
-
-// ---- value loads ------------------------------------------------------------------------
-template <int VT> struct ValLoad;
-template <> struct ValLoad<CSRK_VAL_F64> {
-    static __device__ __forceinline__ double at(const void *v, int64_t k) { return ((const double *)v)[k]; }
-};
-template <> struct ValLoad<CSRK_VAL_F32> {
-    static __device__ __forceinline__ double at(const void *v, int64_t k) { return (double)((const float *)v)[k]; }
-};
-template <> struct ValLoad<CSRK_VAL_NONE> {
-    static __device__ __forceinline__ double at(const void *, int64_t) { return 1.0; }
-};
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -212,9 +201,6 @@ constexpr int MERGE_ITEMS = MERGE_THREADS * MERGE_IPT;   // 2048 path items per 
 constexpr int MERGE_LONG = 64;                           // rows this long get a whole wave
 constexpr int MERGE_MAXLONG = MERGE_ITEMS / MERGE_LONG + 2;
 
-typedef int32_t i32x2_t __attribute__((ext_vector_type(2)));
-typedef double f64x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef i32x2_t I32x2 __attribute__((aligned(4)));
 typedef f64x2_t F64x2 __attribute__((aligned(4)));
 typedef f32x2_t F32x2 __attribute__((aligned(4)));
@@ -326,9 +312,6 @@ struct AccLaunchArgs {
     const uint32_t *wg_map;      // nullptr: one group, block b is its workgroup b
 };
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-
 // physical slot of logical entry e (0..511) of a tile: lane = e / 8, j = e % 8
 __host__ __device__ __forceinline__ int acc_val_slot(int e)
 {
@@ -348,7 +331,6 @@ template <class SV> __host__ __device__ __forceinline__ int acc_slot_of(int e)
 
 // a lane's eight values of a tile: float64 four 16-B loads, float32 (a float32 matrix's stream) two, widened on use; get(a, g): g is
 // the grid exponent of a fix56 tile (the other forms ignore it)
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 template <class SV> struct AccVals;
 template <> struct AccVals<double> {
     f64x2_t v[4];

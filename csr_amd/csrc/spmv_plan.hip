@@ -414,7 +414,7 @@ __global__ void panel_fill_kernel(const P *__restrict__ rp, const int32_t *__res
     int64_t o = off[i];
     for (int64_t k = lo; k < lo + n; k++, o++) {
         pci[o] = ci[k];
-        pvs[o] = ValLoad<VT>::at(vs, k);
+        pvs[o] = csr_val<VT>(vs, k);
     }
 }
 
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256) void acc_fill_kernel(const P *__restrict__ rp,
             const int64_t k = lo_p + (at - npad_p);
             // the pair's first entry: the step from the previous row (or the last padding entry) to this row
             const uint32_t step_in = at == npad_p ? (uint32_t)(g_p - ACC_MAXSTEP * npad_p) : 0u;
-            acc_put<SV, VERIFY>(pvals, pidx, pt, el, ValLoad<VT>::at(vs, k), (uint32_t)(ci[k] - b * cb), el ? step_in : 0u, fx_g,
+            acc_put<SV, VERIFY>(pvals, pidx, pt, el, csr_val<VT>(vs, k), (uint32_t)(ci[k] - b * cb), el ? step_in : 0u, fx_g,
                                 mismatch);
             if (VERIFY) continue;
             if (el == 0) tile_row0[t] = c0 + p;
@@ -862,7 +862,7 @@ __global__ __launch_bounds__(256) void ls_fill_kernel(const P *__restrict__ src,
             ix = LS_PAD | LS_START_BIT;
         } else {
             const int64_t a = (int64_t)src[r] + (L - first);
-            v = ValLoad<VT>::at(vs, a);
+            v = csr_val<VT>(vs, a);
             const int32_t c = ci[a];
             const int32_t sl = slot_map ? slot_map[c] : -1;         // slot of a packed column
             ix = sl >= 0 ? (LS_HOT_BIT | (uint32_t)sl) : (uint32_t)c;

@@ -1,10 +1,10 @@
 // Row top-k of libcsrk on gfx950: csrk_topk_rows keeps, in every row, the k largest entries that pass a threshold
 // (the contract is in include/csrk.h).  Selection and copying only: no arithmetic touches a value.
 //
-// The order is a KEY: a value becomes a 64-bit unsigned integer that sorts like the contract's total order (NaN -> all
-// ones, -0.0 -> +0.0, then the usual sign flip; float32 is widened exactly first), and an entry beats another when its key
-// is larger, or equal with an earlier position in the row.  An entry that fails the threshold gets key 0, below every real
-// key (the smallest is -Inf's, 0x000fffffffffffff).
+// The order is a KEY (topk_order.h): a value becomes a 64-bit unsigned integer that sorts like the contract's total order
+// (NaN -> all ones, -0.0 -> +0.0, then the usual sign flip; float32 is widened exactly first), and an entry beats another
+// when its key is larger, or equal with an earlier position in the row.  An entry that fails the threshold gets key 0,
+// below every real key (the smallest is -Inf's, 0x000fffffffffffff).
 //
 // Three row classes:
 //   short   1 .. 64 entries     one WAVEFRONT per row, one entry per lane: an entry's rank is the number of entries that beat
@@ -27,6 +27,7 @@
 // the input).  When every row keeps its bound the bounded arrays ARE the result.
 // No float atomic, no unordered append decides a winner or its place: the result is a function of the inputs.
 #include "result.h"
+#include "topk_order.h"
 #include "wave.h"
 
 namespace csrk {
@@ -40,14 +41,6 @@ constexpr int TK_BITS = 11;             // radix-select digit
 constexpr int TK_BINS = 1 << TK_BITS;
 constexpr int TK_UNROLL = 4;             // entries a thread of the long class loads before it uses the first
 constexpr uint32_t TK_ALL = 0xffffffffu;          // "every tie is taken"
-
-__device__ __forceinline__ uint64_t topk_key(double w)
-{
-    uint64_t b = (uint64_t)__double_as_longlong(w);
-    if (w != w) return ~0ull;                    // every NaN: above +Inf, all tied
-    if (w == 0.0) b = 0;                         // -0.0 ties with +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int lane)      // `lane` uniform over the wavefront
 {
@@ -130,12 +123,6 @@ __global__ __launch_bounds__(256) void topk_short_kernel(const P *__restrict__ r
 }
 
 // ---- long rows ----------------------------------------------------------------------------------------------------------
-// a beats b
-__device__ __forceinline__ bool topk_before(uint64_t ka, uint32_t pa, uint64_t kb, uint32_t pb)
-{
-    return ka > kb || (ka == kb && pa < pb);
-}
-
 // Bitonic network in the form whose comparators all point the same way (the first step of a merge pairs i with its mirror
 // in the block, i ^ (size - 1); the others i with i ^ j): the better record always goes to the lower index, so n need not
 // be a power of two -- the slots from n up to the next power of two stand for records worse than any, which no comparator
@@ -162,7 +149,7 @@ __device__ __forceinline__ void topk_bitonic(KP key, PP pos, int n, int tid)
                 if (l < n) {
                     const uint64_t ki = key[i], kl = key[l];
                     const uint32_t pi = pos[i], pl = pos[l];
-                    if (topk_before(kl, pl, ki, pi)) {
+                    if (key_before(kl, pl, ki, pi)) {
                         key[i] = kl;
                         pos[i] = pl;
                         key[l] = ki;

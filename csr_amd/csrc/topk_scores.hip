@@ -12,7 +12,7 @@
 // one fused multiply-add per factor, float32 widened exactly first.  Nothing is summed in pieces.
 //
 // Selection.  A row's running list lives in LDS: up to CAP (score bits, item) pairs, of which the first cnt are in use, and a
-// threshold thr = the key (topk.hip's topk_key, restated below) of the row's n_top-th best at its last compaction, 0 while
+// threshold thr = the key (topk_key of topk_order.h) of the row's n_top-th best at its last compaction, 0 while
 // fewer than n_top are known.  After a tile a score SURVIVES when its item exists, it does not fail min_score, its key is
 // above thr (items arrive in ascending order, so on equal keys the listed, smaller item wins) and `seen` does not store the
 // pair (a binary search of the row's sorted columns, made only for scores that got this far).  Most tiles of a long sweep
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_kernel(const void *__r
             if (kc == TS_KC) {
 #pragma unroll
                 for (int t = 0; t < TS_KC; t++) {
-                    const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                    const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                    const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                    const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                     const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                     for (int i = 0; i < TS_B; i++)
@@ -116,8 +116,8 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_kernel(const void *__r
                 }
             } else {
                 for (int t = 0; t < kc; t++) {
-                    const ts_d2 a0 = *(const ts_d2 *)&su[t][TS_B * ty], a1 = *(const ts_d2 *)&su[t][TS_B * ty + 2];
-                    const ts_d2 b0 = *(const ts_d2 *)&sv[t][TS_B * tx], b1 = *(const ts_d2 *)&sv[t][TS_B * tx + 2];
+                    const f64x2_t a0 = *(const f64x2_t *)&su[t][TS_B * ty], a1 = *(const f64x2_t *)&su[t][TS_B * ty + 2];
+                    const f64x2_t b0 = *(const f64x2_t *)&sv[t][TS_B * tx], b1 = *(const f64x2_t *)&sv[t][TS_B * tx + 2];
                     const double u[TS_B] = {a0.x, a0.y, a1.x, a1.y}, v[TS_B] = {b0.x, b0.y, b1.x, b1.y};
 #pragma unroll
                     for (int i = 0; i < TS_B; i++)

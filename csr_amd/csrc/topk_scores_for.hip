@@ -45,9 +45,6 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_for_kernel(const void 
                            min_score, items, ldi, scores, lds, counts, work, split, n_splits);
 }
 
-// does the entry (key ke, item ie) come before (key kx, item ix) in rule 4's order?
-__device__ __forceinline__ bool tsf_before(uint64_t ke, int32_t ie, uint64_t kx, int32_t ix) { return ke > kx || (ke == kx && ie < ix); }
-
 __global__ __launch_bounds__(TSF_MERGE_THREADS) void topk_scores_for_merge_kernel(const int32_t *__restrict__ rows, int64_t n_rows,
                                                                                  int32_t u_rows, int32_t n_top, int n_splits,
                                                                                  const void *__restrict__ work, int32_t *__restrict__ items,
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(TSF_MERGE_THREADS) void topk_scores_for_merge_kerne
                 int lo = 0, hi = cnt[t] < n_top - place ? cnt[t] : n_top - place;      // (beyond n_top no place matters)
                 while (lo < hi) {
                     const int mid = lo + ((hi - lo) >> 1);
-                    if (tsf_before(topk_key(__longlong_as_double((long long)ws.sc[base + mid])), ws.it[base + mid], key, item))
+                    if (key_before(topk_key(__longlong_as_double((long long)ws.sc[base + mid])), ws.it[base + mid], key, item))
                         lo = mid + 1;
                     else
                         hi = mid;

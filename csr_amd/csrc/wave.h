@@ -85,4 +85,17 @@ __device__ __forceinline__ double wave_segscan(double v, bool reset, int /*lane*
     return v;
 }
 
+// A team of TEAM threads (a workgroup, or an aligned part of one wavefront; a team never spans workgroups): its threads
+// have all written their LDS words before any of them reads.
+template <int TEAM> __device__ __forceinline__ void team_sync()
+{
+    if constexpr (TEAM > 64) {
+        __syncthreads();
+    } else {      // within one wavefront LDS operations complete in issue order: order the compiler and the counters
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
 }  // namespace csrk

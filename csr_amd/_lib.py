@@ -109,6 +109,10 @@ SIGNATURES = {
     'csrk_als_rows_cg_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _int, _vp, C.c_double, C.c_double, _i32,
                                        C.c_double, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'csrk_als_cg_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_als_cg_set_long': (_int, [_i64]),
+    'csrk_als_cg_get_long': (_int, [C.POINTER(_i64)]),
+    'csrk_als_cg_long_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_als_cg_last_stats': (_int, [C.POINTER(_i64), _int]),
     'csrk_topk_scores': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp, _i64,
                                 _vp]),
     'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,

@@ -433,7 +433,9 @@ class CSR:
         lower triangle is read and mirrored, as als_rows reads it, so both solvers see the same matrix.  Every output is
         a fixed chain of fused multiply-adds (include/csrk.h, csrk_als_rows_cg): the same bits whatever the launch.
         With return_info=True (U, resid, taken) comes back: the squared residual of the recurrence at each row's stop and
-        the steps it made.  Not a reference entry point.
+        the steps it made.  A row of at least L entries takes a whole workgroup instead of 16 lanes
+        (kernels.hip.als_cg_set_long(L), or the environment variable CSRK_ALS_CG_LONG; 0 turns that off;
+        kernels.hip.als_cg_last_stats() counts such rows): it changes the time, never a bit.  Not a reference entry point.
         """
         K, fn = self._ext('als_rows_cg')
         _, _, _, _, rb, re_, base, _, lam, lam_n, steps, _, x0 = K.als_cg_args(self, V, rhs, base, reg, reg_per_entry, rows, steps, x0,

@@ -939,6 +939,43 @@ def als_cg_limits():
     return _limits(lib.csrk_als_cg_limits, 3)
 
 
+def als_cg_long_limits():
+    """
+    the long-row class of als_rows_cg (include/csrk.h, rule C11): (default L, threads of a long row's workgroup, S = rows
+    whose lengths one workgroup scans, C for float64 k <= 64, float64 k <= 128, float32 k <= 64, float32 k <= 128 = entries
+    of one chunk of the row's LDS image, image buffers)
+    """
+    return _limits(lib.csrk_als_cg_long_limits, 8)
+
+
+def als_cg_set_long(entries):
+    """
+    From how many entries a row of als_rows_cg takes a whole workgroup: an integer >= 1; 0 turns the class off; None (or
+    -1) follows the environment variable CSRK_ALS_CG_LONG (a decimal count; unset: the default).  Process-wide.  No result
+    bit depends on it.
+    """
+    if entries is None:
+        entries = -1
+    if not _is_int(entries) or entries < -1 or entries > 2 ** 63 - 1:
+        raise ValueError(f'entries must be None, -1, 0 or a count of at least 1, not {entries!r}')
+    check(lib.csrk_als_cg_set_long(int(entries)))
+
+
+def als_cg_get_long():
+    "the L in force: a row of at least that many entries is a long row of als_rows_cg; 0: the class is off"
+    v = C.c_int64(0)
+    check(lib.csrk_als_cg_get_long(C.byref(v)))
+    return v.value
+
+
+def als_cg_last_stats():
+    """
+    what this thread's last als_rows_cg did (include/csrk.h, csrk_als_cg_last_stats): (1 if it launched, the L in force,
+    1 if the long rows' launch was issued, its workgroups, the rows it solved, their entries); all 0 after a refused call
+    """
+    return _limits(lib.csrk_als_cg_last_stats, 6)
+
+
 def als_cg_args(h, V, rhs='values', base=None, lam=0.0, lam_n=0.0, rows=None, steps=3, x0=None, tol=0.0):
     """
     als_args' tuple (with the constant ridge lam before lam_n) + (steps, tol2, x0); ValueError for anything the library

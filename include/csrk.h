@@ -478,6 +478,13 @@ CSRK_API int csrk_als_limits(int64_t *out, int n);
  *   C10. A hazard, not a special case.  With tol2 = 0 and steps far past convergence the residual walks into the
  *       subnormals, where pq can reach 0 before rs does and IEEE gives Inf.  (k = 1, M = 12.75, b = 8 never reaches
  *       rs = 0: after 5 steps rs = 1.7e-167.)  Callers who ask for many steps pass a tol2.
+ *   C11. Long rows.  A row of at least L entries (csrk_als_cg_set_long below; L = 0: no row) is a long row: a whole
+ *       workgroup takes it instead of one team -- several teams take the d_e, which are independent of one another, one
+ *       wavefront the chains into q_t and b_t in storage order.  C8 already covers it: the launch geometry changes no
+ *       bit, so out, resid and taken are the same with the class on, off, or at any L.  The device form issues up to two
+ *       launches on `stream`, the long rows' first (workgroup g scans the lengths of rows [g S, (g + 1) S) of the range
+ *       and solves the long ones among them); it still allocates nothing and never synchronises.  C7's in-place rule
+ *       holds: a long row's x0 is read by the workgroup that later writes its out, and no team touches that row.
  *   Limits (csrk_als_cg_limits): out[0] = the largest k (at least 128); [1] = the lanes of a row's team; [2] = the entries a
  *   team has in flight per step of its entry loop;  n <= 3.  No device is touched.
  * Host form: host pointers in and out (panels cross packed; synchronous). */
@@ -491,6 +498,22 @@ CSRK_API int csrk_als_rows_cg_device(csrk_handle_t h, int32_t row_begin, int32_t
                                      double lam_n, int32_t steps, double tol2, const double *d_x0, int64_t ldx0,
                                      double *d_out, int64_t ldo, double *d_resid, int32_t *d_taken, void *stream);
 CSRK_API int csrk_als_cg_limits(int64_t *out, int n);
+/* The long-row class of rule C11.  Process-wide, like csrk_spgemm_set_order: entries >= 1: a row of at least that many
+ * entries is a long row; 0: the class is off (one launch, as without the class); -1: follow the environment variable
+ * CSRK_ALS_CG_LONG (a decimal count; unset, or not a count: the default, csrk_als_cg_long_limits' out[0]).  Anything below
+ * -1 is CSRK_ERR_INVALID and changes nothing.  csrk_als_cg_get_long: the L in force (0 = off).  No device is touched. */
+CSRK_API int csrk_als_cg_set_long(int64_t entries);
+CSRK_API int csrk_als_cg_get_long(int64_t *entries);
+/* out[0] = the default L; [1] = the threads of a long row's workgroup; [2] = S, the rows of the range whose lengths one
+ * workgroup scans; [3..6] = C, the entries of one chunk of the row's LDS image, for (float64 panel, k <= 64), (float64,
+ * k <= 128), (float32, k <= 64), (float32, k <= 128); [7] = the image's buffers (2);  n <= 8.  No device is touched. */
+CSRK_API int csrk_als_cg_long_limits(int64_t *out, int n);
+/* The calling thread's last csrk_als_rows_cg[_device], all 0 after a refused or failed call: out[0] = 1 when it launched
+ * (there were rows); [1] = the L in force (0 = off); [2] = 1 when the long rows' launch was issued (L > 0, rows, and the
+ * matrix has entries); [3] = its workgroups; [4] = the rows it solved and [5] = their entries, counted on the device
+ * (one integer atomic add per row) and read back by the host form -- the device form never synchronises and reports -1
+ * in both when it issued the launch;  n <= 6. */
+CSRK_API int csrk_als_cg_last_stats(int64_t *out, int n);
 
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).

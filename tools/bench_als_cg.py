@@ -13,6 +13,11 @@ relative 2-norm distance of each row's CG result to the exact solve (median and 
 with info = 0), the steps taken, CG twice: equal bits; and the time of the longest row alone (a row range of one row: the tail
 one team walks serially).  Each case runs in a child process of its own under `timeout -k 10`; the parent prints one JSON line.
     python tools/bench_als_cg.py [--cases k64f64,...] [--steps 20] [--steps-exact 5] [--warmup 2] [--scale 1.0] [--max-degree N]
+    python tools/bench_als_cg.py --long 1024,2048,4096,8192,16384 [--max-degree N] [--out profiles/r30_als_cg_long.json]
+                                              the same table with the long-row class (include/csrk.h, rule C11) off and on at each
+                                              L, in one process per case: the CG launch, the longest row alone, equal bits with
+                                              the class off, the census.  Without --max-degree both patterns run: configs[2] and
+                                              the one with the longest row capped at 2 000.  One JSON document goes to --out.
     python tools/bench_als_cg.py --sweeps     5 alternating sweeps on a 20 000 x 20 000 pattern at k = 64: the ALS objective per
                                               sweep for exact sweeps and for CG sweeps (warm, steps 1, 2, 3, 5)
 """
@@ -50,8 +55,9 @@ def _timed(fn, steps, warmup):
             'q75_ms': round(float(q[3]), 3), 'max_ms': round(float(q[4]), 3), 'steps': steps, 'warmup': warmup}
 
 
-def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1):
+def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1, longs=None):
     import torch
+    from csr_amd.kernels import hip as K
     from csr_amd import synth
     from csr_amd._lib import lib, check, handle_t, VAL_F32, VAL_F64, ALS_RHS_VALUES, ALS_RHS_ONE_PLUS
     k, panel = int(case[1:-3]), case[-3:]
@@ -111,6 +117,8 @@ def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1):
                                               None if x0 is None else x0[rb:].data_ptr(), k, Uc[rb:].data_ptr(), k, resid[rb:].data_ptr(),
                                               taken[rb:].data_ptr(), sp))
 
+        if longs is not None:
+            K.als_cg_set_long(0)                                 # the class off: the launch without the class, the base of every column
         c = _timed(in_side(cg), steps, warmup)
         first = Uc.clone()
         in_side(cg)()
@@ -126,6 +134,24 @@ def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1):
         # the longest row alone: what one team walks serially (steps + 1 passes, or steps + 2 warm), against the exact route's
         tail_cg = _timed(in_side(lambda: cg(longest, longest + 1)), max(3, steps // 4), 1)
         tail_exact = _timed(in_side(lambda: exact(longest, longest + 1)), max(3, steps_exact // 2), 1)
+        by_long = None
+        if longs is not None:
+            # the class on at each L: the whole launch, the longest row alone, the bits against the class off, the census
+            by_long = {}
+            keep = (Uc.clone(), resid.clone(), taken.clone())
+            for L in longs:
+                K.als_cg_set_long(L)
+                cl = _timed(in_side(cg), steps, warmup)
+                torch.cuda.synchronize()
+                same = all(bool(torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a, b.view(torch.int64) if b.dtype == torch.float64 else b))
+                           for a, b in zip(keep, (Uc, resid, taken)))
+                tl = _timed(in_side(lambda: cg(longest, longest + 1)), max(3, steps // 4), 1)
+                in_side(cg)()
+                st = K.als_cg_last_stats()
+                by_long[str(L)] = {'cg_steps3': cl, 'longest_row_cg_ms': tl, 'same_bits_as_off': same, 'workgroups': st[3],
+                                   'long_rows': int((lens >= L).sum()), 'long_entries': int(lens[lens >= L].sum())}
+            K.als_cg_set_long(0)
+            del keep
         out[name] = {'cg_steps3': c, 'exact_als_rows': e, 'exact_over_cg': round(e['median_ms'] / c['median_ms'], 2),
                      'cg_repeat_bitwise': repeat, 'exact_info_nonzero_rows': int((~good).sum()),
                      'taken_min': int(taken.min()), 'taken_max': int(taken.max()),
@@ -133,7 +159,11 @@ def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1):
                                                'rows_not_finite': int((~torch.isfinite(rel)).sum())},
                      'rel_distance_of_x0_to_exact_median': None if d0 is None else float(d0.median()),
                      'longest_row': {'entries': int(lens[longest]), 'cg_ms': tail_cg, 'exact_ms': tail_exact}}
+        if by_long is not None:
+            out[name]['long'] = by_long
         del x0
+    if longs is not None:
+        K.als_cg_set_long(None)
     check(lib.csrk_free(h))
     mean_len = float(lens.double().mean())
     return {'case': case, 'k': k, 'panel': panel, 'lambda': lam, 'nrows': n, 'nnz': nnz, 'max_degree': max_degree, 'cg_steps': CG_STEPS,
@@ -141,7 +171,8 @@ def child(case, steps, steps_exact, warmup, scale_n, max_degree, lam=0.1):
             'per_row': {'mean_entries': round(mean_len, 2), 'fma_cg_no_base': round((CG_STEPS + 1) * mean_len * 2 * k, 1),
                         'fma_cg_with_base': round((CG_STEPS + 1) * (mean_len * 2 * k + k * k), 1),
                         'fma_exact': round(mean_len * (k * (k + 1) / 2 + k) + k ** 3 / 6 + k * k, 1)},
-            'parity': {'ok': all(r['cg_repeat_bitwise'] for r in out.values())}}
+            'parity': {'ok': all(r['cg_repeat_bitwise'] and all(v['same_bits_as_off'] for v in r.get('long', {}).values())
+                                 for r in out.values())}}
 
 
 def sweeps(n=20000, nnz=500000, k=64, lam=0.1, n_sweeps=5):
@@ -185,15 +216,20 @@ def main():
     ap.add_argument('--steps-exact', type=int, default=5, help='repetitions of the exact route')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--scale', type=float, default=1.0, help='matrix size relative to configs[2]')
-    ap.add_argument('--max-degree', type=int, default=250_000, help='longest row of the pattern (configs[2]: 250 000); a smaller cap\n'
+    ap.add_argument('--max-degree', type=int, default=None, help='longest row of the pattern (configs[2]: 250 000); a smaller cap\n'
                     'takes the long-row tail out of both routes and shows the rate of the bulk')
+    ap.add_argument('--long', default=None, help='L[,L...]: time the long-row class off and on at each L')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r30_als_cg_long.json'), help='where --long writes its document')
     ap.add_argument('--child-timeout', type=int, default=400)
     ap.add_argument('--child', default=None)
     ap.add_argument('--sweeps', action='store_true')
     ap.add_argument('--sweeps-child', action='store_true')
     a = ap.parse_args()
+    longs = None if a.long is None else [int(x) for x in a.long.split(',')]
+    if longs is not None and (not longs or min(longs) < 1):
+        raise SystemExit('--long takes counts of at least 1')
     if a.child:
-        print(json.dumps(child(a.child, a.steps, a.steps_exact, a.warmup, a.scale, a.max_degree)), flush=True)
+        print(json.dumps(child(a.child, a.steps, a.steps_exact, a.warmup, a.scale, a.max_degree, longs=longs)), flush=True)
         return
     if a.sweeps_child:
         print(json.dumps(sweeps()), flush=True)
@@ -208,23 +244,35 @@ def main():
         print(lines[-1], flush=True)
         return
     results, failed = [], None
-    for case in a.cases.split(','):
-        if case not in ALL_CASES:
-            raise SystemExit(f'unknown case {case}')
-        cmd = ['timeout', '-k', '10', str(a.child_timeout), sys.executable, os.path.abspath(__file__), '--child', case,
-               '--steps', str(a.steps), '--steps-exact', str(a.steps_exact), '--warmup', str(a.warmup), '--scale', str(a.scale), '--max-degree', str(a.max_degree)]
-        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
-        lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
-        if p.returncode != 0 or not lines:
-            failed = {'case': case, 'returncode': p.returncode, 'stderr': p.stderr[-2000:]}
-            break                      # a child that failed ends the run: nothing more is started on the GPU
-        results.append(json.loads(lines[-1]))
-        r = results[-1]['requests']
-        print(f'[bench_als_cg] {case}: ' + ', '.join(f'{nm} cg {r[nm]["cg_steps3"]["median_ms"]} ms / exact '
-                                                     f'{r[nm]["exact_als_rows"]["median_ms"]} ms' for nm in r), file=sys.stderr, flush=True)
-    print(json.dumps({'bench': 'als_rows_cg', 'workload': f'configs[2] pattern (2M x 2M, nnz 5e7 power-law, longest row capped at {a.max_degree}), CG steps = 3 beside the exact route',
-                      'results': results, 'failed': failed,
-                      'parity_ok': failed is None and all(r['parity']['ok'] for r in results)}), flush=True)
+    # --long without --max-degree: both patterns, configs[2] and the one whose longest row is capped at 2 000
+    degrees = [a.max_degree] if a.max_degree is not None else ([250_000, 2000] if longs is not None else [250_000])
+    for degree in degrees:
+        for case in a.cases.split(','):
+            if case not in ALL_CASES:
+                raise SystemExit(f'unknown case {case}')
+            cmd = ['timeout', '-k', '10', str(a.child_timeout), sys.executable, os.path.abspath(__file__), '--child', case,
+                   '--steps', str(a.steps), '--steps-exact', str(a.steps_exact), '--warmup', str(a.warmup), '--scale', str(a.scale),
+                   '--max-degree', str(degree)] + ([] if longs is None else ['--long', a.long])
+            p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+            lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+            if p.returncode != 0 or not lines:
+                failed = {'case': case, 'max_degree': degree, 'returncode': p.returncode, 'stderr': p.stderr[-2000:]}
+                break                  # a child that failed ends the run: nothing more is started on the GPU
+            results.append(json.loads(lines[-1]))
+            r = results[-1]['requests']
+            print(f'[bench_als_cg] {case} (longest row {degree}): ' + ', '.join(
+                f'{nm} cg {r[nm]["cg_steps3"]["median_ms"]} ms' + ''.join(f' | L={L} {v["cg_steps3"]["median_ms"]}' for L, v in r[nm].get('long', {}).items())
+                + f' / exact {r[nm]["exact_als_rows"]["median_ms"]} ms' for nm in r), file=sys.stderr, flush=True)
+        if failed is not None:
+            break
+    doc = {'bench': 'als_rows_cg', 'workload': 'configs[2] pattern (2M x 2M, nnz 5e7 power-law, longest row capped at '
+                                               + ' and '.join(str(d) for d in degrees) + '), CG steps = 3 beside the exact route',
+           'long': longs, 'results': results, 'failed': failed,
+           'parity_ok': failed is None and all(r['parity']['ok'] for r in results)}
+    if longs is not None:
+        with open(a.out, 'w') as f:
+            json.dump(doc, f, indent=1)
+    print(json.dumps(doc), flush=True)
     sys.exit(0 if failed is None else 1)
 
 

@@ -93,6 +93,7 @@ SIGNATURES = {
     'csrk_spmm_dense': (_int, [handle_t, _vp, _i32, _i64, _vp, _i64]),
     'csrk_spmm_dense_device': (_int, [handle_t, _vp, _i32, _i64, _vp, _i64, _vp]),
     'csrk_spmm_plan_stats': (_int, [handle_t, _vp, _int]),
+    'csrk_spmm_plan_ranges': (_int, [handle_t, _vp, _int]),
     'csrk_sddmm': (_int, [handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _vp]),
     'csrk_sddmm_device': (_int, [handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _vp, _vp]),
     'csrk_gram_rows': (_int, [handle_t, _i32, _i32, _vp, _i64, _i32, _int, _int, _vp, _vp]),

@@ -1022,6 +1022,20 @@ int csrk_spmm_plan_stats(csrk_handle_t h, int64_t *out, int n)
     return CSRK_OK;
 }
 
+int csrk_spmm_plan_ranges(csrk_handle_t h, int32_t *out, int n)
+{
+    Matrix *m = from_handle(h);
+    if (!m) return CSRK_ERR_INVALID;
+    CSRK_REQUIRE(out && n >= 0, "out is NULL");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const SpmmPlan *p = m->spmm_plan;
+    if (!p || !p->hr_on) return CSRK_OK;                     // no heavy rows: no table, nothing written
+    CSRK_REQUIRE(n >= p->hr_R + 1, "the range table has %d entries, out holds %d", p->hr_R + 1, n);
+    CSRK_HIP(hipDeviceSynchronize());                        // (the table was written at plan time, on the default stream)
+    CSRK_HIP(hipMemcpy(out, p->hr_range.p, ((size_t)p->hr_R + 1) * 4, hipMemcpyDeviceToHost));
+    return CSRK_OK;
+}
+
 int csrk_spmm_dense(csrk_handle_t h, const double *B, int32_t k, int64_t ldb, double *C, int64_t ldc)
 {
     Matrix *m = from_handle(h);

@@ -284,6 +284,10 @@ CSRK_API int csrk_spmm_dense_device(csrk_handle_t a, const double *d_B, int32_t 
  * the register-accumulator form (csrc/spmm_dense.hip), [1] their row-length threshold, [2] their number, [3] row groups,
  * [4] column ranges, [5] their entries, [6] column tiles, [7] segments of the other rows, [8] of which partial (split rows). */
 CSRK_API int csrk_spmm_plan_stats(csrk_handle_t a, int64_t *out, int n);
+/* Diagnostics, read-only: the plan's column ranges, out[q] = first column tile (128 rows of B) of range q, q = 0 .. R, with
+ * out[R] = the number of tiles (R = csrk_spmm_plan_stats' [4]); n, the room in out, must be at least R + 1.  Without the
+ * register-accumulator form (stats' [0] = 0) nothing is written. */
+CSRK_API int csrk_spmm_plan_ranges(csrk_handle_t a, int32_t *out, int n);
 
 /* ---- sampled dense-dense product (SDDMM): one value per stored entry ---------------------
  * Not a reference entry point (the reference's mult_ab is sparse x sparse only); the transpose-dual of

@@ -39,6 +39,13 @@ int main(void)
     CHECK(csrk_row_extent(h, 3, &s, &e));
     if (nnzs[0] != 2 || nnzs[1] != 1 || nnzs[2] != 0 || nnzs[3] != 1 || s != 3 || e != 4) return 1;
 
+    /* the dense-panel plan's diagnostics on a handle that has no such plan: all zero, and no range table is written */
+    int64_t st[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+    int32_t ranges[2] = {-7, -7};
+    CHECK(csrk_spmm_plan_stats(h, st, 9));
+    CHECK(csrk_spmm_plan_ranges(h, ranges, 2));
+    if (st[0] != 0 || st[4] != 0 || ranges[0] != -7 || ranges[1] != -7) return 1;
+
     CHECK(csrk_transpose(h, 1, &t));
     int32_t nr = 0, nc = 0, p64 = -1, vt = -1;
     int64_t nnz = 0;

@@ -128,6 +128,11 @@ SIGNATURES = {
     'csrk_rank_entries': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp]),
     'csrk_rank_entries_device': (_int, [handle_t, handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp, _vp]),
     'csrk_rank_entries_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_rank_entries_for': (_int, [handle_t, handle_t, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _vp, _i64, _i32]),
+    'csrk_rank_entries_for_device': (_int, [handle_t, handle_t, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _int, _vp, _i64, _vp, _vp,
+                                            _i32, _vp]),
+    'csrk_rank_entries_for_splits': (_int, [_i64, _i32, _i32, C.POINTER(_i32)]),
+    'csrk_rank_entries_for_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_knn_scores': (_int, [handle_t, handle_t, _vp, _i64, _i32, _i32, _int, _vp, C.POINTER(handle_t)]),
     'csrk_knn_scores_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_knn_scores_reach': (_int, [handle_t, handle_t, _vp, _i64, _i32, _i32, _int, _vp, C.POINTER(handle_t)]),

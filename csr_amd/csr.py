@@ -540,6 +540,42 @@ class CSR:
                     ranks, scores = fn(s_h, t_h, U, V, rows)
         return (ranks, scores) if return_scores else ranks
 
+    def rank_entries_for(self, users, U, V, test, *, exclude=True, return_scores=False, return_offsets=False, splits=None):
+        """
+        rank_entries for a list of rows -- evaluating a sample of users: ranks (int32) of the entries `test` stores in rows
+        users[0], users[1], ..., row by row in list order and each row's entries in storage order.  users is a 1-D array of
+        integer row indices in any order, repeats allowed (each occurrence gets its own outputs); an index outside
+        [0, nrows) is a ValueError naming its position.  The entries of users[r] start at offsets[r], the int64 prefix sum of
+        test.row_nnzs()[users] (len(users) + 1 of them).  Returns ranks, followed by scores (float64) with
+        return_scores=True and by offsets with return_offsets=True.  Scores, candidates and order are rank_entries', bit for
+        bit: for users = arange(b, e) the result equals rank_entries(rows=(b, e)).  The items are cut into `splits` ranges
+        that run side by side so that a sample still fills the card (None: chosen from the number of rows;
+        K.rank_entries_for_splits tells) and the partial ranks, integers, add: no bit depends on it (include/csrk.h,
+        csrk_rank_entries_for).  Only the listed rows of U are sent.  This matrix must be canonical (exclude=False: it is not
+        looked at); the values of neither are read.  Runs on the device only.  Not a reference entry point.
+        """
+        K, fn = self._ext('rank_entries_for')
+        if not isinstance(test, CSR):
+            raise ValueError(f'test must be a CSR, not {type(test).__name__}')
+        users = K.rank_entries_for_args(self, test, users, U, V, splits)[0]
+        for m in ((self, test) if exclude else (test,)):
+            if m.nnz > K.max_nnz:
+                raise ValueError('CSR size {} exceeds max nnz {}'.format(m.nnz, K.max_nnz))
+        with releasing(K.to_handle(test), K) as t_h:
+            if not exclude:
+                ranks, scores = fn(None, t_h, users, U, V, splits)
+            elif test is self:                   # one device copy serves both sides
+                ranks, scores = fn(t_h, t_h, users, U, V, splits)
+            else:
+                with releasing(K.to_handle(self), K) as s_h:
+                    ranks, scores = fn(s_h, t_h, users, U, V, splits)
+        out = (ranks,) + ((scores,) if return_scores else ())
+        if return_offsets:
+            offsets = np.zeros(len(users) + 1, np.int64)
+            np.cumsum(test.row_nnzs()[users], out=offsets[1:])
+            out += (offsets,)
+        return out[0] if len(out) == 1 else out
+
     # ---- two matrices entry by entry -----------------------------------------------------------
     def _knn_check(self, K, model, users, max_nbrs, min_nbrs, aggregate, offsets, route='walk'):
         "knn_scores' arguments as the kernel takes them, checked before any device work; users=None: all rows"

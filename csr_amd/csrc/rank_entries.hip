@@ -26,38 +26,12 @@
 
 #include "common.h"
 #include "panel.h"
+#include "rank_list.h"
 #include "score_tile.h"
 
 namespace csrk {
 
-constexpr int RE_T = 32;                        // test entries of a row per sweep
-constexpr int RE_LDT = RE_T + 1;                // list line (rows fall into different banks)
-constexpr int RE_K_MAX = 1024;
-constexpr int32_t RE_BAD_ITEM = 0x7fffffff;     // listed for a test column outside [0, n_items): never dereferenced
-static_assert(RE_T <= WAVE, "one lane per listed entry");
-
-// csrk_topk_scores' rule 2 for one pair, straight from the panels
-template <class T> __device__ __forceinline__ double re_chain(const T *__restrict__ u, const T *__restrict__ v, int k)
-{
-    double s = 0.0;
-    for (int t = 0; t < k; t++) s = __builtin_fma((double)u[t], (double)v[t], s);
-    return s;
-}
-
-// the first of the n listed entries (best first) that (ks, j) comes before; n when there is none
-__device__ __forceinline__ int re_slot(const uint64_t *__restrict__ sk, const int32_t *__restrict__ si, int n, uint64_t ks, int32_t j)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key_before(ks, j, sk[mid], si[mid]))
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
-
+// (the list constants RE_*, re_chain and re_slot: rank_list.h, shared with rank_entries_for.hip)
 template <class T, bool WIDE>
 __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__restrict__ seen_rp, int seen_ptr64,
                                                                  const int32_t *__restrict__ seen_ci, const void *__restrict__ test_rp,

@@ -8,7 +8,7 @@ csr/kernels/mkl/*): max_nnz, to_handle, from_handle, release_handle, order_colum
 mult_ab, mult_abt, mult_vec.  Extra members for the operations the reference runs
 outside its kernel protocol but on the same hot path: transpose, row_nnzs, unit_rows,
 center_rows, filter_zeros, pick_rows, mult_dense, sddmm, gram_rows, als_rows, als_rows_cg, solve_blocks, topk_rows, combine, coalesce,
-is_canonical, topk_scores, topk_scores_for, rank_entries, knn_scores, knn_reach_index.
+is_canonical, topk_scores, topk_scores_for, rank_entries, rank_entries_for, knn_scores, knn_reach_index.
 
 A handle owns a copy of the matrix in HBM, like the MKL kernel's handle
 (csr/kernels/mkl/handle.py:47-70).  There is no CPU fallback: without a GPU every call
@@ -1185,6 +1185,71 @@ def rank_entries(seen_h, test_h, U, V, rows=None):
         m = row_extent(test_h, re_ - 1)[1] - row_extent(test_h, rb)[0]
     ranks, scores = _out(m, np.int32), _out(m, np.float64)
     _call(lib.csrk_rank_entries, sh, _live(test_h), rb, re_, ptr(U), ldu, ptr(V), ldv, k, code, ptr(ranks), ptr(scores))
+    return ranks, scores
+
+
+def rank_entries_for_limits():
+    "(most splits, workgroups that fill the card)"
+    return _limits(lib.csrk_rank_entries_for_limits, 2)
+
+
+def rank_entries_for_splits(n_rows, n_items, splits=None):
+    """
+    Into how many ranges rank_entries_for cuts the items for n_rows listed rows and n_items items (splits=None: as many as
+    fill the card).  From the library's constants alone: no device is touched.
+    """
+    for name, v in (('n_rows', n_rows), ('n_items', n_items)):
+        if not _is_int(v):
+            raise ValueError(f'{name} must be an integer, not {v!r}')
+    if n_items > np.iinfo('i4').max:
+        raise ValueError(f'{n_items} items are more than 32-bit indices hold')
+    used = C.c_int32(0)
+    check(lib.csrk_rank_entries_for_splits(int(n_rows), int(n_items), _splits(splits), C.byref(used)))
+    return used.value
+
+
+def rank_entries_for_args(seen_h, test_h, users, U, V, splits=None):
+    """
+    (users int32, U, ldu, V, ldv, k, panel code, splits, u_rows) as the library takes them; ValueError for anything it would
+    refuse as invalid.  seen_h and test_h are as in rank_entries_args; users is a 1-D array of integer row indices in any
+    order, repeats allowed; no library call is made.
+    """
+    U, ldu, V, ldv, k, code, _, nrows = rank_entries_args(seen_h, test_h, U, V, None)
+    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
+    if users.ndim != 1:
+        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
+    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
+        raise ValueError(f'users must hold integers, not {users.dtype}')
+    bad = np.flatnonzero((users < 0) | (users >= nrows))
+    if len(bad):
+        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
+    return np.ascontiguousarray(users, dtype=np.int32), U, ldu, V, ldv, k, code, _splits(splits), nrows
+
+
+def rank_entries_for(seen_h, test_h, users, U, V, splits=None):
+    """
+    rank_entries for a list of rows: (ranks int32 [m], scores float64 [m]) with m the entries test_h stores in the rows
+    users[0], users[1], ... -- row by row in list order, each row's entries in storage order.  users may be in any order and
+    repeat a row; every occurrence gets its own outputs.  The items are cut into `splits` ranges that run side by side (None:
+    as many as fill the card) and the partial ranks add, which changes no bit: for users = arange(b, e) the result is
+    rank_entries' for rows = (b, e) (include/csrk.h, csrk_rank_entries_for).  Only the listed rows of U are sent.  Not a
+    reference entry point.
+    """
+    users, U, ldu, V, ldv, k, code, sp, nrows = rank_entries_for_args(seen_h, test_h, users, U, V, splits)
+    sh = 0 if seen_h is None else _live(seen_h)
+    lim = rank_entries_limits()
+    if k > lim[0]:      # the library's refusal, before any result array is made
+        one = np.zeros(1, np.int32)
+        check(lib.csrk_rank_entries_for(sh, _live(test_h), ptr(one), 1, nrows, ptr(U), ldu, ptr(V), ldv, k, code, None, None, 0, sp))
+        raise ValueError(f'k = {k} is above the limit {lim[0]}')
+    m = 0
+    if len(users) and test_h.nnz:
+        m = int(row_nnzs(test_h)[users].sum(dtype=np.int64))
+    ranks, scores = _out(m, np.int32), _out(m, np.float64)
+    if m == 0:
+        return ranks, scores
+    _call(lib.csrk_rank_entries_for, sh, _live(test_h), ptr(users), len(users), nrows, ptr(U), ldu, ptr(V), ldv, k, code, ptr(ranks),
+          ptr(scores), m, sp)
     return ranks, scores
 
 

@@ -836,7 +836,8 @@ CSRK_API int csrk_topk_scores_for_limits(int64_t *out, int n);
  *   8. Device form.  Allocates nothing and does not synchronise the host, with one exception: the first call that asks
  *      `seen` whether it is canonical looks at its rows (csrk_is_canonical beforehand takes that look).  A workgroup takes a
  *      block of rows across all items and holds up to out[4] test entries per row on the chip; rows with more are swept
- *      again, decided on the device: no scratch memory.  The items of a small row range are not split across workgroups.
+ *      again, decided on the device: no scratch memory.  The items of a small row range are not split across workgroups
+ *      (csrk_rank_entries_for splits them).
  *      The host form sends the panels packed (the rows of the range only) and is synchronous.
  *   9. Refusals; a refused call writes nothing.  The scalar arguments are looked at first and answered whatever the handles
  *      are: CSRK_ERR_INVALID for k < 1, ldu < k, ldv < k, an unknown panel_type, row_begin < 0 or row_begin > row_end;
@@ -857,6 +858,70 @@ CSRK_API int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, in
                                       int32_t *d_ranks, double *d_scores, void *stream);
 /* Diagnostics: the five limits of rule 10, in its order;  n <= 5.  No device is touched. */
 CSRK_API int csrk_rank_entries_limits(int64_t *out, int n);
+
+/* ---- rank_entries_for: csrk_rank_entries for a list of rows, the items split across workgroups ------
+ * Not a reference entry point: offline evaluation of a SAMPLE of users.  The rows with held-out entries are scattered over
+ * the matrix, and a thousand of them do not fill the card when one workgroup takes 64 rows across all items: here the rows
+ * are named one by one and the items are cut into S ranges that run side by side; the partial ranks are integers and add.
+ * Everything not said here is csrk_rank_entries' rule of the same number; rules 11 and 12 are this entry's own.
+ *   1. Rows.  rows[r] (int32, n_rows of them) is an ABSOLUTE row index: U[rows[r]] is the factor row, row rows[r] of `test`
+ *      holds the entries ranked and row rows[r] of `seen` the exclusion list.  The list may be in any order and may repeat
+ *      a row; each occurrence is computed on its own and gets its own output positions (rule 4).  u_rows is the number of
+ *      rows U holds and must equal test's nrows.  In the device form an index outside [0, u_rows) is not dereferenced: that
+ *      list position reads and writes nothing, and no neighbour is affected.  The host form looks at the list first and
+ *      refuses with CSRK_ERR_INVALID, naming the first bad position and its value (as csrk_topk_scores_for does); it sends
+ *      only the listed rows of U, packed in list order.  The bad-column part of csrk_rank_entries' rule 1 holds: a test
+ *      column outside [0, n_items) gets rank -1 and a NaN score -- exactly -1, for any number of splits.
+ *   2. Score, 3. Rank and 7. Special values are rules 2, 3 and 7 of csrk_rank_entries, word for word (i = rows[r]).  For
+ *      rows = b, b + 1, ..., e - 1 every output bit equals that of csrk_rank_entries(row_begin = b, row_end = e).
+ *   4. Output.  With len(r) = the entries `test` stores in row rows[r] and offsets[r] = len(0) + ... + len(r - 1): the x-th
+ *      entry of that row, in test's storage order, goes to ranks[offsets[r] + x], and its score to scores[offsets[r] + x]
+ *      when scores is not NULL.  n_out = offsets[n_rows].  The device form takes d_offsets (int64, n_rows + 1 of them, 8-B
+ *      aligned) from the caller, since it allocates nothing; it cannot verify them, so a position outside [0, n_out) is
+ *      never written: offsets that are not this prefix sum give unspecified ranks, but no write outside [0, n_out).  The
+ *      host form computes the offsets itself and refuses with CSRK_ERR_INVALID, naming the total, when n_out is not it.
+ *   5. Agreement.  csrk_rank_entries' rule 5 holds with csrk_topk_scores_for on the same list: a test entry that `seen`
+ *      does not store and whose rank < n_top is items[r][rank] there, with the same score bits.
+ *   6. Invariance.  No output bit depends on splits, the order or repetition of rows, the previous contents of `ranks`,
+ *      repeated calls into the same buffers, or anything in csrk_rank_entries' rule 6.
+ *   8. Device form.  Allocates nothing and does not synchronise the host, apart from the remembered canonical look at
+ *      `seen` of csrk_rank_entries' rule 8; the clear and the launch go to `stream`.  The host form is synchronous.
+ *   9. Refusals; a refused call writes nothing.  Every refusal of csrk_rank_entries that applies, the scalars first, in the
+ *      same order, with texts that begin "rank_entries_for: ".  CSRK_ERR_INVALID further: n_rows < 0, u_rows < 0,
+ *      splits < 0, n_out < 0 (after the panel type, in this order); u_rows != test's nrows; when there is work, NULL rows
+ *      or offsets, and rows or offsets not aligned to their element.  CSRK_ERR_UNSUPPORTED: k above out[0] of
+ *      csrk_rank_entries_limits, and more row blocks x splits than a grid holds (2^31 - 1).  n_rows == 0 or n_out == 0:
+ *      CSRK_OK, nothing launched and nothing cleared.
+ *  10. Limits (csrk_rank_entries_for_limits): out[0] = S_max; [1] = W;  n <= 2.
+ *  11. Splits.  With tile = out[2] of csrk_rank_entries_limits and T = ceil(n_items / tile), the items are cut at tile
+ *      boundaries into S contiguous ranges: range s holds the tiles [s T / S, (s + 1) T / S) (integer division;
+ *      csrk_topk_scores_for's rule 3).  One workgroup takes one (block of 64 list rows, range s) pair.  It scores and orders
+ *      its rows' test entries exactly as csrk_rank_entries does -- every split of a block lists the same entries in the
+ *      same order --, sweeps only its item interval, takes out again only the `seen` entries whose column lies in that
+ *      interval (`seen` is canonical: a lower bound in the row finds where they start) and forms the prefix sums as
+ *      csrk_rank_entries does: partial ranks.  splits >= 1 forces S = min(splits, T, S_max), and S = 1 when T = 0 or
+ *      n_rows = 0.  splits = 0 is automatic: S = clamp(ceil(W / ceil(n_rows / 64)), 1, min(T, S_max)), with S_max = 64 and
+ *      W = 512 the workgroups that fill the card (two per CU, 256 CUs).  csrk_rank_entries_for_splits returns S from these
+ *      constants alone.
+ *  12. Combining.  S = 1 stores the ranks directly in one launch and touches nothing else of `ranks`.  S > 1 clears
+ *      ranks[0 .. n_out) on the stream first; every workgroup then adds its partial rank with one integer atomic add per
+ *      listed entry (none where the partial rank is 0).  Only split 0 writes `scores`, and only split 0 contributes the -1
+ *      of a bad column.  Integer addition commutes, so no bit depends on S, on the order in which workgroups arrive or on
+ *      what `ranks` held before the call.  No float atomics, no workspace, and no workgroup waits for another.  A row with
+ *      more than out[4] of csrk_rank_entries_limits test entries is swept again per out[4] of them inside its workgroup. */
+CSRK_API int csrk_rank_entries_for(csrk_handle_t seen, csrk_handle_t test, const int32_t *rows, int64_t n_rows, int32_t u_rows,
+                                   const void *U, int64_t ldu, const void *V, int64_t ldv, int32_t k, int panel_type,
+                                   int32_t *ranks, double *scores, int64_t n_out, int32_t splits);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream). */
+CSRK_API int csrk_rank_entries_for_device(csrk_handle_t seen, csrk_handle_t test, const int32_t *d_rows, int64_t n_rows,
+                                          int32_t u_rows, const void *d_U, int64_t ldu, const void *d_V, int64_t ldv, int32_t k,
+                                          int panel_type, const int64_t *d_offsets, int64_t n_out, int32_t *d_ranks,
+                                          double *d_scores, int32_t splits, void *stream);
+/* Rule 11: *splits_used = S.  CSRK_ERR_INVALID: n_rows < 0, n_items < 0, splits < 0, a NULL result pointer.  No device is
+ * touched. */
+CSRK_API int csrk_rank_entries_for_splits(int64_t n_rows, int32_t n_items, int32_t splits, int32_t *splits_used);
+/* Diagnostics: the two limits of rule 10, in its order;  n <= 2.  No device is touched. */
+CSRK_API int csrk_rank_entries_for_limits(int64_t *out, int n);
 
 /* ---- knn_scores: score items from an item-kNN model's nearest rated neighbours -------------------------
  * Not a reference entry point: the scoring side of the neighbourhood model that csrk_spgemm_abt + csrk_topk_rows build (each

@@ -33,7 +33,11 @@
 // jj at a time (sg_walk_products: inside one B_j the columns are distinct, a barrier separates the steps); the strips by
 // giving every column to one wavefront, whose LDS operations complete in program order; expand-sort-compress by a stable
 // sort.  (Round 1 let the wavefronts of a workgroup take different jj and race on the accumulators: last bits varied.)
+#include <cstdlib>
+#include <memory>
+
 #include "common.h"
+#include "spgemm_plan.h"
 #include "wave.h"
 
 namespace csrk {
@@ -45,7 +49,12 @@ void spgemm_order_limits(int64_t out[5]);
 
 // csrk_spgemm_last_stats: what the calling thread's last general product did with its rows (include/csrk.h has the layout);
 // zeroed by every csrk_spgemm_ab / _abt, filled at the end of spgemm_run from what the driver holds on the host anyway
-constexpr int SG_N_STATS = 16;
+enum SgStat {      // (the order of include/csrk.h and of tests/spgemm_cases.py: STATS)
+    SG_STAT_GENERAL, SG_STAT_FAST, SG_STAT_STRIPS, SG_STAT_STRIP_ROWS, SG_STAT_STRIP_ENTRIES, SG_STAT_STRIP_FUSED, SG_STAT_ESC_ROWS,
+    SG_STAT_ESC_PRODUCTS, SG_STAT_LARGE_ROWS, SG_STAT_LDS_SYMBOLIC, SG_STAT_LDS_ROWS, SG_STAT_HASH_BIG_ROWS, SG_STAT_HBM_ROWS,
+    SG_STAT_SMALL_FUSED, SG_STAT_MID_ROWS, SG_STAT_HASH_ROWS, SG_N_STATS
+};
+static_assert(SG_N_STATS == 16, "csrk_spgemm_last_stats has 16 fields (include/csrk.h)");
 static thread_local int64_t t_last_stats[SG_N_STATS];
 
 struct MatView {
@@ -157,7 +166,7 @@ __device__ __forceinline__ void sg_walk_products(const MatView &a, const MatView
 constexpr int SG_THREADS = 256;
 constexpr int SG_SLOTS = 2048;
 constexpr int SG_CAP = 1024;      // max products for the LDS hash path (load factor <= 0.5)
-constexpr int SG_WAVE_CAP = 128;  // rows with at most this many products take the sub-wavefront kernels (sg_quad_kernel)
+// (SG_WAVE_CAP, at most this many products for the sub-wavefront kernels (sg_quad_kernel): spgemm_plan.h)
 
 // products per output row: ub[i] = sum_{j in A_i} |B_j|.  (A thread per row spent 1.9 ms on 2000 rows of a MovieLens-shaped A,
 // whose rows have up to 7000 entries.)  Eight lanes per row (most rows of a sparse product have a handful of entries: a wavefront per row took 159 us for 10^6
@@ -166,11 +175,11 @@ constexpr int SG_COUNT_LONG = 64;
 // The long rows are appended to SG_LONG_LISTS lists, workgroup b to list b % SG_LONG_LISTS (a counter per list, a cache line
 // apart): appends to ONE counter are served one after the other, ~10 ns each -- 10^4 long rows of a 10^6-row power-law matrix
 // cost 100 us of a 2.9-ms product.  List k holds at most long_cap rows (the rows of the workgroups that append to it).
-constexpr int SG_LONG_LISTS = 64, SG_LONG_STRIDE = 32;      // (counters SG_LONG_STRIDE int32 apart)
+// (SG_LONG_LISTS, and SG_LONG_STRIDE, the int32 between two counters: spgemm_plan.h)
 // Rows of more than SG_COUNT_VLONG entries go to one more list (number SG_LONG_LISTS, at long_list + SG_LONG_LISTS * long_cap) and
 // are counted by ALL wavefronts together, 256 entries at a time (a wavefront per row: the longest row of a power-law matrix
 // alone was 0.10 ms).
-constexpr int SG_COUNT_VLONG = 4096;
+// (SG_COUNT_VLONG: spgemm_plan.h)
 template <bool FAST>
 __global__ __launch_bounds__(256) void sg_count_products(MatView a, MatView b, int64_t *__restrict__ ub,
                                                          int32_t *__restrict__ long_list, int32_t long_cap, int32_t *__restrict__ n_long)
@@ -843,17 +852,13 @@ __global__ __launch_bounds__(SGL_THREADS) void sg_hash_big_kernel(MatView a, Mat
 // way), so these are a sub-range of B_j, and the sub-range bounds of every (A entry, strip boundary) are found once by
 // binary search (sg_strip_table) -- the table is 4 (S+1) bytes per A entry, which is why only rows with at least
 // SGS_MIN_PER_CELL products per (A entry, strip) on average take this path.
-#ifndef CSRK_SGS_W
-#define CSRK_SGS_W 832
-#endif
 // columns per strip (13 x 64): 6.5 KiB of sums + a tag byte per column, 20 wavefronts per CU.  Measured on the ratings
 // blocks (2000 x 20000^T / 500 x 5000^T): 544 -> 1.85 / 1.08 ms, 704 -> 1.68 / 1.17, 832 -> 1.58 / 1.13, 960 -> 1.70 / 1.27,
 // 1088 -> 1.65 / 1.23: narrower strips split the hot columns' ordered adds over more units, wider ones need fewer
 // sub-ranges per product.
-constexpr int SGS_W = CSRK_SGS_W;
+// (SGS_W itself, SGS_MAX_S and the strips' two budgets: spgemm_plan.h)
 constexpr int SGS_WAVES_PER_CU = 16 * 1088 / SGS_W;
 constexpr int SGS_CHUNKS = SGS_W / WAVE;
-constexpr int SGS_MAX_S = 256;              // strips per row (wider products fall back to the workgroup paths)
 #ifndef CSRK_SGS_G
 #define CSRK_SGS_G 8
 #endif
@@ -864,8 +869,6 @@ constexpr int SGS_MIN_PER_CELL = 4;
 #endif
 constexpr int SGS_MIN_PER_UNIT = CSRK_SGS_MIN_PER_UNIT;     // products per (row, strip) on average
 constexpr int SGS_HEAVY_J = 1024;           // rows with this many A entries are scheduled first (longest chains)
-constexpr int64_t SGS_TABLE_BUDGET = 2ll << 30;
-constexpr int64_t SGS_TEMP_BUDGET = 24ll << 30;      // bytes of compacted strips held between the one pass and the copy
 
 // bad[0] = 1 unless every row of the matrix is strictly ascending in its columns
 __global__ void sg_sorted_check(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci, int32_t nrows, int64_t nnz,
@@ -1335,11 +1338,7 @@ __global__ __launch_bounds__(256) void sg_strip_copy(const int32_t *__restrict__
 // into ascending column order with the products of one column still in their original order, and one thread per run of
 // equal columns adds the run front to back: the reference's sums, bit for bit, without atomics.  (Before: a dense float64
 // work row in HBM per workgroup, a barrier per A entry: 7.5 ms of a 200k x 200k product's 13.8.)
-constexpr int64_t SGE_BUDGET_PRODUCTS = 200ll << 20;     // above this the round-1 heavy-row paths are used instead
-#ifndef CSRK_SGE_MIN
-#define CSRK_SGE_MIN 32
-#endif
-constexpr int64_t SGE_MIN = CSRK_SGE_MIN;                // rows with more products than this (and not dense enough for strips)
+// (SGE_MIN, the products above which a row comes here, and SGE_BUDGET_PRODUCTS, the sort's budget: spgemm_plan.h)
 
 __global__ void sg_esc_gather(const int32_t *__restrict__ list, int32_t n, const int64_t *__restrict__ ub, int64_t *__restrict__ pu)
 {
@@ -1580,6 +1579,544 @@ __global__ void sg_split_large(const int32_t *__restrict__ list, int32_t n_large
         list_b[atomicAdd(&n_ahb[2], 1)] = i;
 }
 
+// ---- the driver ------------------------------------------------------------------------------------------------------
+// spgemm_run (at the end) reads as the algorithm: count the products, plan the routes (sg_plan), the symbolic step of each
+// route, scan and allocate C, the numeric step of each route, drain.  Each route is a struct that owns its buffers and
+// both of its halves; what every route reads (SgShared) stays with the driver and is passed in; the budget arithmetic is
+// spgemm_plan.h's.  Everything runs on the default stream.  The ORDER in which the steps ask the pool for memory and launch
+// is part of the behaviour (the pool serves best-fit, so the order decides which block a request reuses), which is why the
+// large rows have a step before the others' symbolic steps and two numeric ones: spgemm_run calls the steps in that order.
+
+// CSRK_SPGEMM_STRIPS / _ESC / _FUSED, read once per call (the tests set them between calls): on unless set to 0.
+// STRIPS=0: workgroup paths only; ESC=0: the fallback paths instead of expand-sort-compress; FUSED=0: two passes
+struct SgKnobs {
+    bool strips, esc, fused;
+};
+
+static SgKnobs sg_read_knobs()
+{
+    auto on = [](const char *name) {
+        const char *e = getenv(name);
+        return !(e && atoi(e) == 0);
+    };
+    return {on("CSRK_SPGEMM_STRIPS"), on("CSRK_SPGEMM_ESC"), on("CSRK_SPGEMM_FUSED")};
+}
+
+// what every route reads: the operands, the knobs, the rows' product counts (ub), routes and output counts (cnt), the
+// persistent kernels' row counters (next) and the compute units
+struct SgShared {
+    Matrix *a, *b;
+    MatView av, bv;
+    int32_t nr;
+    SgKnobs knobs;
+    DevBuf ub, cnt, route, next;
+    int grid_lds = 256;
+};
+
+// what the listing decided (sg_plan); the routes read it
+struct SgPlan {
+    int32_t strips = 0;                   // column strips per row in force (0: off)
+    int32_t s_dense = 0;                  // the strips' density test, in force or not
+    int64_t esc_min = -1;                 // rows above this many products go to expand-sort-compress (-1: none)
+    int32_t n_large = 0, n_strip = 0, n_strip_e = 0, n_esc = 0;      // rows of the fallback paths, of the strips, their entries of A, rows of ESC
+    int64_t esc_products = 0;             // (the last count, also when a budget then sent those rows elsewhere)
+    bool hash_rows = true, mid_rows = true;
+};
+
+// the plan's own temporaries: long_cnt goes back to the pool after the symbolic steps, the others with the call
+struct SgPlanScratch {
+    DevBuf long_cnt, counters, sorted_bad;
+};
+
+// C's arrays as the numeric kernels take them
+struct SgOut {
+    const int32_t *rp;
+    int32_t *ci;
+    double *vs;
+};
+
+static int sg_new_matrix(int32_t nrows, int32_t ncols, int64_t nnz, std::unique_ptr<Matrix> *out)
+{
+    Matrix *m = nullptr;
+    CSRK_TRY(new_matrix(nrows, ncols, nnz, 0, CSRK_VAL_F64, &m));
+    out->reset(m);
+    return CSRK_OK;
+}
+
+static int sg_transpose(Matrix *m, std::unique_ptr<Matrix> *out)
+{
+    Matrix *t = nullptr;
+    CSRK_TRY(transpose_matrix(m, 1, &t, nullptr));
+    out->reset(t);
+    return CSRK_OK;
+}
+
+// ---- small rows: at most SG_WAVE_CAP products on the 16- and 32-lane sg_quad_kernels, up to SG_CAP on sg_hash_kernel --
+struct SgSmallRows {
+    DevBuf room, off, tci, tvs;           // the one-pass form: each row's room in the temporary, where it starts, the temporary
+    bool fused = false, any = true;       // one pass; there are rows for the sub-wavefront kernels at all
+
+    template <bool NUMERIC, bool FAST>
+    void quads(const SgShared &sh, const SgPlan &p, int32_t *cnt, const int32_t *c_rp, int32_t *c_ci, double *c_vs, const int64_t *t_off)
+    {
+        sg_quad_kernel<16, 32, NUMERIC, FAST><<<(unsigned)ceil_div(sh.nr, 16), 256>>>(
+            sh.av, sh.bv, sh.ub.as<int64_t>(), 0, sh.route.as<unsigned char>(), cnt, c_rp, c_ci, c_vs, t_off);
+        if (p.mid_rows)
+            sg_quad_kernel<32, SG_WAVE_CAP, NUMERIC, FAST><<<(unsigned)ceil_div(sh.nr, 8), 256>>>(
+                sh.av, sh.bv, sh.ub.as<int64_t>(), 32, sh.route.as<unsigned char>(), cnt, c_rp, c_ci, c_vs, t_off);
+    }
+
+    // (rows with no products keep the zero count of the driver's memset)
+    template <bool FAST>
+    int symbolic(const SgShared &sh, const SgPlan &p)
+    {
+        const int32_t nr = sh.nr;
+        if (sh.knobs.fused) {             // one pass into temporaries when they fit; else two passes, as with CSRK_SPGEMM_FUSED=0
+            CSRK_TRY(room.alloc((size_t)(nr + 1) * 4));
+            CSRK_TRY(off.alloc((size_t)(nr + 1) * 8));
+            sg_small_room<<<(unsigned)ceil_div(nr, 256), 256>>>(sh.ub.as<int64_t>(), sh.route.as<unsigned char>(), nr, room.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            CSRK_TRY(exclusive_scan_i32_to_i64(room.as<int32_t>(), off.as<int64_t>(), nr, nullptr));
+            int64_t total = 0;
+            CSRK_HIP(hipMemcpy(&total, off.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost));
+            fused = sgplan::small_fused(total);
+            if (fused && (tci.alloc((size_t)total * 4) != CSRK_OK || tvs.alloc((size_t)total * 8) != CSRK_OK)) {
+                tci.release();            // no room for the temporary: two passes
+                tvs.release();
+                fused = false;
+            }
+            any = total > 0;
+        }
+        if (fused) {
+            quads<true, FAST>(sh, p, sh.cnt.as<int32_t>(), nullptr, tci.as<int32_t>(), tvs.as<double>(), off.as<int64_t>());
+            CSRK_LAUNCH_CHECK();
+        } else if (any) {
+            quads<false, FAST>(sh, p, sh.cnt.as<int32_t>(), nullptr, nullptr, nullptr, nullptr);
+            CSRK_LAUNCH_CHECK();
+        }
+        if (p.hash_rows) {
+            sg_hash_kernel<false, FAST><<<(unsigned)nr, SG_THREADS>>>(sh.av, sh.bv, sh.ub.as<int64_t>(), sh.route.as<unsigned char>(),
+                                                                     sh.cnt.as<int32_t>(), nullptr, nullptr, nullptr);
+            CSRK_LAUNCH_CHECK();
+        }
+        return CSRK_OK;
+    }
+
+    template <bool FAST>
+    void numeric(const SgShared &sh, const SgPlan &p, SgOut c)
+    {
+        if (fused)
+            sg_small_copy<<<(unsigned)ceil_div((int64_t)sh.nr * 16, 256), 256>>>(room.as<int32_t>(), sh.nr, sh.cnt.as<int32_t>(),
+                                                                                off.as<int64_t>(), tci.as<int32_t>(),
+                                                                                tvs.as<double>(), c.rp, c.ci, c.vs);
+        else if (any)
+            quads<true, FAST>(sh, p, nullptr, c.rp, c.ci, c.vs, nullptr);
+        if (p.hash_rows)
+            sg_hash_kernel<true, FAST><<<(unsigned)sh.nr, SG_THREADS>>>(sh.av, sh.bv, sh.ub.as<int64_t>(), sh.route.as<unsigned char>(),
+                                                                       nullptr, c.rp, c.ci, c.vs);
+    }
+};
+
+// ---- column strips (FAST operands only): one wavefront per (row, strip) ------------------------------------------------
+struct SgStrips {
+    DevBuf list_s, ebase;                 // the strip rows and where each row's entries of A start in the numbering (sg_list_rows)
+    DevBuf emap, table, cnt_s, occ_s;     // A entry of each number, sub-range table, per-unit counts, occupancy words (two passes)
+    DevBuf off, tci, tvs;                 // the one-pass form: where each unit starts in the temporary, the temporary
+    bool fused = false;
+    unsigned grid = 0;
+
+    // the sub-range bounds of every (A entry, strip boundary): through the strip starts of B's rows when B has few rows
+    // for the entries, else by binary search per cell
+    int build_table(const SgShared &sh, const SgPlan &p)
+    {
+        const Matrix *a = sh.a, *b = sh.b;
+        const int32_t strips = p.strips, n_strip_e = p.n_strip_e;
+        const unsigned cells = (unsigned)ceil_div((int64_t)n_strip_e * (strips + 1), 256);
+        if ((int64_t)b->nrows <= 2 * (int64_t)n_strip_e) {
+            DevBuf sp, start_bits;
+            CSRK_TRY(sp.alloc((size_t)b->nrows * (strips + 1) * 4));
+            CSRK_TRY(start_bits.alloc((size_t)(b->nnz / 32 + 2) * 4));
+            CSRK_HIP(hipMemsetAsync(start_bits.p, 0, (size_t)(b->nnz / 32 + 2) * 4, nullptr));
+            sg_strip_rowstarts<<<(unsigned)ceil_div(b->nrows, 256), 256>>>((const int32_t *)b->d_rowptrs, b->nrows, strips,
+                                                                          start_bits.as<uint32_t>(), sp.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            sg_strip_rowptrs<<<(unsigned)ceil_div(b->nnz, 256), 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows, b->nnz,
+                                                                      strips, start_bits.as<uint32_t>(), sp.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            sg_strip_table_gather<<<cells, 256>>>(a->d_colinds, emap.as<int32_t>(), sp.as<int32_t>(), n_strip_e, strips,
+                                                  table.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            // (`sp` goes back to the pool here: every launch of this call is on the default stream, in order)
+        } else {
+            sg_strip_table<<<cells, 256>>>(a->d_colinds, (const int32_t *)b->d_rowptrs, b->d_colinds, emap.as<int32_t>(), n_strip_e,
+                                           strips, table.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+        }
+        return CSRK_OK;
+    }
+
+    // MODE 0: count (two passes), 1: write (two passes), 2: both into the temporary (one pass)
+    template <int MODE>
+    void launch(const SgShared &sh, const SgPlan &p, unsigned g, int32_t *cnt, SgOut c, const int64_t *t_off, int32_t *next)
+    {
+        const Matrix *a = sh.a, *b = sh.b;
+        sg_strip_kernel<MODE><<<g, WAVE>>>((const int32_t *)a->d_rowptrs, (const double *)a->d_values, b->d_colinds,
+                                           (const double *)b->d_values, b->nnz - 1, list_s.as<int32_t>(), ebase.as<int32_t>(),
+                                           p.n_strip, p.strips, p.n_strip_e, table.as<int32_t>(), cnt_s.as<int32_t>(),
+                                           MODE == 2 ? nullptr : occ_s.as<unsigned long long>(), cnt, c.rp, c.ci, c.vs, t_off, next);
+    }
+
+    int symbolic(const SgShared &sh, const SgPlan &p)
+    {
+        const Matrix *a = sh.a;
+        const int32_t strips = p.strips, n_strip = p.n_strip, n_strip_e = p.n_strip_e;
+        const int64_t n_units = (int64_t)n_strip * strips;
+        CSRK_TRY(emap.alloc((size_t)n_strip_e * 4));
+        CSRK_TRY(table.alloc((size_t)n_strip_e * (strips + 1) * 4));
+        CSRK_TRY(cnt_s.alloc((size_t)n_units * 4));
+        sg_strip_expand<<<(unsigned)n_strip, 256>>>((const int32_t *)a->d_rowptrs, list_s.as<int32_t>(), ebase.as<int32_t>(),
+                                                    emap.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(build_table(sh, p));
+        grid = (unsigned)(n_units < (int64_t)sh.grid_lds * SGS_WAVES_PER_CU ? n_units : (int64_t)sh.grid_lds * SGS_WAVES_PER_CU);
+        if (sh.knobs.fused) {             // one pass into a temporary when it fits; else two passes, as with CSRK_SPGEMM_FUSED=0
+            DevBuf cap;
+            CSRK_TRY(cap.alloc((size_t)(n_units + 1) * 4));
+            CSRK_TRY(off.alloc((size_t)(n_units + 1) * 8));
+            sg_strip_cap<<<(unsigned)ceil_div(n_units * WAVE, 256), 256>>>((const int32_t *)a->d_rowptrs, list_s.as<int32_t>(),
+                                                                        ebase.as<int32_t>(), n_strip, strips, n_strip_e,
+                                                                        table.as<int32_t>(), cap.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+            CSRK_TRY(exclusive_scan_i32_to_i64(cap.as<int32_t>(), off.as<int64_t>(), n_units, nullptr));
+            int64_t total_cap = 0;
+            CSRK_HIP(hipMemcpy(&total_cap, off.as<int64_t>() + n_units, 8, hipMemcpyDeviceToHost));
+            fused = sgplan::strip_fused(total_cap);
+            if (fused && (tci.alloc((size_t)(total_cap + 1) * 4) != CSRK_OK || tvs.alloc((size_t)(total_cap + 1) * 8) != CSRK_OK)) {
+                tci.release();            // no room for the temporary on this device now: two passes
+                tvs.release();
+                fused = false;
+            }
+        }
+        if (fused) {
+            launch<2>(sh, p, grid, sh.cnt.as<int32_t>(), SgOut{nullptr, tci.as<int32_t>(), tvs.as<double>()}, off.as<int64_t>(),
+                      sh.next.as<int32_t>() + 3);
+        } else {
+            CSRK_TRY(occ_s.alloc((size_t)n_units * SGS_CHUNKS * 8));
+            const unsigned grid_sym = (unsigned)(n_units < (int64_t)sh.grid_lds * 32 ? n_units : (int64_t)sh.grid_lds * 32);
+            launch<0>(sh, p, grid_sym, sh.cnt.as<int32_t>(), SgOut{nullptr, nullptr, nullptr}, nullptr, sh.next.as<int32_t>() + 3);
+        }
+        CSRK_LAUNCH_CHECK();
+        return CSRK_OK;
+    }
+
+    void numeric(const SgShared &sh, const SgPlan &p, SgOut c)
+    {
+        if (fused)
+            sg_strip_copy<<<(unsigned)ceil_div((int64_t)p.n_strip * p.strips * WAVE, 256), 256>>>(
+                list_s.as<int32_t>(), p.n_strip, p.strips, cnt_s.as<int32_t>(), off.as<int64_t>(), tci.as<int32_t>(),
+                tvs.as<double>(), c.rp, c.ci, c.vs);
+        else
+            launch<1>(sh, p, grid, nullptr, c, nullptr, sh.next.as<int32_t>() + 4);
+    }
+};
+
+// ---- expand, sort, compress ---------------------------------------------------------------------------------------------
+struct SgEsc {
+    DevBuf list_e, pu, off;               // the rows (sg_list_rows), their product counts, where each row's products start
+    std::unique_ptr<Matrix> sorted;       // the product matrix, every row in ascending column order: from the counting step to the write
+    DevBuf tile_cnt, tile_off, first_run; // run numbering: runs per tile, their scan, the first run of each row
+    int32_t n = 0, n_pos = 0, tiles = 0;
+
+    // (the plan's question: how many products do the n listed rows have?)
+    int count_products(const SgShared &sh, int32_t n_rows, int64_t *products)
+    {
+        CSRK_TRY(pu.alloc((size_t)(n_rows + 1) * 8));
+        CSRK_TRY(off.alloc((size_t)(n_rows + 1) * 8));
+        sg_esc_gather<<<(unsigned)ceil_div(n_rows, 256), 256>>>(list_e.as<int32_t>(), n_rows, sh.ub.as<int64_t>(), pu.as<int64_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(exclusive_scan_i64(pu.as<int64_t>(), off.as<int64_t>(), n_rows, nullptr));
+        CSRK_HIP(hipMemcpy(products, off.as<int64_t>() + n_rows, 8, hipMemcpyDeviceToHost));
+        return CSRK_OK;
+    }
+
+    // MODE 0: runs per tile, 1: the first run of each row, 2: every run added front to back into its place in C
+    template <int MODE>
+    void runs(SgOut c)
+    {
+        sg_esc_runs<MODE><<<(unsigned)tiles, 256>>>(list_e.as<int32_t>(), n, (const int32_t *)sorted->d_rowptrs, sorted->d_colinds,
+                                                    (const double *)sorted->d_values, n_pos, tile_cnt.as<int32_t>(),
+                                                    tile_off.as<int32_t>(), first_run.as<int32_t>(), c.rp, c.ci, c.vs);
+    }
+
+    // products out in the reference's order, two stable transposes, runs counted
+    template <bool FAST>
+    int symbolic(const SgShared &sh, const SgPlan &p)
+    {
+        n = p.n_esc;
+        std::unique_ptr<Matrix> pm, pt;
+        CSRK_TRY(sg_new_matrix(n, sh.b->ncols, p.esc_products, &pm));
+        sg_esc_rowptr<<<(unsigned)ceil_div(n + 1, 256), 256>>>(off.as<int64_t>(), n, (int32_t *)pm->d_rowptrs);
+        bool launched = hipGetLastError() == hipSuccess;
+        sg_esc_expand<FAST><<<(unsigned)n, 256>>>(sh.av, sh.bv, list_e.as<int32_t>(), off.as<int64_t>(), pm->d_colinds,
+                                                  (double *)pm->d_values);
+        if (launched && hipGetLastError() != hipSuccess) launched = false;
+        if (!launched) {
+            set_error("expand-sort-compress: kernel launch failed");
+            return CSRK_ERR_HIP;
+        }
+        CSRK_TRY(sg_transpose(pm.get(), &pt));
+        pm.reset();
+        CSRK_TRY(sg_transpose(pt.get(), &sorted));
+        pt.reset();
+        n_pos = (int32_t)p.esc_products;
+        tiles = (int32_t)ceil_div(n_pos, SGE_TILE);
+        CSRK_TRY(tile_cnt.alloc((size_t)(tiles + 1) * 4));
+        CSRK_TRY(tile_off.alloc((size_t)(tiles + 1) * 4));
+        CSRK_TRY(first_run.alloc((size_t)(n + 1) * 4));
+        runs<0>(SgOut{nullptr, nullptr, nullptr});
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(exclusive_scan_i32(tile_cnt.as<int32_t>(), tile_off.as<int32_t>(), tiles, nullptr));
+        runs<1>(SgOut{nullptr, nullptr, nullptr});
+        CSRK_LAUNCH_CHECK();
+        sg_esc_rowcnt<<<(unsigned)ceil_div(n, 256), 256>>>(list_e.as<int32_t>(), n, first_run.as<int32_t>(),
+                                                           tile_off.as<int32_t>() + tiles, sh.cnt.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        return CSRK_OK;
+    }
+
+    void numeric(SgOut c)
+    {
+        sg_esc_rowbase<<<(unsigned)ceil_div(n, 256), 256>>>(list_e.as<int32_t>(), n, c.rp, first_run.as<int32_t>());
+        runs<2>(c);
+    }
+};
+
+// ---- large rows: the fallback paths above SG_CAP products ---------------------------------------------------------------
+struct SgLargeRows {
+    DevBuf list;                          // the rows (sg_list_rows)
+    DevBuf list_a, list_h, list_b, n_ab;  // after the LDS count: rows for the LDS tiles, the big hash table, the HBM work rows; how many
+    DevBuf work, mark, scratch;           // the dense path's HBM work, marker and sort rows, one of each per workgroup
+    int64_t scratch_len = 1;
+    int grid_dense = 0;
+    bool lds_symbolic = false;            // the distinct outputs are counted in LDS (B narrow enough), which splits the rows three ways
+    int32_t n_lds = 0, n_hash = 0, n_hbm = 0;
+
+    int alloc_dense(const SgShared &sh, const SgPlan &p)      // when some row needs the dense path
+    {
+        if (work.p) return CSRK_OK;
+        const int32_t nc = sh.b->ncols;
+        grid_dense = sgplan::grid_dense(p.n_large, nc, scratch_len);
+        CSRK_TRY(work.alloc((size_t)grid_dense * nc * 8));
+        CSRK_TRY(mark.alloc((size_t)grid_dense * nc * 4));
+        CSRK_TRY(scratch.alloc((size_t)grid_dense * scratch_len * 4));
+        CSRK_HIP(hipMemset(work.p, 0, work.bytes));
+        CSRK_HIP(hipMemset(mark.p, 0, mark.bytes));
+        return CSRK_OK;
+    }
+
+    // before the other routes' symbolic steps: which form the count takes, and the dense rows when it is the dense one
+    template <bool FAST>
+    int prepare(const SgShared &sh, const SgPlan &p)
+    {
+        lds_symbolic = p.n_large > 0 && sh.b->ncols <= SGL_MAXBITS;
+        if (lds_symbolic) {
+            CSRK_HIP(hipFuncSetAttribute((const void *)sg_lds_symbolic_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
+            CSRK_HIP(hipFuncSetAttribute((const void *)sg_lds_numeric_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)((size_t)SGL_W * 8 + SGL_W / 8)));
+            CSRK_HIP(hipFuncSetAttribute((const void *)sg_hash_big_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        }
+        if (p.n_large > 0 && !lds_symbolic) CSRK_TRY(alloc_dense(sh, p));
+        return CSRK_OK;
+    }
+
+    template <bool FAST>
+    int symbolic(const SgShared &sh, const SgPlan &p)
+    {
+        const int32_t n_large = p.n_large, nc = sh.b->ncols;
+        if (!lds_symbolic) {
+            sg_dense_kernel<false, FAST><<<grid_dense, SG_THREADS>>>(sh.av, sh.bv, list.as<int32_t>(), n_large, work.as<double>(),
+                                                                    mark.as<int32_t>(), nullptr, 0, sh.cnt.as<int32_t>(), nullptr,
+                                                                    nullptr, nullptr);
+            CSRK_LAUNCH_CHECK();
+            n_hbm = n_large;
+            return CSRK_OK;
+        }
+        const size_t lds = (size_t)((nc + 31) / 32) * 4;
+        sg_lds_symbolic_kernel<FAST><<<(unsigned)(n_large < sh.grid_lds ? n_large : sh.grid_lds), SGL_THREADS, lds>>>(
+            sh.av, sh.bv, list.as<int32_t>(), n_large, sh.cnt.as<int32_t>(), sh.next.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        // numeric: nearly full rows -> LDS tiles, few distinct outputs -> the big hash table, the others -> HBM work rows
+        CSRK_TRY(list_a.alloc((size_t)n_large * 4));
+        CSRK_TRY(list_h.alloc((size_t)n_large * 4));
+        CSRK_TRY(list_b.alloc((size_t)n_large * 4));
+        CSRK_TRY(n_ab.alloc(12));
+        CSRK_HIP(hipMemset(n_ab.p, 0, 12));
+        sg_split_large<<<(unsigned)ceil_div(n_large, 256), 256>>>(list.as<int32_t>(), n_large, sh.cnt.as<int32_t>(), nc, SGB_CAP,
+                                                                 list_a.as<int32_t>(), list_h.as<int32_t>(), list_b.as<int32_t>(),
+                                                                 n_ab.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        int32_t nab[3] = {0, 0, 0};
+        CSRK_HIP(hipMemcpy(nab, n_ab.p, 12, hipMemcpyDeviceToHost));
+        n_lds = nab[0];
+        n_hash = nab[1];
+        n_hbm = nab[2];
+        if (n_hbm > 0) CSRK_TRY(alloc_dense(sh, p));
+        return CSRK_OK;
+    }
+
+    template <bool FAST>
+    void numeric_lds(const SgShared &sh, SgOut c)
+    {
+        const int grid_lds = sh.grid_lds;
+        if (n_lds > 0)
+            sg_lds_numeric_kernel<FAST><<<(unsigned)(n_lds < grid_lds ? n_lds : grid_lds), SGL_THREADS, (size_t)SGL_W * 8 + SGL_W / 8>>>(
+                sh.av, sh.bv, list_a.as<int32_t>(), n_lds, c.rp, c.ci, c.vs, sh.next.as<int32_t>() + 1);
+        if (n_hash > 0)
+            sg_hash_big_kernel<FAST><<<(unsigned)(n_hash < grid_lds ? n_hash : grid_lds), SGL_THREADS,
+                                       (size_t)SGB_SLOTS * 12 + (size_t)SGB_CAP * 12>>>(sh.av, sh.bv, list_h.as<int32_t>(), n_hash, c.rp,
+                                                                                        c.ci, c.vs, sh.next.as<int32_t>() + 2);
+    }
+
+    template <bool FAST>
+    void numeric_hbm(const SgShared &sh, SgOut c)
+    {
+        if (n_hbm > 0)
+            sg_dense_kernel<true, FAST><<<grid_dense, SG_THREADS>>>(sh.av, sh.bv, lds_symbolic ? list_b.as<int32_t>() : list.as<int32_t>(),
+                                                                   n_hbm, work.as<double>(), mark.as<int32_t>(), scratch.as<int32_t>(),
+                                                                   scratch_len, nullptr, c.rp, c.ci, c.vs);
+    }
+};
+
+// ---- the plan: products counted, rows listed by route, the budgets asked -------------------------------------------
+// ub[i] <- the products of row i (sg_count_products; rows of many entries through the lists of long rows)
+template <bool FAST>
+static int sg_count_rows(const SgShared &sh, SgPlanScratch &tmp, SgStrips &strip)
+{
+    const int32_t nr = sh.nr;
+    const int64_t count_blocks = sgplan::count_blocks(nr);
+    const int32_t long_cap = sgplan::long_cap(nr);            // 32 rows per workgroup
+    CSRK_TRY(tmp.long_cnt.alloc((size_t)(SG_LONG_LISTS + 1) * SG_LONG_STRIDE * 4));
+    CSRK_TRY(tmp.counters.alloc(16));
+    CSRK_TRY(strip.list_s.alloc((size_t)sgplan::list_s_slots(nr, sh.a->nnz) * 4));
+    // the lists of long rows, then the list of very long rows: they borrow the strip list's allocation, which sg_list_rows
+    // fills only after the counting is done with them
+    int32_t *const long_rows = strip.list_s.as<int32_t>();
+    CSRK_HIP(hipMemsetAsync(tmp.long_cnt.p, 0, (size_t)(SG_LONG_LISTS + 1) * SG_LONG_STRIDE * 4, nullptr));
+    sg_count_products<FAST><<<(unsigned)count_blocks, 256>>>(sh.av, sh.bv, sh.ub.as<int64_t>(), long_rows, long_cap, tmp.long_cnt.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    sg_count_products_long<FAST><<<1024, 256>>>(sh.av, sh.bv, sh.ub.as<int64_t>(), long_rows, long_cap, tmp.long_cnt.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the strips need B's rows strictly ascending (our transpose's are)
+static int sg_rows_ascend(const Matrix *b, DevBuf &sorted_bad, bool *ascend)
+{
+    CSRK_TRY(sorted_bad.alloc(4));
+    CSRK_HIP(hipMemset(sorted_bad.p, 0, 4));
+    sg_sorted_check<<<(unsigned)ceil_div(b->nnz - 1, 256), 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows, b->nnz,
+                                                                 sorted_bad.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    int32_t bad = 0;
+    CSRK_HIP(hipMemcpy(&bad, sorted_bad.p, 4, hipMemcpyDeviceToHost));
+    *ascend = !bad;
+    return CSRK_OK;
+}
+
+// ... and into device memory?  When the room is not there even after the pool has given its cached blocks back, the
+// fallback paths take over instead of failing the whole product on an allocation half-way through.
+static int sg_esc_fits_device(int64_t products, bool *fits)
+{
+    size_t mfree = 0, mtotal = 0;
+    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
+    *fits = sgplan::esc_fits_memory(products, mfree);
+    if (!*fits) {
+        (void)csrk_trim_cache();
+        CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
+        *fits = sgplan::esc_fits_memory(products, mfree);
+    }
+    return CSRK_OK;
+}
+
+// Every row gets its route (sg_list_rows) and every route its list.  The rows are listed AGAIN, without the route, when
+// the strips' sub-range table would not pay for itself (sgplan::table_pays), or when the products of the
+// expand-sort-compress rows are beyond the sort's budget (esc_fits_sort) or free device memory (esc_fits_memory).
+template <bool FAST>
+static int sg_plan(SgShared &sh, bool b_rows_ascend, SgPlanScratch &tmp, SgStrips &strip, SgEsc &esc, SgLargeRows &large, SgPlan *plan)
+{
+    const Matrix *b = sh.b;
+    const int32_t nr = sh.nr;
+    SgPlan &p = *plan;
+    CSRK_TRY(sg_count_rows<FAST>(sh, tmp, strip));
+    CSRK_TRY(strip.ebase.alloc((size_t)(nr + 1) * 4));
+    p.strips = sgplan::strips_in_force(b->ncols, nr, FAST, sh.knobs.strips);
+    if (p.strips > 0 && b->nnz > 1 && !b_rows_ascend) {
+        bool ascend = false;
+        CSRK_TRY(sg_rows_ascend(b, tmp.sorted_bad, &ascend));
+        if (!ascend) p.strips = 0;
+    }
+    // expand-sort-compress takes the rows above esc_min products that are not dense enough for the strips
+    p.esc_min = sgplan::esc_min(sh.knobs.esc);
+    p.s_dense = sgplan::s_dense(b->ncols);
+    CSRK_TRY(sh.route.alloc((size_t)nr + 1));
+    CSRK_TRY(esc.list_e.alloc((size_t)(nr + 1) * 4));
+    int32_t cnts[4] = {0, 0, 0, 0};      // rows of the fallback paths, of the strips, the strip rows' entries of A, rows of ESC
+    for (;;) {
+        CSRK_HIP(hipMemset(tmp.counters.p, 0, 16));
+        CSRK_HIP(hipMemset(sh.route.p, 0, (size_t)nr + 1));
+        for (int pass = 0; pass < (p.strips > 0 ? 2 : 1); pass++) {
+            sg_list_rows<FAST><<<(unsigned)ceil_div(nr, SG_LIST_THREADS), SG_LIST_THREADS>>>(
+                sh.av, sh.ub.as<int64_t>(), nr, p.s_dense, p.strips > 0 ? 1 : 0, p.esc_min, pass, sh.route.as<unsigned char>(),
+                large.list.as<int32_t>(), strip.list_s.as<int32_t>(), strip.ebase.as<int32_t>(), esc.list_e.as<int32_t>(),
+                tmp.counters.as<int32_t>());
+            CSRK_LAUNCH_CHECK();
+        }
+        CSRK_HIP(hipMemcpy(cnts, tmp.counters.p, 16, hipMemcpyDeviceToHost));
+        if (p.strips > 0 && !sgplan::table_pays(cnts[2], p.strips)) {
+            p.strips = 0;                 // workgroup paths
+            continue;
+        }
+        if (cnts[3] > 0) {
+            CSRK_TRY(esc.count_products(sh, cnts[3], &p.esc_products));
+            bool fits = sgplan::esc_fits_sort(p.esc_products);
+            if (fits) CSRK_TRY(sg_esc_fits_device(p.esc_products, &fits));
+            if (!fits) {
+                p.esc_min = -1;           // the round-1 heavy-row paths take these rows
+                continue;
+            }
+        }
+        break;
+    }
+    p.n_large = cnts[0];
+    p.n_strip = cnts[1];
+    p.n_strip_e = cnts[2];
+    p.n_esc = cnts[3];
+    p.hash_rows = sgplan::hash_rows(p.esc_min);
+    p.mid_rows = sgplan::mid_rows(p.esc_min);
+    return CSRK_OK;
+}
+
+static void sg_fill_stats(bool fast, const SgPlan &p, const SgSmallRows &small, const SgStrips &strip, const SgLargeRows &large)
+{
+    int64_t *st = t_last_stats;
+    st[SG_STAT_GENERAL] = 1;
+    st[SG_STAT_FAST] = fast ? 1 : 0;
+    st[SG_STAT_STRIPS] = p.strips;
+    st[SG_STAT_STRIP_ROWS] = p.n_strip;
+    st[SG_STAT_STRIP_ENTRIES] = p.n_strip_e;
+    st[SG_STAT_STRIP_FUSED] = strip.fused ? 1 : 0;
+    st[SG_STAT_ESC_ROWS] = p.n_esc;
+    st[SG_STAT_ESC_PRODUCTS] = p.esc_products;
+    st[SG_STAT_LARGE_ROWS] = p.n_large;
+    st[SG_STAT_LDS_SYMBOLIC] = large.lds_symbolic ? 1 : 0;
+    st[SG_STAT_LDS_ROWS] = large.n_lds;
+    st[SG_STAT_HASH_BIG_ROWS] = large.n_hash;
+    st[SG_STAT_HBM_ROWS] = large.n_hbm;
+    st[SG_STAT_SMALL_FUSED] = small.fused ? 1 : 0;
+    st[SG_STAT_MID_ROWS] = p.mid_rows ? 1 : 0;
+    st[SG_STAT_HASH_ROWS] = p.hash_rows ? 1 : 0;
+}
+
 template <bool FAST>
 static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, DevBuf *products)
 {
@@ -1587,349 +2124,51 @@ static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, De
     CSRK_REQUIRE(a->val_type != CSRK_VAL_NONE && b->val_type != CSRK_VAL_NONE,
                  "mult_ab needs values on both operands (csr/kernels/numba/multiply.py:115,120)");
     const int32_t nr = a->nrows;
+    std::unique_ptr<Matrix> c;
     if (a->nnz == 0 || b->nnz == 0) {         // no products at all (also: the walker's clamped loads need an entry of B)
-        Matrix *c = nullptr;
-        CSRK_TRY(new_matrix(nr, b->ncols, 0, 0, CSRK_VAL_F64, &c));
+        CSRK_TRY(sg_new_matrix(nr, b->ncols, 0, &c));
         if (hipMemset(c->d_rowptrs, 0, (size_t)(nr + 1) * 4) != hipSuccess) {
             set_error("hipMemset failed");
-            delete c;
             return CSRK_ERR_HIP;
         }
-        *out = c;
-        t_last_stats[0] = 1;
-        t_last_stats[1] = FAST ? 1 : 0;
+        *out = c.release();
+        t_last_stats[SG_STAT_GENERAL] = 1;
+        t_last_stats[SG_STAT_FAST] = FAST ? 1 : 0;
         return CSRK_OK;
     }
-    MatView av = view_of(a), bv = view_of(b);
-    DevBuf ub, cnt, list, work, mark, scratch, list_a, list_h, list_b, n_ab, next;
-    int grid_lds = 256;
-    unsigned grid_strip = 0;
-    int32_t n_lds = 0, n_hash = 0, n_hbm = 0;
-    bool lds_symbolic = false;
-    int64_t scratch_len = 1;
-    while (scratch_len < (int64_t)b->ncols) scratch_len <<= 1;     // padded length for the bitonic network
-    CSRK_TRY(ub.alloc((size_t)(nr + 1) * 8));
-    CSRK_TRY(cnt.alloc((size_t)(nr + 1) * 4));
-    CSRK_TRY(list.alloc((size_t)(nr + 1) * 4));
-    CSRK_HIP(hipMemset(cnt.p, 0, (size_t)(nr + 1) * 4));
-    int32_t n_large = 0;
-    int grid_dense = 0;
-    // strip rows (FAST operands only): their list, A-entry numbering, sub-range table, per-unit counts and occupancy words
-    DevBuf list_s, ebase, emap, table, cnt_s, occ_s, counters, sorted_bad, route;
-    bool strip_fused = false, hash_rows = true, mid_rows = true, small_fused = false, small_any = true;
-    DevBuf small_room, small_off, small_tci, small_tvs;
-    DevBuf strip_off, strip_tci, strip_tvs;
-    // expand-sort-compress rows: their list, the sorted product matrix (kept from the counting step to the write), run numbering
-    DevBuf list_e, esc_pu, esc_off, esc_tile_cnt, esc_tile_off, esc_first_run;
-    Matrix *esc_ps = nullptr;
-    struct EscGuard {
-        Matrix **m;
-        ~EscGuard() { delete *m; }
-    } esc_guard{&esc_ps};
-    int32_t n_esc = 0, esc_tiles = 0;
-    int64_t esc_products = 0;
-    int32_t n_strip = 0, n_strip_e = 0, strips = 0;
-    if (nr > 0) {
-        unsigned g = (unsigned)ceil_div(nr, 256);
-        // (list_s / counters are scratch here: the list of long rows and its length)
-        const int64_t count_blocks = ceil_div((int64_t)nr * 8, 256);
-        const int32_t long_cap = (int32_t)(ceil_div(count_blocks, (int64_t)SG_LONG_LISTS) * 32);      // 32 rows per workgroup
-        DevBuf long_cnt;
-        CSRK_TRY(long_cnt.alloc((size_t)(SG_LONG_LISTS + 1) * SG_LONG_STRIDE * 4));
-        CSRK_TRY(counters.alloc(16));
-        // (the lists of long rows, then the list of very long rows: at most nnz / SG_COUNT_VLONG of them)
-        CSRK_TRY(list_s.alloc((size_t)std::max<int64_t>((int64_t)nr + 1, (int64_t)SG_LONG_LISTS * long_cap + a->nnz / SG_COUNT_VLONG + 1) * 4));
-        CSRK_HIP(hipMemsetAsync(long_cnt.p, 0, (size_t)(SG_LONG_LISTS + 1) * SG_LONG_STRIDE * 4, nullptr));
-        sg_count_products<FAST><<<(unsigned)count_blocks, 256>>>(av, bv, ub.as<int64_t>(), list_s.as<int32_t>(), long_cap,
-                                                                long_cnt.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        sg_count_products_long<FAST><<<1024, 256>>>(av, bv, ub.as<int64_t>(), list_s.as<int32_t>(), long_cap, long_cnt.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        CSRK_TRY(ebase.alloc((size_t)(nr + 1) * 4));
-        const char *strips_env = getenv("CSRK_SPGEMM_STRIPS");      // 0: workgroup paths only (A/B measurements)
-        if (FAST && !(strips_env && atoi(strips_env) == 0)) {
-            strips = (int32_t)ceil_div(b->ncols, SGS_W);
-            if (strips > SGS_MAX_S || (int64_t)nr * strips > (1ll << 30)) strips = 0;
-        }
-        if (strips > 0 && b->nnz > 1 && !b_rows_ascend) {          // the strips need B's rows strictly ascending (our transpose's are)
-            CSRK_TRY(sorted_bad.alloc(4));
-            CSRK_HIP(hipMemset(sorted_bad.p, 0, 4));
-            sg_sorted_check<<<(unsigned)ceil_div(b->nnz - 1, 256), 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows,
-                                                                         b->nnz, sorted_bad.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            int32_t bad = 0;
-            CSRK_HIP(hipMemcpy(&bad, sorted_bad.p, 4, hipMemcpyDeviceToHost));
-            if (bad) strips = 0;
-        }
-        // expand-sort-compress takes the rows above esc_min products that are not dense enough for the strips
-        // (CSRK_SPGEMM_ESC=0: off -- the fallback paths run instead, as they do beyond the sort's budget)
-        const char *esc_env = getenv("CSRK_SPGEMM_ESC");
-        int64_t esc_min = (esc_env && atoi(esc_env) == 0) ? -1 : SGE_MIN;
-        int32_t s_dense = (int32_t)ceil_div(b->ncols, SGS_W);       // the strips' density test, whether they can be used or not
-        if (s_dense > SGS_MAX_S) s_dense = 0;
-        CSRK_TRY(route.alloc((size_t)nr + 1));
-        CSRK_TRY(list_e.alloc((size_t)(nr + 1) * 4));
-        int32_t cnts[4] = {0, 0, 0, 0};
-        for (;;) {
-            CSRK_HIP(hipMemset(counters.p, 0, 16));
-            CSRK_HIP(hipMemset(route.p, 0, (size_t)nr + 1));
-            for (int pass = 0; pass < (strips > 0 ? 2 : 1); pass++) {
-                sg_list_rows<FAST><<<(unsigned)ceil_div(nr, SG_LIST_THREADS), SG_LIST_THREADS>>>(av, ub.as<int64_t>(), nr, s_dense, strips > 0 ? 1 : 0, esc_min, pass,
-                                               route.as<unsigned char>(), list.as<int32_t>(), list_s.as<int32_t>(),
-                                               ebase.as<int32_t>(), list_e.as<int32_t>(), counters.as<int32_t>());
-                CSRK_LAUNCH_CHECK();
-            }
-            CSRK_HIP(hipMemcpy(cnts, counters.p, 16, hipMemcpyDeviceToHost));
-            if (strips > 0 && (int64_t)cnts[2] * (strips + 1) * 4 > SGS_TABLE_BUDGET) {
-                strips = 0;                      // the sub-range table would not pay for itself: workgroup paths
-                continue;
-            }
-            if (cnts[3] > 0) {                   // do the products of the expand-sort-compress rows fit its budget?
-                CSRK_TRY(esc_pu.alloc((size_t)(cnts[3] + 1) * 8));
-                CSRK_TRY(esc_off.alloc((size_t)(cnts[3] + 1) * 8));
-                sg_esc_gather<<<(unsigned)ceil_div(cnts[3], 256), 256>>>(list_e.as<int32_t>(), cnts[3], ub.as<int64_t>(),
-                                                                         esc_pu.as<int64_t>());
-                CSRK_LAUNCH_CHECK();
-                CSRK_TRY(exclusive_scan_i64(esc_pu.as<int64_t>(), esc_off.as<int64_t>(), cnts[3], nullptr));
-                CSRK_HIP(hipMemcpy(&esc_products, esc_off.as<int64_t>() + cnts[3], 8, hipMemcpyDeviceToHost));
-                if (esc_products > SGE_BUDGET_PRODUCTS) {
-                    esc_min = -1;                // beyond the sort's budget: the round-1 heavy-row paths take these rows
-                    continue;
-                }
-                // ... and into device memory?  The product matrix, its two transposes and the sort's scratch are ~52 B per
-                // product at the peak; when that is not there even after the pool has given its cached blocks back, the same paths take over
-                // instead of failing the whole product on an allocation half-way through.
-                size_t mfree = 0, mtotal = 0;
-                CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
-                if ((size_t)esc_products * 52 + (64u << 20) > mfree) {
-                    (void)csrk_trim_cache();
-                    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
-                    if ((size_t)esc_products * 52 + (64u << 20) > mfree) {
-                        esc_min = -1;
-                        continue;
-                    }
-                }
-            }
-            break;
-        }
-        n_esc = cnts[3];
-        // (with expand-sort-compress taking every row above 32 products, the 32-lane and workgroup-hash kernels have no rows)
-        hash_rows = esc_min < 0 || esc_min > SG_WAVE_CAP;
-        mid_rows = esc_min < 0 || esc_min > 32;
-        n_large = cnts[0];
-        n_strip = cnts[1];
-        n_strip_e = cnts[2];
-        int cus = 0;
-        CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, a->device));
-        grid_lds = cus > 0 ? cus : 256;
-        lds_symbolic = n_large > 0 && b->ncols <= SGL_MAXBITS;
-        if (lds_symbolic) {
-            CSRK_HIP(hipFuncSetAttribute((const void *)sg_lds_symbolic_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
-            CSRK_HIP(hipFuncSetAttribute((const void *)sg_lds_numeric_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)((size_t)SGL_W * 8 + SGL_W / 8)));
-            CSRK_HIP(hipFuncSetAttribute((const void *)sg_hash_big_kernel<FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        }
-        auto alloc_dense = [&]() -> int {       // HBM work / marker rows of the dense path, when some row needs it
-            if (work.p) return CSRK_OK;
-            const int64_t per = (int64_t)b->ncols * 12 + scratch_len * 4;
-            int64_t g_max = (4ll << 30) / (per > 0 ? per : 1);
-            if (g_max < 1) g_max = 1;
-            grid_dense = (int)(n_large < 256 ? n_large : 256);
-            if (grid_dense > g_max) grid_dense = (int)g_max;
-            CSRK_TRY(work.alloc((size_t)grid_dense * b->ncols * 8));
-            CSRK_TRY(mark.alloc((size_t)grid_dense * b->ncols * 4));
-            CSRK_TRY(scratch.alloc((size_t)grid_dense * scratch_len * 4));
-            CSRK_HIP(hipMemset(work.p, 0, work.bytes));
-            CSRK_HIP(hipMemset(mark.p, 0, mark.bytes));
-            return CSRK_OK;
-        };
-        if (n_large > 0 && !lds_symbolic) CSRK_TRY(alloc_dense());
-        if (n_esc > 0) {
-            // expand-sort-compress, first half: products out in the reference's order, two stable transposes, runs counted
-            Matrix *pm = nullptr, *pt = nullptr;
-            CSRK_TRY(new_matrix(n_esc, b->ncols, esc_products, 0, CSRK_VAL_F64, &pm));
-            sg_esc_rowptr<<<(unsigned)ceil_div(n_esc + 1, 256), 256>>>(esc_off.as<int64_t>(), n_esc, (int32_t *)pm->d_rowptrs);
-            int erc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
-            sg_esc_expand<FAST><<<(unsigned)n_esc, 256>>>(av, bv, list_e.as<int32_t>(), esc_off.as<int64_t>(), pm->d_colinds,
-                                                          (double *)pm->d_values);
-            if (erc == CSRK_OK && hipGetLastError() != hipSuccess) erc = CSRK_ERR_HIP;
-            if (erc != CSRK_OK) set_error("expand-sort-compress: kernel launch failed");
-            if (erc == CSRK_OK) erc = transpose_matrix(pm, 1, &pt, nullptr);
-            delete pm;
-            if (erc == CSRK_OK) erc = transpose_matrix(pt, 1, &esc_ps, nullptr);
-            delete pt;
-            CSRK_TRY(erc);
-            const int32_t n_pos = (int32_t)esc_products;
-            esc_tiles = (int32_t)ceil_div(n_pos, SGE_TILE);
-            CSRK_TRY(esc_tile_cnt.alloc((size_t)(esc_tiles + 1) * 4));
-            CSRK_TRY(esc_tile_off.alloc((size_t)(esc_tiles + 1) * 4));
-            CSRK_TRY(esc_first_run.alloc((size_t)(n_esc + 1) * 4));
-#define ESC_RUNS(MODE, C_RP, C_CI, C_VS)                                                                                     \
-    sg_esc_runs<MODE><<<(unsigned)esc_tiles, 256>>>(list_e.as<int32_t>(), n_esc, (const int32_t *)esc_ps->d_rowptrs,           \
-                                                    esc_ps->d_colinds, (const double *)esc_ps->d_values, n_pos,                 \
-                                                    esc_tile_cnt.as<int32_t>(), esc_tile_off.as<int32_t>(),                     \
-                                                    esc_first_run.as<int32_t>(), C_RP, C_CI, C_VS)
-            ESC_RUNS(0, nullptr, nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-            CSRK_TRY(exclusive_scan_i32(esc_tile_cnt.as<int32_t>(), esc_tile_off.as<int32_t>(), esc_tiles, nullptr));
-            ESC_RUNS(1, nullptr, nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-            sg_esc_rowcnt<<<(unsigned)ceil_div(n_esc, 256), 256>>>(list_e.as<int32_t>(), n_esc, esc_first_run.as<int32_t>(),
-                                                                   esc_tile_off.as<int32_t>() + esc_tiles, cnt.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-        }
-        // symbolic (rows with no products keep the zero count of the memset)
-        const unsigned gq = (unsigned)ceil_div(nr, 16), gq2 = (unsigned)ceil_div(nr, 8);
-        // the rows of at most SG_WAVE_CAP products: one pass into temporaries when they fit (CSRK_SPGEMM_FUSED=0: two passes,
-        // the form a product whose temporaries exceed the budget takes)
-        {
-            const char *sf_env = getenv("CSRK_SPGEMM_FUSED");
-            if (!(sf_env && atoi(sf_env) == 0)) {
-                CSRK_TRY(small_room.alloc((size_t)(nr + 1) * 4));
-                CSRK_TRY(small_off.alloc((size_t)(nr + 1) * 8));
-                sg_small_room<<<g, 256>>>(ub.as<int64_t>(), route.as<unsigned char>(), nr, small_room.as<int32_t>());
-                CSRK_LAUNCH_CHECK();
-                CSRK_TRY(exclusive_scan_i32_to_i64(small_room.as<int32_t>(), small_off.as<int64_t>(), nr, nullptr));
-                int64_t total = 0;
-                CSRK_HIP(hipMemcpy(&total, small_off.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost));
-                small_fused = total > 0 && total * 12 <= SGS_TEMP_BUDGET / 4;
-                if (small_fused && (small_tci.alloc((size_t)total * 4) != CSRK_OK || small_tvs.alloc((size_t)total * 8) != CSRK_OK)) {
-                    small_tci.release();             // no room for the temporary: two passes
-                    small_tvs.release();
-                    small_fused = false;
-                }
-                small_any = total > 0;
-            }
-        }
-        if (small_fused) {
-            sg_quad_kernel<16, 32, true, FAST><<<gq, 256>>>(av, bv, ub.as<int64_t>(), 0, route.as<unsigned char>(), cnt.as<int32_t>(),
-                                                            nullptr, small_tci.as<int32_t>(), small_tvs.as<double>(),
-                                                            small_off.as<int64_t>());
-            CSRK_LAUNCH_CHECK();
-            if (mid_rows)
-                sg_quad_kernel<32, SG_WAVE_CAP, true, FAST><<<gq2, 256>>>(av, bv, ub.as<int64_t>(), 32, route.as<unsigned char>(),
-                                                                      cnt.as<int32_t>(), nullptr, small_tci.as<int32_t>(),
-                                                                      small_tvs.as<double>(), small_off.as<int64_t>());
-            CSRK_LAUNCH_CHECK();
-        } else if (small_any) {
-            sg_quad_kernel<16, 32, false, FAST><<<gq, 256>>>(av, bv, ub.as<int64_t>(), 0, route.as<unsigned char>(), cnt.as<int32_t>(),
-                                                             nullptr, nullptr, nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-            if (mid_rows)
-                sg_quad_kernel<32, SG_WAVE_CAP, false, FAST><<<gq2, 256>>>(av, bv, ub.as<int64_t>(), 32, route.as<unsigned char>(),
-                                                                       cnt.as<int32_t>(), nullptr, nullptr, nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-        }
-        if (hash_rows) {
-            sg_hash_kernel<false, FAST><<<(unsigned)nr, SG_THREADS>>>(av, bv, ub.as<int64_t>(), route.as<unsigned char>(), cnt.as<int32_t>(),
-                                                                     nullptr, nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-        }
-        CSRK_TRY(next.alloc(20));
-        CSRK_HIP(hipMemset(next.p, 0, 20));
-        if constexpr (FAST) {
-            if (n_strip > 0) {
-                const int64_t n_units = (int64_t)n_strip * strips;
-                CSRK_TRY(emap.alloc((size_t)n_strip_e * 4));
-                CSRK_TRY(table.alloc((size_t)n_strip_e * (strips + 1) * 4));
-                CSRK_TRY(cnt_s.alloc((size_t)n_units * 4));
-                sg_strip_expand<<<(unsigned)n_strip, 256>>>((const int32_t *)a->d_rowptrs, list_s.as<int32_t>(), ebase.as<int32_t>(),
-                                                            emap.as<int32_t>());
-                CSRK_LAUNCH_CHECK();
-                if ((int64_t)b->nrows <= 2 * (int64_t)n_strip_e) {
-                    DevBuf sp, start_bits;
-                    CSRK_TRY(sp.alloc((size_t)b->nrows * (strips + 1) * 4));
-                    CSRK_TRY(start_bits.alloc((size_t)(b->nnz / 32 + 2) * 4));
-                    CSRK_HIP(hipMemsetAsync(start_bits.p, 0, (size_t)(b->nnz / 32 + 2) * 4, nullptr));
-                    sg_strip_rowstarts<<<(unsigned)ceil_div(b->nrows, 256), 256>>>((const int32_t *)b->d_rowptrs, b->nrows, strips,
-                                                                                  start_bits.as<uint32_t>(), sp.as<int32_t>());
-                    CSRK_LAUNCH_CHECK();
-                    sg_strip_rowptrs<<<(unsigned)ceil_div(b->nnz, 256), 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows,
-                                                                              b->nnz, strips, start_bits.as<uint32_t>(),
-                                                                              sp.as<int32_t>());
-                    CSRK_LAUNCH_CHECK();
-                    sg_strip_table_gather<<<(unsigned)ceil_div((int64_t)n_strip_e * (strips + 1), 256), 256>>>(
-                        a->d_colinds, emap.as<int32_t>(), sp.as<int32_t>(), n_strip_e, strips, table.as<int32_t>());
-                    CSRK_LAUNCH_CHECK();
-                    // (`sp` goes back to the pool here: every launch of this call is on the default stream, in order)
-                } else {
-                    sg_strip_table<<<(unsigned)ceil_div((int64_t)n_strip_e * (strips + 1), 256), 256>>>(
-                        a->d_colinds, (const int32_t *)b->d_rowptrs, b->d_colinds, emap.as<int32_t>(), n_strip_e, strips,
-                        table.as<int32_t>());
-                    CSRK_LAUNCH_CHECK();
-                }
-                grid_strip = (unsigned)(n_units < (int64_t)grid_lds * SGS_WAVES_PER_CU ? n_units : (int64_t)grid_lds * SGS_WAVES_PER_CU);
-                // one pass into a temporary when it fits (CSRK_SPGEMM_FUSED=0: the two-pass form)
-                const char *fu_env = getenv("CSRK_SPGEMM_FUSED");
-                if (!(fu_env && atoi(fu_env) == 0)) {
-                    DevBuf cap;
-                    CSRK_TRY(cap.alloc((size_t)(n_units + 1) * 4));
-                    CSRK_TRY(strip_off.alloc((size_t)(n_units + 1) * 8));
-                    sg_strip_cap<<<(unsigned)ceil_div(n_units * WAVE, 256), 256>>>((const int32_t *)a->d_rowptrs, list_s.as<int32_t>(),
-                                                                                ebase.as<int32_t>(), n_strip, strips, n_strip_e,
-                                                                                table.as<int32_t>(), cap.as<int32_t>());
-                    CSRK_LAUNCH_CHECK();
-                    CSRK_TRY(exclusive_scan_i32_to_i64(cap.as<int32_t>(), strip_off.as<int64_t>(), n_units, nullptr));
-                    int64_t total_cap = 0;
-                    CSRK_HIP(hipMemcpy(&total_cap, strip_off.as<int64_t>() + n_units, 8, hipMemcpyDeviceToHost));
-                    strip_fused = total_cap * 12 <= SGS_TEMP_BUDGET;
-                    if (strip_fused &&
-                        (strip_tci.alloc((size_t)(total_cap + 1) * 4) != CSRK_OK || strip_tvs.alloc((size_t)(total_cap + 1) * 8) != CSRK_OK)) {
-                        strip_tci.release();         // no room for the temporary on this device now: two passes
-                        strip_tvs.release();
-                        strip_fused = false;
-                    }
-                }
-                if (strip_fused) {
-                    sg_strip_kernel<2><<<grid_strip, WAVE>>>(
-                        (const int32_t *)a->d_rowptrs, (const double *)a->d_values, b->d_colinds, (const double *)b->d_values, b->nnz - 1,
-                        list_s.as<int32_t>(), ebase.as<int32_t>(), n_strip, strips, n_strip_e, table.as<int32_t>(), cnt_s.as<int32_t>(),
-                        nullptr, cnt.as<int32_t>(), nullptr, strip_tci.as<int32_t>(), strip_tvs.as<double>(),
-                        strip_off.as<int64_t>(), next.as<int32_t>() + 3);
-                } else {
-                    CSRK_TRY(occ_s.alloc((size_t)n_units * SGS_CHUNKS * 8));
-                    const unsigned grid_sym = (unsigned)(n_units < (int64_t)grid_lds * 32 ? n_units : (int64_t)grid_lds * 32);
-                    sg_strip_kernel<0><<<grid_sym, WAVE>>>(
-                        (const int32_t *)a->d_rowptrs, (const double *)a->d_values, b->d_colinds, (const double *)b->d_values, b->nnz - 1,
-                        list_s.as<int32_t>(), ebase.as<int32_t>(), n_strip, strips, n_strip_e, table.as<int32_t>(), cnt_s.as<int32_t>(),
-                        occ_s.as<unsigned long long>(), cnt.as<int32_t>(), nullptr, nullptr, nullptr, nullptr, next.as<int32_t>() + 3);
-                }
-                CSRK_LAUNCH_CHECK();
-            }
-        }
-        if (n_large > 0 && lds_symbolic) {
-            const size_t lds = (size_t)((b->ncols + 31) / 32) * 4;
-            sg_lds_symbolic_kernel<FAST><<<(unsigned)(n_large < grid_lds ? n_large : grid_lds), SGL_THREADS, lds>>>(
-                av, bv, list.as<int32_t>(), n_large, cnt.as<int32_t>(), next.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            // numeric: nearly full rows -> LDS tiles, the others -> HBM work rows
-            CSRK_TRY(list_a.alloc((size_t)n_large * 4));
-            CSRK_TRY(list_h.alloc((size_t)n_large * 4));
-            CSRK_TRY(list_b.alloc((size_t)n_large * 4));
-            CSRK_TRY(n_ab.alloc(12));
-            CSRK_HIP(hipMemset(n_ab.p, 0, 12));
-            sg_split_large<<<(unsigned)ceil_div(n_large, 256), 256>>>(list.as<int32_t>(), n_large, cnt.as<int32_t>(), b->ncols,
-                                                                     SGB_CAP, list_a.as<int32_t>(), list_h.as<int32_t>(),
-                                                                     list_b.as<int32_t>(), n_ab.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            int32_t nab[3] = {0, 0, 0};
-            CSRK_HIP(hipMemcpy(nab, n_ab.p, 12, hipMemcpyDeviceToHost));
-            n_lds = nab[0];
-            n_hash = nab[1];
-            n_hbm = nab[2];
-            if (n_hbm > 0) CSRK_TRY(alloc_dense());
-        } else if (n_large > 0) {
-            sg_dense_kernel<false, FAST><<<grid_dense, SG_THREADS>>>(av, bv, list.as<int32_t>(), n_large, work.as<double>(),
-                                                              mark.as<int32_t>(), nullptr, 0, cnt.as<int32_t>(), nullptr,
-                                                              nullptr, nullptr);
-            CSRK_LAUNCH_CHECK();
-            n_hbm = n_large;
-        }
-    }
+    // (A has entries from here on, so nr > 0)
+    SgShared sh{a, b, view_of(a), view_of(b), nr, sg_read_knobs()};
+    SgPlan plan;
+    SgPlanScratch plan_tmp;
+    SgSmallRows small;
+    SgStrips strip;
+    SgEsc esc;
+    SgLargeRows large;
+    large.scratch_len = sgplan::scratch_len(b->ncols);
+
+    CSRK_TRY(sh.ub.alloc((size_t)(nr + 1) * 8));
+    CSRK_TRY(sh.cnt.alloc((size_t)(nr + 1) * 4));
+    CSRK_TRY(large.list.alloc((size_t)(nr + 1) * 4));
+    CSRK_HIP(hipMemset(sh.cnt.p, 0, (size_t)(nr + 1) * 4));
+    CSRK_TRY(sg_plan<FAST>(sh, b_rows_ascend, plan_tmp, strip, esc, large, &plan));
+    int cus = 0;
+    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, a->device));
+    sh.grid_lds = cus > 0 ? cus : 256;
+
+    // symbolic: every route counts its rows' outputs into cnt
+    CSRK_TRY(large.prepare<FAST>(sh, plan));
+    if (plan.n_esc > 0) CSRK_TRY(esc.symbolic<FAST>(sh, plan));
+    CSRK_TRY(small.symbolic<FAST>(sh, plan));
+    CSRK_TRY(sh.next.alloc(20));
+    CSRK_HIP(hipMemset(sh.next.p, 0, 20));
+    if (FAST && plan.n_strip > 0) CSRK_TRY(strip.symbolic(sh, plan));
+    if (plan.n_large > 0) CSRK_TRY(large.symbolic<FAST>(sh, plan));
+    plan_tmp.long_cnt.release();
+
     // row pointers: int64 scan first so an overflowing product is detected, not wrapped
     DevBuf rp64;
     CSRK_TRY(rp64.alloc((size_t)(nr + 1) * 8));
-    CSRK_TRY(exclusive_scan_i32_to_i64(cnt.as<int32_t>(), rp64.as<int64_t>(), nr, nullptr));
+    CSRK_TRY(exclusive_scan_i32_to_i64(sh.cnt.as<int32_t>(), rp64.as<int64_t>(), nr, nullptr));
     int64_t c_nnz = 0;
     CSRK_HIP(hipMemcpy(&c_nnz, rp64.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost));
     if (c_nnz > INT32_MAX) {
@@ -1937,63 +2176,17 @@ static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, De
                   "multiply row blocks of A instead", (long long)c_nnz);
         return CSRK_ERR_OVERFLOW;
     }
-    Matrix *c = nullptr;
-    CSRK_TRY(new_matrix(nr, b->ncols, c_nnz, 0, CSRK_VAL_F64, &c));
-    int rc = exclusive_scan_i32(cnt.as<int32_t>(), (int32_t *)c->d_rowptrs, nr, nullptr);
-    if (rc == CSRK_OK && nr > 0 && c_nnz > 0) {
-        if (small_fused) {
-            sg_small_copy<<<(unsigned)ceil_div((int64_t)nr * 16, 256), 256>>>(small_room.as<int32_t>(), nr, cnt.as<int32_t>(),
-                                                                             small_off.as<int64_t>(), small_tci.as<int32_t>(),
-                                                                             small_tvs.as<double>(), (const int32_t *)c->d_rowptrs,
-                                                                             c->d_colinds, (double *)c->d_values);
-        } else if (small_any) {
-            sg_quad_kernel<16, 32, true, FAST><<<(unsigned)ceil_div(nr, 16), 256>>>(av, bv, ub.as<int64_t>(), 0, route.as<unsigned char>(),
-                                                                                    nullptr, (const int32_t *)c->d_rowptrs, c->d_colinds,
-                                                                                    (double *)c->d_values, nullptr);
-            if (mid_rows)
-                sg_quad_kernel<32, SG_WAVE_CAP, true, FAST><<<(unsigned)ceil_div(nr, 8), 256>>>(
-                av, bv, ub.as<int64_t>(), 32, route.as<unsigned char>(), nullptr, (const int32_t *)c->d_rowptrs, c->d_colinds,
-                (double *)c->d_values, nullptr);
-        }
-        if (hash_rows)
-            sg_hash_kernel<true, FAST><<<(unsigned)nr, SG_THREADS>>>(av, bv, ub.as<int64_t>(), route.as<unsigned char>(), nullptr,
-                                                             (const int32_t *)c->d_rowptrs,
-                                                             c->d_colinds, (double *)c->d_values);
-        if constexpr (FAST) {
-            if (n_strip > 0 && strip_fused)
-                sg_strip_copy<<<(unsigned)ceil_div((int64_t)n_strip * strips * WAVE, 256), 256>>>(
-                    list_s.as<int32_t>(), n_strip, strips, cnt_s.as<int32_t>(), strip_off.as<int64_t>(), strip_tci.as<int32_t>(),
-                    strip_tvs.as<double>(), (const int32_t *)c->d_rowptrs, c->d_colinds, (double *)c->d_values);
-            else if (n_strip > 0)
-                sg_strip_kernel<1><<<grid_strip, WAVE>>>(
-                    (const int32_t *)a->d_rowptrs, (const double *)a->d_values, b->d_colinds, (const double *)b->d_values, b->nnz - 1,
-                    list_s.as<int32_t>(), ebase.as<int32_t>(), n_strip, strips, n_strip_e, table.as<int32_t>(), cnt_s.as<int32_t>(),
-                    occ_s.as<unsigned long long>(), nullptr, (const int32_t *)c->d_rowptrs, c->d_colinds, (double *)c->d_values,
-                    nullptr, next.as<int32_t>() + 4);
-        }
-        if (n_lds > 0)
-            sg_lds_numeric_kernel<FAST><<<(unsigned)(n_lds < grid_lds ? n_lds : grid_lds), SGL_THREADS,
-                                    (size_t)SGL_W * 8 + SGL_W / 8>>>(av, bv, list_a.as<int32_t>(), n_lds,
-                                                                     (const int32_t *)c->d_rowptrs, c->d_colinds,
-                                                                     (double *)c->d_values, next.as<int32_t>() + 1);
-        if (n_hash > 0)
-            sg_hash_big_kernel<FAST><<<(unsigned)(n_hash < grid_lds ? n_hash : grid_lds), SGL_THREADS,
-                                 (size_t)SGB_SLOTS * 12 + (size_t)SGB_CAP * 12>>>(av, bv, list_h.as<int32_t>(), n_hash,
-                                                                                  (const int32_t *)c->d_rowptrs, c->d_colinds,
-                                                                                  (double *)c->d_values, next.as<int32_t>() + 2);
-        if (n_esc > 0) {
-            // expand-sort-compress, second half: every run of equal columns added front to back into its place in C
-            const int32_t n_pos = (int32_t)esc_products;
-            sg_esc_rowbase<<<(unsigned)ceil_div(n_esc, 256), 256>>>(list_e.as<int32_t>(), n_esc, (const int32_t *)c->d_rowptrs,
-                                                                    esc_first_run.as<int32_t>());
-            ESC_RUNS(2, (const int32_t *)c->d_rowptrs, c->d_colinds, (double *)c->d_values);
-        }
-#undef ESC_RUNS
-        if (n_hbm > 0)
-            sg_dense_kernel<true, FAST><<<grid_dense, SG_THREADS>>>(av, bv, lds_symbolic ? list_b.as<int32_t>() : list.as<int32_t>(),
-                                                             n_hbm, work.as<double>(), mark.as<int32_t>(),
-                                                             scratch.as<int32_t>(), scratch_len, nullptr,
-                                                             (const int32_t *)c->d_rowptrs, c->d_colinds, (double *)c->d_values);
+    CSRK_TRY(sg_new_matrix(nr, b->ncols, c_nnz, &c));
+
+    // numeric: the launches are not checked one by one; one drain and one check at the end
+    int rc = exclusive_scan_i32(sh.cnt.as<int32_t>(), (int32_t *)c->d_rowptrs, nr, nullptr);
+    if (rc == CSRK_OK && c_nnz > 0) {
+        const SgOut o{(const int32_t *)c->d_rowptrs, c->d_colinds, (double *)c->d_values};
+        small.numeric<FAST>(sh, plan, o);
+        if (FAST && plan.n_strip > 0) strip.numeric(sh, plan, o);
+        large.numeric_lds<FAST>(sh, o);
+        if (plan.n_esc > 0) esc.numeric(o);
+        large.numeric_hbm<FAST>(sh, o);
     }
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipGetLastError();
@@ -2001,21 +2194,13 @@ static int spgemm_run(Matrix *a, Matrix *b, Matrix **out, bool b_rows_ascend, De
         set_error("spgemm kernels failed: %s", hipGetErrorString(e));
         rc = CSRK_ERR_HIP;
     }
-    if (rc != CSRK_OK) {
-        delete c;
-        return rc;
-    }
-    *out = c;
-    {
-        const int64_t st[SG_N_STATS] = {1, FAST ? 1 : 0, strips, n_strip, n_strip_e, strip_fused ? 1 : 0, n_esc, esc_products,
-                                        n_large, lds_symbolic ? 1 : 0, n_lds, n_hash, n_hbm, small_fused ? 1 : 0,
-                                        mid_rows ? 1 : 0, hash_rows ? 1 : 0};
-        for (int k = 0; k < SG_N_STATS; k++) t_last_stats[k] = st[k];
-    }
+    if (rc != CSRK_OK) return rc;
+    *out = c.release();
+    sg_fill_stats(FAST, plan, small, strip, large);
     if (products) {                                  // the rows' product counts: the ordering pass needs them too
         products->release();
-        products->bytes = ub.bytes;
-        products->p = ub.take();
+        products->bytes = sh.ub.bytes;
+        products->p = sh.ub.take();
     }
     return CSRK_OK;
 }

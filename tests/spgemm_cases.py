@@ -6,7 +6,7 @@ csrk_spgemm_limits and the restated product against the oracle; tests/test_gpu_s
 same cases and compares csrk_spgemm_last_stats with the census field by field.
 
 The routing, restated.  A row of the product is sent by its product count u = sum over the entries (i, j) of A of |B_j| and
-its entry count J (sg_list_rows, spgemm_run):
+its entry count J (sg_list_rows; the driver's sg_plan decides what is in force):
   u = 0                                                     nothing
   u > SG_CAP, strip-dense, strips in force                   column strips
   u > SGE_MIN, not (strip-dense and u > SG_CAP), ESC on     expand-sort-compress
@@ -23,7 +23,8 @@ Every case is built from a generator seeded with zlib.crc32 of its name and carr
 its edge, each already evaluated to a bool.  Both test files assert them.
 
 Not reachable with a small input, and so not covered: the memory-budget fallbacks SGE_BUDGET_PRODUCTS (2 * 10^8 products
-in expand-sort-compress), its hipMemGetInfo check, SGS_TABLE_BUDGET, SGS_TEMP_BUDGET and nrows * strips > 2^30.
+in expand-sort-compress), its hipMemGetInfo check, SGS_TABLE_BUDGET, SGS_TEMP_BUDGET and nrows * strips > 2^30.  Their
+arithmetic (csrc/spgemm_plan.h) is checked on the host at every edge: tests/test_spgemm_plan_host.py.
 """
 import zlib
 

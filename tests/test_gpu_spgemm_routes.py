@@ -12,7 +12,8 @@ whenever no row of the right operand as multiplied holds a column twice, within 
 give the same bits.
 
 Not covered (no small input reaches them): the memory-budget fallbacks SGE_BUDGET_PRODUCTS, the hipMemGetInfo check,
-SGS_TABLE_BUDGET, SGS_TEMP_BUDGET and nrows * strips > 2^30.  The dense-panel route of mult_ab has its own tests.
+SGS_TABLE_BUDGET, SGS_TEMP_BUDGET and nrows * strips > 2^30 -- their arithmetic (csrc/spgemm_plan.h) is checked on the
+host, tests/test_spgemm_plan_host.py.  The dense-panel route of mult_ab has its own tests.
 """
 import numpy as np
 import pytest

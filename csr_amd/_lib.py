@@ -114,6 +114,23 @@ SIGNATURES = {
     'csrk_als_cg_get_long': (_int, [C.POINTER(_i64)]),
     'csrk_als_cg_long_limits': (_int, [C.POINTER(_i64), _int]),
     'csrk_als_cg_last_stats': (_int, [C.POINTER(_i64), _int]),
+    'csrk_panel_gram': (_int, [_i64, _i32, _vp, _i64, _int, C.c_double, _vp]),
+    'csrk_panel_gram_device': (_int, [_i64, _i32, _vp, _i64, _int, C.c_double, _vp, _vp, _i64, _vp]),
+    'csrk_panel_gram_workspace': (_int, [_i64, _i32, C.POINTER(_i64)]),
+    'csrk_panel_gram_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_als_objective_rows': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _int, _int, C.c_double, C.c_double, _vp]),
+    'csrk_als_objective_rows_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _int, _int, _int, C.c_double, C.c_double,
+                                              _vp, _vp]),
+    'csrk_als_objective': (_int, [handle_t, handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _int, C.c_double, C.c_double, _vp]),
+    'csrk_als_objective_device': (_int, [handle_t, handle_t, _vp, _i64, _vp, _i64, _i32, _int, _int, _int, C.c_double, C.c_double, _vp,
+                                         _vp, _i64, _vp]),
+    'csrk_als_objective_workspace': (_int, [_i32, _i32, _i32, _int, C.POINTER(_i64)]),
+    'csrk_als_objective_limits': (_int, [C.POINTER(_i64), _int]),
+    'csrk_als_fit': (_int, [handle_t, handle_t, _i32, _i32, _int, _i32, C.c_double, _int, _int, _int, C.c_double, C.c_double, _vp, _i64,
+                            _vp, _i64, _vp, _vp]),
+    'csrk_als_fit_device': (_int, [handle_t, handle_t, _i32, _i32, _int, _i32, C.c_double, _int, _int, _int, C.c_double, C.c_double, _vp,
+                                   _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'csrk_als_fit_workspace': (_int, [_i32, _i32, _i32, _int, _int, _int, C.POINTER(_i64)]),
     'csrk_topk_scores': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp, _i64,
                                 _vp]),
     'csrk_topk_scores_device': (_int, [handle_t, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _int, _i32, C.c_double, _vp, _i64, _vp,

@@ -398,7 +398,8 @@ class CSR:
         over the row's n_i stored columns j, with w = 1 or (weighted=True) the entry's value and c = the value
         (rhs='values'), 1 ('ones') or 1 + the value ('one_plus_values': implicit feedback with values stored as
         confidence - 1).  Explicit ALS: weighted=False, rhs='values', a ridge in base or reg_per_entry.  Implicit ALS:
-        weighted=True, rhs='one_plus_values', base = V^T V + lambda I.  The k x k block is gram_rows' block bit for bit,
+        weighted=True, rhs='one_plus_values', base = V^T V + lambda I (kernels.hip.panel_gram(V, lambda) computes it on the
+        device in a fixed order; als_fit runs whole sweeps).  The k x k block is gram_rows' block bit for bit,
         but it is built and factorised (LDL^T, no pivoting, a fixed order of fused multiply-adds) on the chip and never
         stored, so the result is small whatever k and no max_bytes is needed (include/csrk.h, csrk_als_rows).  A row
         whose system has a pivot that is not positive (an empty row without base, an indefinite base) raises ValueError
@@ -447,6 +448,61 @@ class CSR:
         with releasing(K.to_handle(self), K) as h:
             U, resid, taken = fn(h, V, weighted, rhs, base, lam, lam_n, (rb, re_), steps, x0, tol)
         return (U, resid, taken) if return_info else U
+
+    def als_objective(self, U, V, *, weighted=False, rhs='values', implicit=False, reg=0.0, reg_per_entry=0.0):
+        """
+        What the ALS half-steps minimise, one float, for row factors U [nrows x k] and column factors V [ncols x k]
+        (float64):
+            sum_ij (w_ij s_ij - 2 c_ij) s_ij  +  sum_i (reg + reg_per_entry n_i) |u_i|^2  +  sum_j (reg + reg_per_entry m_j) |v_j|^2
+        over the stored entries, s_ij = u_i . v_j, w and c as in als_rows, n_i and m_j the entries of row i and column j;
+        with implicit=True plus sum over ALL pairs of s_ij^2, computed as <U^T U, V^T V>.  This is the usual loss minus a
+        constant that does not depend on the factors: sum a_ij^2 for explicit ALS (weighted=False, rhs='values'),
+        sum (1 + a_ij) for Hu-Koren implicit ALS (weighted=True, rhs='one_plus_values', implicit=True), so a sweep that
+        helps lowers it.  Every sum runs on the device in a fixed order (include/csrk.h, rule J).  Not a reference entry
+        point.
+        """
+        K, fn = self._ext('als_objective')
+        K.als_objective_args(self, None, U, V, rhs, reg, reg_per_entry)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            with releasing(K.transpose(h, True), K) as th:
+                return fn(h, th, U, V, weighted, rhs, implicit, reg, reg_per_entry)
+
+    def als_fit(self, U0, V0, *, sweeps=10, solver='cg', steps=3, weighted=False, rhs='values', implicit=False, reg=0.0,
+                reg_per_entry=0.0, tol=0.0, return_objective=False, return_info=False):
+        """
+        Alternating least squares from the caller's start factors U0 [nrows x k] and V0 [ncols x k] (float64; no random
+        numbers are drawn here): `sweeps` times a half-step for the rows' factors, then one for the columns' on the
+        transpose, with both panels on the device throughout.  solver='cg': als_rows_cg, `steps` warm-started steps (tol
+        as there); solver='exact': als_rows.  The shared base is not a parameter: implicit=True makes it V^T V (resp. U^T U)
+        on the device in a fixed order, and reg is the constant ridge, reg_per_entry the one that grows with a row's
+        entries; weighted and rhs are als_rows'.  Explicit ALS: the defaults with a reg or reg_per_entry.  Hu-Koren
+        implicit ALS: weighted=True, rhs='one_plus_values', implicit=True, values stored as confidence - 1.  The result is
+        the caller's own loop over panel_gram, als_rows[_cg] and als_objective bit for bit (include/csrk.h, rule F).
+        Returns (U, V); with return_objective=True the float64 [sweeps + 1] objective (als_objective before the first
+        sweep and after each) follows, with return_info=True the int64 [2 sweeps] count of rows per half-step whose system
+        was not positive definite (solver='exact').  Without return_info such a row raises ValueError naming the first
+        half-step that has one.  Not a reference entry point.
+        """
+        K, fn = self._ext('als_fit')
+        K.als_fit_args(self, None, U0, V0, sweeps, solver, steps, rhs, reg, reg_per_entry, tol)
+        if self.nnz > K.max_nnz:
+            raise ValueError('CSR size {} exceeds max nnz {}'.format(self.nnz, K.max_nnz))
+        with releasing(K.to_handle(self), K) as h:
+            with releasing(K.transpose(h, True), K) as th:
+                U, V, obj, bad = fn(h, th, U0, V0, sweeps, solver, steps, weighted, rhs, implicit, reg, reg_per_entry, tol,
+                                    return_objective)
+        if not return_info and bad.any():
+            first = int(np.flatnonzero(bad)[0])
+            raise ValueError(f'half-step {first} (sweep {first // 2}, the {"rows" if first % 2 == 0 else "columns"}) has '
+                             f'{int(bad[first])} systems that are not positive definite (return_info=True returns the counts)')
+        out = (U, V)
+        if return_objective:
+            out += (obj,)
+        if return_info:
+            out += (bad,)
+        return out
 
     def topk_rows(self, k, *, min_value=None, order='descending'):
         """

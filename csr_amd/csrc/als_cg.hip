@@ -32,6 +32,7 @@
 #include "common.h"
 #include "device_loads.h"
 #include "panel.h"
+#include "team_dot.h"
 #include "wave.h"
 #include <atomic>
 #include <cstdlib>
@@ -45,31 +46,7 @@ constexpr int CG_TEAMS = CG_THREADS / CG_G;
 constexpr int CG_E = 4;                  // entries in flight per team and step of the entry loop
 constexpr int CG_K_MAX = 128;            // two chunks of 64 columns (csrk_als_limits' value)
 
-// dpp_ctrl encodings (CDNA ISA): quad_perm [1, 0, 3, 2] and [2, 3, 0, 1], lanes 7 - l of a half row, 15 - l of a row
-constexpr int DPP_QUAD_X1 = 0xB1, DPP_QUAD_X2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141, DPP_ROW_MIRROR = 0x140;
-
-// rule C2's tree, in every lane of the team
-__device__ __forceinline__ double cg_team_sum(double s)
-{
-    s = __dadd_rn(s, dpp_f64<DPP_QUAD_X1>(0.0, s));
-    s = __dadd_rn(s, dpp_f64<DPP_QUAD_X2>(0.0, s));
-    s = __dadd_rn(s, dpp_f64<DPP_ROW_HALF_MIRROR>(0.0, s));
-    s = __dadd_rn(s, dpp_f64<DPP_ROW_MIRROR>(0.0, s));
-    return s;
-}
-
-// rule C2: DOT(a, b); OFFT is the panel type (it fixes which columns the lane owns)
-template <class OFFT, int NCH, class A>
-__device__ __forceinline__ double cg_dot(const A (&a)[NCH][4], const double (&b)[NCH][4], int sub, int k)
-{
-    double s = 0.0;
-#pragma unroll
-    for (int c = 0; c < NCH; c++)
-#pragma unroll
-        for (int q = 0; q < 4; q++)
-            if (64 * c + panel_off<OFFT>(sub, q) < k) s = __builtin_fma((double)a[c][q], b[c][q], s);
-    return cg_team_sum(s);
-}
+// (rule C2's DOT, cg_dot, and its tree, cg_team_sum: team_dot.h)
 
 // rule C3's first two parts: q = base y (u ascending), then q_t = fma(rho, y_t, q_t).  ys: the team's k doubles of LDS.
 template <class OFFT, int NCH, bool BW>

@@ -47,6 +47,16 @@ inline void mark_user_stream(Matrix *m, hipStream_t s)
     m->used_user_stream = true;
 }
 
+// `at` has the shape and the entry count of a's transpose (csrk_als_objective, csrk_als_fit; that it IS the transpose is
+// the caller's business)
+static int check_transpose_shape(const Matrix *a, const Matrix *at)
+{
+    CSRK_REQUIRE(at->nrows == a->ncols && at->ncols == a->nrows && at->nnz == a->nnz,
+                 "the second matrix is %d x %d with %lld entries: not the shape of the transpose of %d x %d with %lld", at->nrows, at->ncols,
+                 (long long)at->nnz, a->nrows, a->ncols, (long long)a->nnz);
+    return CSRK_OK;
+}
+
 // ---- the scalar refusals the entries share, one each: CSRK_REQUIRE with the shared words behind the entry's prefix (pre, a
 // string literal: "" or "topk_scores: " / "rank_entries: ").  A refusal that an entry words differently stays in that entry.
 #define CSRK_CHECK_K(pre, k) CSRK_REQUIRE((k) >= 1, pre "k must be at least 1 (k=%d)", k)

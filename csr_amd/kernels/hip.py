@@ -1015,6 +1015,146 @@ def als_rows_cg(h, V, scale=False, rhs='values', base=None, lam=0.0, lam_n=0.0, 
     return out, resid, taken
 
 
+def panel_gram_limits():
+    "(largest k, R = the rows of one chunk of panel_gram's sum)"
+    return _limits(lib.csrk_panel_gram_limits, 2)
+
+
+def panel_gram_args(V, ridge=0.0):
+    "(V, ldv, n, k, panel code, ridge) as the library takes them; ValueError for anything it would refuse as invalid.  No library call."
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError(f'V must be 2-D, not of shape {V.shape}')
+    if V.dtype not in _PANEL_CODES:
+        raise ValueError(f'V must be float32 or float64, not {V.dtype}')
+    if V.shape[1] == 0:
+        raise ValueError('V has no columns (k = 0)')
+    if not _is_real(ridge) or float(ridge) != float(ridge):
+        raise ValueError(f'ridge must be one real number that is not NaN, not {ridge!r}')
+    V, ldv = _panel(V, V.shape[0], 'V')
+    return V, ldv, V.shape[0], V.shape[1], _PANEL_CODES[V.dtype], float(ridge)
+
+
+def panel_gram(V, ridge=0.0):
+    """
+    G = V^T V + ridge I as a fresh float64 [k, k], exactly symmetric: the `base` of implicit-feedback ALS (als_rows,
+    als_rows_cg).  V [n x k] is float32 or float64.  Each element is a chain of fused multiply-adds over every chunk of R
+    rows (panel_gram_limits) and a fixed tree of rounded additions over the chunks; the ridge is added to the diagonal last
+    (include/csrk.h, rule P).  No rows give ridge I.  Not a reference entry point.
+    """
+    V, ldv, n, k, code, ridge = panel_gram_args(V, ridge)
+    out = _out((k, k), np.float64)
+    _call(lib.csrk_panel_gram, n, k, ptr(V), ldv, code, ridge, ptr(out))
+    return out
+
+
+def als_objective_limits():
+    "(largest k, L = the elements of one serial chunk of the objective's sums, lanes of a row's team, entries in flight per step)"
+    return _limits(lib.csrk_als_objective_limits, 4)
+
+
+def _factor_pair(a, U, V):
+    "(U, ldu, V, ldv, k) for float64 factor panels of a's rows and columns; ValueError otherwise.  No library call."
+    U, V = np.asarray(U), np.asarray(V)
+    _panel_pair(U, V)
+    if U.dtype != np.float64:
+        raise ValueError(f'U and V must be float64, not {U.dtype}')
+    U, ldu = _panel(U, a.nrows, 'U')
+    V, ldv = _panel(V, a.ncols, 'V')
+    return U, ldu, V, ldv, U.shape[1]
+
+
+def als_objective_args(a, at, U, V, rhs='values', lam=0.0, lam_n=0.0, rows=None):
+    """
+    (U, ldu, V, ldv, k, rhs code, lam, lam_n, row_begin, row_end) as the library takes them; ValueError for anything it would
+    refuse as invalid.  a and at are anything with nrows, ncols and nnz (handles or CSRs); at may be None (the rows form).
+    No library call is made.
+    """
+    U, ldu, V, ldv, k = _factor_pair(a, U, V)
+    if at is not None and (at.nrows, at.ncols, at.nnz) != (a.ncols, a.nrows, a.nnz):
+        raise ValueError(f'the second matrix is {at.nrows} x {at.ncols} with {at.nnz} entries: not the shape of the transpose of '
+                         f'{a.nrows} x {a.ncols} with {a.nnz}')
+    if not isinstance(rhs, str) or rhs not in _RHS_CODES:
+        raise ValueError(f'rhs must be one of {sorted(_RHS_CODES)}, not {rhs!r}')
+    if not _is_real(lam) or not _is_real(lam_n):
+        raise ValueError(f'the ridges must be real numbers, not {lam!r} and {lam_n!r}')
+    rb, re_ = _row_range(rows, a.nrows)
+    return U, ldu, V, ldv, k, _RHS_CODES[rhs], float(lam), float(lam_n), rb, re_
+
+
+def als_objective_rows(h, U, V, scale=False, rhs='values', lam=0.0, lam_n=0.0, data=True, rows=None):
+    """
+    The ALS objective row by row, float64 [end - begin]: for each row i of rows = (begin, end) (None: all rows)
+        J_i = sum_e (g_e - 2 c_e) s_e + (lam + lam_n n_i) |u_i|^2,   s_e = u_i . v_j,  g_e = w_e s_e (scale) or s_e,
+    with w and c as in als_rows; data=False leaves the entries out (V is not read): the regulariser alone.  U [nrows x k]
+    and V [ncols x k] are float64.  One fused multiply-add per entry in storage order (include/csrk.h, rule J1).  Not a
+    reference entry point.
+    """
+    U, ldu, V, ldv, k, rcode, lam, lam_n, rb, re_ = als_objective_args(h, None, U, V, rhs, lam, lam_n, rows)
+    out = _out(re_ - rb, np.float64)
+    _call(lib.csrk_als_objective_rows, _live(h), rb, re_, ptr(U), ldu, ptr(V), ldv, k, int(bool(scale)), rcode, int(bool(data)), lam,
+          lam_n, ptr(out))
+    return out
+
+
+def als_objective(a_h, at_h, U, V, scale=False, rhs='values', implicit=False, lam=0.0, lam_n=0.0):
+    """
+    The ALS objective, one float: the sum of als_objective_rows over a_h's rows, of the regulariser over at_h's rows (the
+    transpose: only its row lengths are read) and, with implicit=True, of <U^T U, V^T V>, the all-pairs term of implicit
+    ALS -- every sum in a fixed order (include/csrk.h, rules J2 and T).  It is the usual loss MINUS a constant that does not
+    depend on the factors: sum a_e^2 for explicit ALS (scale=False, rhs='values'), sum (1 + a_e) for Hu-Koren implicit ALS
+    (scale=True, rhs='one_plus_values', implicit=True).  Not a reference entry point.
+    """
+    U, ldu, V, ldv, k, rcode, lam, lam_n, _, _ = als_objective_args(a_h, at_h, U, V, rhs, lam, lam_n)
+    out = np.zeros(1, np.float64)
+    _call(lib.csrk_als_objective, _live(a_h), _live(at_h), ptr(U), ldu, ptr(V), ldv, k, int(bool(scale)), rcode, int(bool(implicit)),
+          lam, lam_n, ptr(out))
+    return float(out[0])
+
+
+_SOLVER_CODES = {'exact': 0, 'cg': 1}
+
+
+def als_fit_args(a, at, U0, V0, sweeps=10, solver='cg', steps=3, rhs='values', lam=0.0, lam_n=0.0, tol=0.0):
+    """
+    (U, V, k, sweeps, solver code, steps, tol2, rhs code, lam, lam_n) as the library takes them -- U and V fresh packed
+    float64 copies of the start factors, which the fit overwrites; ValueError for anything it would refuse as invalid.
+    tol is a residual 2-norm: the library takes its square.  No library call is made.
+    """
+    U, _, V, _, k, rcode, lam, lam_n, _, _ = als_objective_args(a, at, U0, V0, rhs, lam, lam_n)
+    if not _is_int(sweeps) or sweeps < 0 or sweeps > 2 ** 30:
+        raise ValueError(f'sweeps must be an integer that is not negative, not {sweeps!r}')
+    if not isinstance(solver, str) or solver not in _SOLVER_CODES:
+        raise ValueError(f'solver must be one of {sorted(_SOLVER_CODES)}, not {solver!r}')
+    if not _is_int(steps) or steps < 0 or steps > 2 ** 31 - 1:
+        raise ValueError(f'steps must be an integer that is not negative, not {steps!r}')
+    if not _is_real(tol) or not float(tol) >= 0.0:
+        raise ValueError(f'tol must be a real number that is not negative, not {tol!r}')
+    tol = float(tol)
+    return np.array(U, dtype=np.float64, order='C'), np.array(V, dtype=np.float64, order='C'), k, int(sweeps), _SOLVER_CODES[solver], \
+        int(steps), tol * tol, rcode, lam, lam_n
+
+
+def als_fit(a_h, at_h, U0, V0, sweeps=10, solver='cg', steps=3, scale=False, rhs='values', implicit=False, lam=0.0, lam_n=0.0, tol=0.0,
+            objective=False):
+    """
+    `sweeps` sweeps of alternating least squares with both factor panels on the device throughout: (U, V, objective, bad).
+    a_h is the matrix, at_h its transpose with values; U0 [nrows x k] and V0 [ncols x k] are the float64 start factors (the
+    library draws no random numbers).  A sweep is a half-step for U and one for V -- solver 'cg': als_rows_cg, `steps` steps
+    from the current factors; 'exact': als_rows -- with base = V^T V (panel_gram) under implicit=True and lam, lam_n as the
+    ridges; the result equals the caller's own loop over panel_gram, als_rows[_cg] and als_objective bit for bit
+    (include/csrk.h, rule F).  objective=True: a float64 [sweeps + 1] array, als_objective before the first sweep and after
+    each; else None.  bad: int64 [2 sweeps], per half-step the rows whose system had a pivot that is not positive
+    (always 0 for 'cg').  Not a reference entry point.
+    """
+    U, V, k, sweeps, scode, steps, tol2, rcode, lam, lam_n = als_fit_args(a_h, at_h, U0, V0, sweeps, solver, steps, rhs, lam, lam_n, tol)
+    obj = np.zeros(sweeps + 1, np.float64) if objective else None
+    bad = np.zeros(2 * sweeps, np.int64)
+    _call(lib.csrk_als_fit, _live(a_h), _live(at_h), k, sweeps, scode, steps, tol2, int(bool(scale)), rcode, int(bool(implicit)), lam,
+          lam_n, ptr(U), k, ptr(V), k, ptr(obj), ptr(bad))
+    return U, V, obj, bad
+
+
 def topk_scores_limits():
     "(largest k, largest n, rows per workgroup, items per tile, factors per LDS chunk, list entries per row for n <= 32)"
     return _limits(lib.csrk_topk_scores_limits, 6)

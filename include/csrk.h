@@ -519,6 +519,150 @@ CSRK_API int csrk_als_cg_long_limits(int64_t *out, int n);
  * in both when it issued the launch;  n <= 6. */
 CSRK_API int csrk_als_cg_last_stats(int64_t *out, int n);
 
+/* ---- panel_gram: G = V^T V + ridge I, the matrix every row's system shares ---------------------------
+ * Not a reference entry point.  Implicit-feedback ALS passes base = V^T V (+ lambda I) to csrk_als_rows[_cg]; this entry
+ * computes it on the device in a stated order, like every other number of the ALS path.  All arithmetic is float64;
+ * fma(a, b, c) is round(a b + c), one rounding.
+ *
+ * P. V is n rows of k elements, float32 or float64 by panel_type, row j at V + j * ldv (ldv >= k in elements); out is
+ *    k x k float64, packed row-major.
+ *   P1. Operands.  v_j[t] is element t of row j, float32 widened exactly to float64.  ridge is one double, not NaN.
+ *   P2. Chunks.  The rows are cut into consecutive chunks of R rows, chunk c = rows [c R, min((c + 1) R, n)); the last may
+ *       be shorter.  R is a constant of the build (csrk_panel_gram_limits' out[1]), never a function of the device, its
+ *       compute units or the launch.  For chunk c and every t >= u: S_c[t][u] starts at +0.0 and takes one step per row of
+ *       the chunk, j ascending: S_c[t][u] = fma(v_j[t], v_j[u], S_c[t][u]).
+ *   P3. Tree.  The chunk partials S_0, S_1, ... are combined level by level: within a level the adjacent pairs (2 m, 2 m + 1)
+ *       are added, every addition rounded on its own, and an unpaired last partial is carried unchanged to the next level;
+ *       this repeats until one partial is left, the sum.  n = 0 (no chunk): the sum is +0.0.
+ *   P4. Output.  out[t][t] = round(sum[t][t] + ridge), the addition always made (ridge = 0.0 leaves a -0.0 sum as +0.0);
+ *       for t > u, out[t][u] = sum[t][u] and out[u][t] = out[t][u]: the result is exactly symmetric.  n = 0 gives ridge I.
+ *   P5. The result depends only on V's values, n, k, the panel type and ridge: not on ldv, the alignment, the load form,
+ *       the stream, the launch geometry or repeated calls.  Parallelism is over chunks and over (t, u), never inside a
+ *       chain; no float atomics.  NaN and Inf follow IEEE arithmetic (a created NaN has its position specified, not its
+ *       sign or payload).
+ *   P6. CSRK_ERR_INVALID: n < 0, k < 1, ldv < k, an unknown panel_type, a NaN ridge, a NULL out, a NULL V when n > 0, a V,
+ *       out or workspace that is not aligned to its element size (8 bytes for the workspace), a workspace that is NULL or
+ *       smaller than csrk_panel_gram_workspace asks for.  CSRK_ERR_UNSUPPORTED: k above csrk_panel_gram_limits' out[0] (at
+ *       least 128).  CSRK_ERR_OVERFLOW: n above 2^40.  A refused call writes nothing.  The device form allocates nothing
+ *       and never synchronises the host; its launches go on `stream` in order, and the workspace's contents afterwards
+ *       are unspecified.
+ *   Limits (csrk_panel_gram_limits): out[0] = the largest k; [1] = R;  n <= 2.  No device is touched.
+ * Host form: host pointers in and out (the panel crosses packed; synchronous). */
+CSRK_API int csrk_panel_gram(int64_t n, int32_t k, const void *V, int64_t ldv, int panel_type, double ridge, double *out);
+/* Device form: every pointer in HBM, launched on `stream` (NULL = the default stream).  d_work: work_bytes bytes, at least
+ * what csrk_panel_gram_workspace reports for (n, k) (0 for n = 0: d_work may then be NULL). */
+CSRK_API int csrk_panel_gram_device(int64_t n, int32_t k, const void *d_V, int64_t ldv, int panel_type, double ridge,
+                                    double *d_out, void *d_work, int64_t work_bytes, void *stream);
+CSRK_API int csrk_panel_gram_workspace(int64_t n, int32_t k, int64_t *bytes);
+CSRK_API int csrk_panel_gram_limits(int64_t *out, int n);
+
+/* ---- the ALS objective: what a half-step minimises, per row and in total ---------------------------------
+ * Not reference entry points.  For a side with matrix A, row factors U [nrows x k] and column factors V [ncols x k], both
+ * float64, the quadratic form that csrk_als_rows and csrk_als_rows_cg minimise over U with V fixed.  J is the usual loss
+ * MINUS A CONSTANT that does not depend on the factors, so differences of J are differences of the loss:
+ *     explicit ALS (scale = 0, rhs = values, implicit = 0):
+ *         sum_e (a_e - u_i . v_j)^2 + regulariser                                          = J + sum_e a_e^2
+ *     Hu-Koren implicit ALS (scale = 1, rhs = one_plus_values, implicit = 1, values = confidence - 1):
+ *         sum_e (1 + a_e) (1 - u_i . v_j)^2 + sum over pairs not stored (u_i . v_j)^2 + regulariser = J + sum_e (1 + a_e)
+ *     regulariser = sum_i rho_i |u_i|^2 + sum_j rho'_j |v_j|^2 with the rhos of J1 over A's and A^T's rows.
+ * All arithmetic is float64; fma(a, b, c) is round(a b + c), one rounding.
+ *
+ * J. For row i of [row_begin, row_end), its entries e = (i, j_e) in storage order, n_i of them, u_i = row i of U,
+ *    v_e = row j_e of V:
+ *   J1. Per row.  w_e and c_e are exactly csrk_als_rows' (rule 1 of csrk_gram_rows and rule A3, chosen by scale and
+ *       rhs_mode); rho_i = fma(lam_n, (double)n_i, lam).  J_i starts at +0.0 and takes one step per entry, in storage order:
+ *           s_e = DOT(u_i, v_e)               rule C2's order for float64 panels
+ *           g_e = round(w_e s_e) under scale = 1, else s_e
+ *           h_e = round(g_e - 2 c_e)          (2 c_e is exact)
+ *           J_i = fma(h_e, s_e, J_i)
+ *       and after the entries J_i = fma(rho_i, DOT(u_i, u_i), J_i).  data = 0 skips the entry loop: only n_i and u_i matter
+ *       (V, the columns and the values are not read), which gives the other side's regulariser from A^T's row lengths.
+ *       csrk_als_objective_rows writes out[i - row_begin] = J_i, float64.
+ *   T.  The fixed-order sum of a float64 array x[0 .. n): x is cut into consecutive chunks of L elements (L a constant of
+ *       the build, csrk_als_objective_limits' out[1]; the last chunk may be shorter); each chunk is added serially,
+ *       ascending, from +0.0, every addition rounded; the chunk partials are combined by rule P3's tree.  n = 0: +0.0.
+ *   J2. Total.  objective = round(round(T(J over all rows of A with U, V) + T(J with data = 0 over all rows of A^T with V
+ *       in U's place)) + F).  F is +0.0 unless implicit = 1; then F = T of the k k numbers round(G_U[t][u] G_V[t][u]) in
+ *       row-major order, G_U and G_V rule P's Gram matrices of U and V with ridge 0.0: sum_i u_i^T (V^T V) u_i =
+ *       <U^T U, V^T V>, the all-pairs term of implicit ALS without a visit to all pairs.
+ *   J3. A row's J_i depends only on its entries, u_i, the V rows they name, k, scale, rhs_mode, data, lam and lam_n; the
+ *       objective only on those of all rows, on the row lengths of A^T and on implicit: not on the row range, the pointer
+ *       width, ldu, ldv, the alignment, the load form, the stream, the launch geometry or repeated calls.  Parallelism is
+ *       over rows, chunks and elements, never inside a chain; no float atomics.  Unsorted and repeated columns are just
+ *       more entries.  NaN and Inf follow IEEE arithmetic (a created NaN has its position specified, not its sign or
+ *       payload).
+ *   J4. csrk_als_objective takes A and a second handle for A^T and requires it to be ncols x nrows with A's entry count:
+ *       anything else is CSRK_ERR_INVALID.  It does NOT verify that the second matrix is the transpose; only its row
+ *       lengths are read.
+ *   J5. CSRK_ERR_INVALID: k < 1, ldu < k or ldv < k, scale, data or implicit outside {0, 1}, an unknown rhs_mode, a bad row
+ *       range, a NULL or misaligned U, V (when read) or output, a workspace that is NULL, misaligned or smaller than
+ *       csrk_als_objective_workspace asks for.  CSRK_ERR_UNSUPPORTED: k above csrk_als_objective_limits' out[0] (at least
+ *       128).  What the scalars alone decide is refused before a handle is looked at.  row_begin == row_end: CSRK_OK,
+ *       nothing launched.  A refused call writes nothing.  The device forms allocate nothing and never synchronise the
+ *       host; the handles are not modified and keep their plans.
+ *   Limits (csrk_als_objective_limits): out[0] = the largest k; [1] = L; [2] = the lanes of a row's team; [3] = the
+ *   entries a team has in flight per step;  n <= 4.  No device is touched.
+ * Host forms: host pointers in and out (panels cross packed; synchronous).  U has the matrix's nrows rows whatever the
+ * row range: row i reads U + i * ldu. */
+CSRK_API int csrk_als_objective_rows(csrk_handle_t h, int32_t row_begin, int32_t row_end, const double *U, int64_t ldu,
+                                     const double *V, int64_t ldv, int32_t k, int scale, int rhs_mode, int data, double lam,
+                                     double lam_n, double *out);
+CSRK_API int csrk_als_objective(csrk_handle_t hA, csrk_handle_t hAt, const double *U, int64_t ldu, const double *V,
+                                int64_t ldv, int32_t k, int scale, int rhs_mode, int implicit, double lam, double lam_n,
+                                double *objective);
+/* Device forms: every pointer in HBM, launched on `stream` (NULL = the default stream).  d_work: work_bytes bytes, at least
+ * what csrk_als_objective_workspace reports; its contents afterwards are unspecified. */
+CSRK_API int csrk_als_objective_rows_device(csrk_handle_t h, int32_t row_begin, int32_t row_end, const double *d_U,
+                                            int64_t ldu, const double *d_V, int64_t ldv, int32_t k, int scale,
+                                            int rhs_mode, int data, double lam, double lam_n, double *d_out, void *stream);
+CSRK_API int csrk_als_objective_device(csrk_handle_t hA, csrk_handle_t hAt, const double *d_U, int64_t ldu,
+                                       const double *d_V, int64_t ldv, int32_t k, int scale, int rhs_mode, int implicit,
+                                       double lam, double lam_n, double *d_objective, void *d_work, int64_t work_bytes,
+                                       void *stream);
+CSRK_API int csrk_als_objective_workspace(int32_t nrows, int32_t ncols, int32_t k, int implicit, int64_t *bytes);
+CSRK_API int csrk_als_objective_limits(int64_t *out, int n);
+
+/* ---- als_fit: ALS sweeps with both factor panels on the device ---------------------------------------------
+ * Not a reference entry point.  A composition: rule F defines the result as the public entries above called in a fixed
+ * order, so the fit equals a caller's own loop over them bit for bit -- without the factors crossing to the host between
+ * half-steps.
+ *
+ * F. hA is A (nrows x ncols), hAt its transpose (with values); U [nrows x k] and V [ncols x k] are float64, in: the start,
+ *    out: the result.
+ *   F1. The sequence.
+ *           objective[0] = csrk_als_objective(hA, hAt, U, V)                               (when objective is not NULL)
+ *           for s = 0 .. sweeps-1:
+ *               B = base_for(V);  U = half(hA,  V, B, start U)     -> bad[2 s]
+ *               B = base_for(U);  V = half(hAt, U, B, start V)     -> bad[2 s + 1]
+ *               objective[s + 1] = csrk_als_objective(hA, hAt, U, V)
+ *       scale, rhs_mode, implicit, lam and lam_n go to every part as given.
+ *   F2. base_for(P).  solver cg: csrk_panel_gram(P, ridge 0.0) with implicit = 1, else NULL.  solver exact:
+ *       csrk_panel_gram(P, ridge lam) with implicit = 1; else NULL when lam == 0, and otherwise csrk_panel_gram over 0 rows
+ *       with ridge lam, which is lam I (rule P4).
+ *   F3. half.  solver cg: csrk_als_rows_cg over all rows, float64 panel, lam and lam_n as given, steps = cg_steps, tol2,
+ *       x0 = the side's current factors written in place (rule C7), resid and taken NULL; its bad count is 0.  solver
+ *       exact: csrk_als_rows over all rows with lam_n (lam is in the base); bad is the number of rows whose info is not 0.
+ *       The fit does not stop on bad rows (the device form cannot know): it returns CSRK_OK with bad filled, and the rows'
+ *       Inf or NaN factors go into the next half-step as rule A5 and IEEE arithmetic have them.
+ *   F4. Nothing else influences a bit: U, V, objective and bad depend only on the two matrices, the start factors and the
+ *       scalar arguments.  sweeps = 0 is valid: the factors are unchanged and only objective[0] is written.
+ *   F5. CSRK_ERR_INVALID: every refusal of the parts (rules P6, A7, C9, J5), sweeps < 0, a solver outside {0, 1}, an hAt
+ *       that is not ncols x nrows with A's entry count, any overlap of U, V and the workspace, a workspace that is NULL,
+ *       not 16-B aligned or smaller than csrk_als_fit_workspace asks for.  CSRK_ERR_UNSUPPORTED: k above 128.  All of it
+ *       is refused before the first launch: a refused call writes nothing.  The device form issues every launch on
+ *       `stream`, in order, allocates nothing and never synchronises the host.
+ * solver: 0 exact, 1 cg.  objective: float64[sweeps + 1] or NULL; bad: int64[2 sweeps] or NULL. */
+CSRK_API int csrk_als_fit(csrk_handle_t hA, csrk_handle_t hAt, int32_t k, int32_t sweeps, int solver, int32_t cg_steps,
+                          double tol2, int scale, int rhs_mode, int implicit, double lam, double lam_n, double *U,
+                          int64_t ldu, double *V, int64_t ldv, double *objective, int64_t *bad);
+/* Device form: every pointer in HBM.  with_objective: 1 when d_objective is not NULL. */
+CSRK_API int csrk_als_fit_device(csrk_handle_t hA, csrk_handle_t hAt, int32_t k, int32_t sweeps, int solver,
+                                 int32_t cg_steps, double tol2, int scale, int rhs_mode, int implicit, double lam,
+                                 double lam_n, double *d_U, int64_t ldu, double *d_V, int64_t ldv, double *d_objective,
+                                 int64_t *d_bad, void *d_work, int64_t work_bytes, void *stream);
+CSRK_API int csrk_als_fit_workspace(int32_t nrows, int32_t ncols, int32_t k, int solver, int implicit, int with_objective,
+                                    int64_t *bytes);
+
 /* ---- transpose ------------------------------------------------------------------------
  * csr/structure.py:172-247 (_transpose_values / _transpose_structure / transpose).
  * Bit-exact with the reference's stable counting sort: output rowptrs keep the input

@@ -1,12 +1,14 @@
 // Shared between spmv.hip (the kernels a product runs, their launches, the C ABI) and spmv_plan.hip (what is built
 // once per handle: the tiers, the hot-column pack, the light stream and its cold staging): the plan's structures, the
-// tile / stream layout constants and the slot arithmetic both sides must agree on.
+// tile / stream layout constants and the slot arithmetic both sides must agree on.  (The plain structures the plan kernels
+// read and the host arithmetic that lays a plan out are in spmv_layout.h.)
 #pragma once
 #include "common.h"
 #include "device_loads.h"
 #include "wave.h"
 #include "fix56.h"
 #include "acc_groups.h"
+#include "spmv_layout.h"
 
 #include <type_traits>
 #include <vector>
@@ -59,13 +61,7 @@ struct Panel {
     int64_t listed = 0, pad_groups = 0;
 };
 
-// one segment of an accumulator-form workgroup's tile range (see "long rows, accumulator form")
-struct AccSeg {
-    int64_t tile0;    // first tile of the segment (logical: block-major order)
-    int64_t ptile0;   // ... and where it is stored; the segment's tile t is stored at ptile0 + t * n_wg
-    int32_t ntiles;   // <= ACC_SEG_TILES, all in one column block
-    int32_t blk;
-};
+// (AccSeg, one segment of an accumulator-form workgroup's tile range: spmv_layout.h)
 
 // Tier 0 in accumulator form: one group of <= ACC_MAXROWS heavy rows (see "long rows, accumulator form")
 struct AccPanel {
@@ -232,20 +228,9 @@ __host__ __device__ __forceinline__ int panel_slot_of_rank(int rank, int nn)
     return (chunk << 7) + (i < 64 ? 2 * i : 2 * (i - 64) + 1);
 }
 
-struct PanelTile {
-    int64_t j0;      // first entry of the tile in M'
-    int64_t cslot;   // where the tile's carry goes: an index into the partials' carry rows (Panel::ncs), or -1: carry_val[t]
-    int32_t i0, i1;  // rows of M' completed before the tile start / end
-    int32_t nn;      // entries in the tile
-    int32_t blk;     // column block
-};
+// (PanelTile, a tile of M', and PanelGroup, a workgroup's tiles: spmv_layout.h)
 constexpr int PANEL_CARRY_ROWS = 4;      // carry rows behind the block partials at most (a long row's first carries)
 
-struct PanelGroup {
-    int64_t t0;      // first tile
-    int32_t nt;      // tiles handled by this workgroup (all in one column block)
-    int32_t blk;
-};
 // ---- long rows, accumulator form (tier 0, default) ---------------------------------------------------
 // The pair form above spends a quarter of the tier-0 traffic on bookkeeping: a row pointer and a partial
 // per (column block, row) pair (avg. 7.8 entries), the partials re-read by the reduce, plus four

@@ -10,10 +10,7 @@
 #include <type_traits>
 
 namespace csrk {
-// tile_row[t] = number of row ends consumed before merge-path diagonal d = min(t*ITEMS, nrows+nnz).
-// Row end r (= rp[r+1]) is consumed once all its nnz are: it lies before diagonal d iff
-// rp[r+1] + r + 1 <= d.
-// CSRK_PLAN_TRACE: laps of the plan builders on stderr (each lap waits for the device)
+// CSRK_PLAN_TRACE (SpmvKnobs::trace): laps of the plan builders on stderr (each lap waits for the device)
 struct PlanTrace {
     bool on;
     double t0;
@@ -23,7 +20,7 @@ struct PlanTrace {
         clock_gettime(CLOCK_MONOTONIC, &ts);
         return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
     }
-    PlanTrace() : on(getenv("CSRK_PLAN_TRACE") != nullptr), t0(0.0)
+    explicit PlanTrace(const SpmvKnobs &knobs) : on(knobs.trace), t0(0.0)
     {
         if (on) {
             (void)hipDeviceSynchronize();
@@ -40,6 +37,9 @@ struct PlanTrace {
     }
 };
 
+// tile_row[t] = number of row ends consumed before merge-path diagonal d = min(t*ITEMS, nrows+nnz).
+// Row end r (= rp[r+1]) is consumed once all its nnz are: it lies before diagonal d iff
+// rp[r+1] + r + 1 <= d.
 template <class P>
 __global__ void merge_plan_kernel(const P *__restrict__ rp, int32_t nrows, int64_t nnz, int items,
                                   int64_t n_tiles, int32_t *__restrict__ tile_row)
@@ -267,8 +267,8 @@ __global__ void hot_slot_kernel(const int32_t *__restrict__ hot_cols, int32_t n_
     if (k < n_hot) slot[hot_cols[k]] = k;
 }
 
-static int HEAVY_MIN = 2048;      // tier 0 threshold (CSRK_HEAVY_MIN)
-static int TIERB_MIN = TIERB_MIN_DEFAULT;       // tier 1 threshold (CSRK_TIERB_MIN; 0 disables tier 1)
+constexpr int HEAVY_MIN_DEFAULT = 2048;      // tier 0 threshold (CSRK_HEAVY_MIN; the split may lower it per matrix: build_heavy_split)
+// (tier 1's threshold: TIERB_MIN_DEFAULT, CSRK_TIERB_MIN; 0 disables tier 1)
 
 template <class P>
 __global__ void heavy_flag_kernel(const P *__restrict__ rp, int32_t nrows, int32_t *__restrict__ flag,
@@ -902,23 +902,73 @@ __global__ void vec_fill_kernel(const int64_t *__restrict__ seg_off, int32_t nro
 }
 
 // ---- host side ----------------------------------------------------------------------------------
+// The builders are the steps of DESIGN.md section 4, "The plan builder", in its order.  What DECIDES a layout is plain
+// arithmetic in spmv_layout.h (checked on the host: tests/spmv_layout_host); here are the launches, the round trips and
+// the allocations.  The order in which the steps ask the pool for memory, release it and launch is behaviour (it decides
+// pool reuse and plan_bytes): a builder declares its temporaries itself, in the order they are released in reverse, and
+// hands them to its steps by reference.  Everything runs on the default stream.
 constexpr int HEAVY_STREAMS = 8;   // XCDs: blockIdx % 8 labels the XCD group (speed assumption only)
 
-// Build one panel tier: M' (column-block-major copy of the listed rows, float64 values), its tiles and
-// the workgroup list.  `xcd_streams`: order the groups so that column block b is served by workgroups
-// with blockIdx % 8 == b % 8.
-template <class P, int VT>
-static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, int64_t nnz_rows, int32_t cb,
-                       int tpw, bool xcd_streams, hipStream_t s)
+// The knobs of one plan build (spmv_layout.h: SpmvKnobs, with their parsing rules): read here, once, at the top of
+// build_plan, and handed down.  No builder reads the environment.
+static SpmvKnobs read_spmv_knobs()
 {
-    PlanTrace tr;
+    SpmvKnobStrings e;
+    e.heavy_split = getenv("CSRK_SPMV_HEAVY_SPLIT");
+    e.heavy_min = getenv("CSRK_HEAVY_MIN");
+    e.tierb_min = getenv("CSRK_TIERB_MIN");
+    e.acc_groups = getenv("CSRK_ACC_GROUPS");
+    e.acc_group_rows = getenv("CSRK_ACC_GROUP_ROWS");
+    e.nib = getenv("CSRK_SPMV_NIB");
+    e.fix56 = getenv("CSRK_SPMV_FIX56");
+    e.hot = getenv("CSRK_SPMV_HOT");
+    e.ls_stage = getenv("CSRK_LS_STAGE");
+    e.stream = getenv("CSRK_SPMV_STREAM");
+    e.trace = getenv("CSRK_PLAN_TRACE");
+    const SpmvKnobDefaults d = {HEAVY_MIN_DEFAULT, TIERB_MIN_DEFAULT, ACC_GROUPS_DEFAULT, accgroups::MAX_GROUPS, ACC_MAXROWS};
+    return parse_spmv_knobs(e, d);
+}
+
+// the device's compute units (256 where the runtime does not say)
+static int device_cus(const Matrix *m, int *cus)
+{
+    int n = 0;
+    CSRK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, m->device));
+    *cus = n > 0 ? n : 256;
+    return CSRK_OK;
+}
+
+// A builder templated on the matrix's value type, called with it as a constant: f(std::integral_constant<int, VT>).
+template <class F> static int with_val_type(int val_type, F &&f)
+{
+    if (val_type == CSRK_VAL_F64) return f(std::integral_constant<int, CSRK_VAL_F64>());
+    if (val_type == CSRK_VAL_F32) return f(std::integral_constant<int, CSRK_VAL_F32>());
+    return f(std::integral_constant<int, CSRK_VAL_NONE>());
+}
+
+// Both panels: `off` holds the scanned (block, row) pair counts.  Entries before each block's end -> the host -> tiles before
+// each block (spmvlayout::tile_starts: `items` per tile, `extra` items per block), in t0 and, for the kernels, in `bends`.
+static int block_tile_starts(const DevBuf &off, int32_t n, int32_t nb, int64_t items, int64_t extra, DevBuf &bends,
+                             std::vector<int64_t> &t0, hipStream_t s)
+{
+    CSRK_TRY(bends.alloc((size_t)(nb + 1) * 8));
+    panel_blockends_kernel<<<(unsigned)ceil_div(nb + 1, 256), 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>());
+    CSRK_LAUNCH_CHECK();
+    std::vector<int64_t> be((size_t)nb + 1);      // (host: nb is at most a few thousand)
+    CSRK_TRY(stage_d2h(be.data(), bends.p, (size_t)(nb + 1) * 8, s));
+    CSRK_HIP(hipStreamSynchronize(s));
+    t0 = spmvlayout::tile_starts(be.data(), nb, items, extra);
+    CSRK_TRY(stage_h2d(bends.p, t0.data(), (size_t)(nb + 1) * 8, s));
+    return CSRK_OK;
+}
+
+// ---- tier 1 (pair form): build_panel and its steps ------------------------------------------------
+// M': the pair counts, their scan, and the column-block-major copy of the listed rows (float64 values)
+template <class P, int VT>
+static int panel_matrix(Matrix *m, Panel *pn, int32_t n, int32_t nb, int32_t cb, int64_t nnz_rows, DevBuf &off, hipStream_t s)
+{
     const P *rp = (const P *)m->d_rowptrs;
-    const int32_t n = (int32_t)rows.size();
-    const int32_t nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, cb);
     const int64_t pairs = (int64_t)n * nb;
-    CSRK_TRY(pn->row_list.alloc((size_t)n * 4));
-    CSRK_TRY(stage_h2d(pn->row_list.p, rows.data(), (size_t)n * 4, s));
-    DevBuf off, bends;
     CSRK_TRY(off.alloc((size_t)(pairs + 1) * 8));
     const unsigned g = (unsigned)xcd_block_chunk_grid(ceil_div(n, 256), nb);
     panel_count_kernel<P><<<g, 256, 0, s>>>(rp, m->d_colinds, pn->row_list.as<int32_t>(), n, nb, cb, off.as<int64_t>());
@@ -937,18 +987,12 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
                                                           cb, off.as<int64_t>(), pn->rp.as<int32_t>(),
                                                           pn->ci.as<int32_t>(), pn->vs.as<double>());
     CSRK_LAUNCH_CHECK();
-    // tiles per block (host: nb is at most a few thousand)
-    CSRK_TRY(bends.alloc((size_t)(nb + 1) * 8));
-    panel_blockends_kernel<<<(unsigned)ceil_div(nb + 1, 256), 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>());
-    CSRK_LAUNCH_CHECK();
-    std::vector<int64_t> be((size_t)nb + 1), t0((size_t)nb + 1);
-    CSRK_TRY(stage_d2h(be.data(), bends.p, (size_t)(nb + 1) * 8, s));
-    CSRK_HIP(hipStreamSynchronize(s));
-    t0[0] = 0;
-    for (int32_t b = 0; b < nb; b++) t0[b + 1] = t0[b] + ceil_div((int64_t)n + be[b + 1] - be[b], MERGE_ITEMS);
-    const int64_t n_tiles = t0[nb];
-    CSRK_TRY(stage_h2d(bends.p, t0.data(), (size_t)(nb + 1) * 8, s));
-    tr.lap("  tier 1: count, scan, fill");
+    return CSRK_OK;
+}
+
+// the tiles' coordinates (bends: tiles before each block), then every tile's entries into column order
+static int panel_tiles(Panel *pn, int32_t n, int32_t nb, int32_t cb, const DevBuf &bends, int64_t n_tiles, hipStream_t s)
+{
     CSRK_TRY(pn->tile.alloc((size_t)n_tiles * sizeof(PanelTile)));
     if (pn->p64)
         panel_plan_kernel<int64_t><<<(unsigned)ceil_div(n_tiles, 256), 256, 0, s>>>(
@@ -962,85 +1006,68 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
         panel_colsort_kernel<<<(unsigned)n_tiles, 256, 0, s>>>(pn->tile.as<PanelTile>(), cb, pn->ci.as<int32_t>(), pn->vs.as<double>());
         CSRK_LAUNCH_CHECK();
     }
-    tr.lap("  tier 1: tiles, column order");
+    return CSRK_OK;
+}
 
-    // workgroup list: `tpw` consecutive tiles of one block per workgroup
-    std::vector<PanelGroup> groups;
-    auto block_groups = [&](int32_t b, std::vector<PanelGroup> &out) {
-        for (int64_t t = t0[b]; t < t0[b + 1]; t += tpw) {
-            PanelGroup gq;
-            gq.t0 = t;
-            gq.nt = (int32_t)(t0[b + 1] - t < tpw ? t0[b + 1] - t : tpw);
-            gq.blk = b;
-            out.push_back(gq);
-        }
-    };
-    if (!xcd_streams || nb < 2 * HEAVY_STREAMS) {      // too few blocks to keep all 8 XCDs busy per stream
-        for (int32_t b = 0; b < nb; b++) block_groups(b, groups);
-    } else {
-        std::vector<PanelGroup> st[HEAVY_STREAMS];
-        size_t longest = 0;
-        for (int32_t b = 0; b < nb; b++) block_groups(b, st[b % HEAVY_STREAMS]);
-        for (int q = 0; q < HEAVY_STREAMS; q++) longest = st[q].size() > longest ? st[q].size() : longest;
-        PanelGroup pad;
-        pad.t0 = 0;
-        pad.nt = 0;
-        pad.blk = 0;
-        groups.reserve(longest * HEAVY_STREAMS);
-        for (size_t i = 0; i < longest; i++)
-            for (int q = 0; q < HEAVY_STREAMS; q++) groups.push_back(i < st[q].size() ? st[q][i] : pad);
+// The tiles' carries per long row (spmvlayout::panel_carries; Panel::ncs): the tiles come to the host, get their carry
+// slots and go back; the carries beyond the slots are listed in crp / cidx, which exist only then.
+static int panel_carry_slots(Panel *pn, int32_t n, int64_t pairs, int64_t n_tiles)
+{
+    std::vector<PanelTile> ht((size_t)n_tiles);
+    CSRK_TRY(stage_d2h(ht.data(), pn->tile.p, (size_t)n_tiles * sizeof(PanelTile), nullptr));
+    const spmvlayout::PanelCarries pc = spmvlayout::panel_carries(ht, n, pairs, PANEL_CARRY_ROWS);
+    pn->listed = pc.listed;
+    pn->ncs = pc.ncs;
+    CSRK_TRY(stage_h2d(pn->tile.p, ht.data(), (size_t)n_tiles * sizeof(PanelTile), nullptr));
+    if (pc.listed) {
+        CSRK_TRY(pn->crp.alloc(pc.crp.size() * 4));
+        CSRK_TRY(pn->cidx.alloc(pc.cidx.size() * 4));
+        CSRK_TRY(stage_h2d(pn->crp.p, pc.crp.data(), pc.crp.size() * 4, nullptr));
+        CSRK_TRY(stage_h2d(pn->cidx.p, pc.cidx.data(), pc.cidx.size() * 4, nullptr));
     }
-    // the tiles' carries per long row (a tile's carry belongs to the pair holding its last, unfinished row end: static): the
-    // first `ncs` of a row go to carry rows behind the block partials (Panel::ncs), the others are listed
-    int32_t ncs = 0;
-    {
-        std::vector<PanelTile> ht((size_t)n_tiles);
-        CSRK_TRY(stage_d2h(ht.data(), pn->tile.p, (size_t)n_tiles * sizeof(PanelTile), nullptr));
-        std::vector<int32_t> cnt((size_t)n, 0);
-        for (int64_t t = 0; t < n_tiles; t++)
-            if ((int64_t)ht[(size_t)t].i1 < pairs) {
-                const int32_t c = ++cnt[(size_t)(ht[(size_t)t].i1 % n)];
-                ncs = c > ncs ? c : ncs;
-            }
-        ncs = ncs < PANEL_CARRY_ROWS ? ncs : PANEL_CARRY_ROWS;
-        std::vector<int32_t> crp((size_t)n + 1, 0), cidx;
-        bool listed = false;
-        for (int32_t h = 0; h < n; h++) {
-            crp[(size_t)h + 1] = crp[(size_t)h] + (cnt[(size_t)h] > ncs ? cnt[(size_t)h] - ncs : 0);
-            listed = listed || cnt[(size_t)h] > ncs;
-        }
-        cidx.resize((size_t)crp[(size_t)n] + 1);
-        pn->listed = crp[(size_t)n];
-        std::vector<int32_t> seen((size_t)n, 0);
-        for (int64_t t = 0; t < n_tiles; t++) {      // ascending tiles: each row's carries come out in tile order
-            PanelTile &T = ht[(size_t)t];
-            T.cslot = -1;
-            if ((int64_t)T.i1 >= pairs) continue;
-            const int32_t h = (int32_t)(T.i1 % n), j = seen[(size_t)h]++;
-            if (j < ncs) T.cslot = pairs + (int64_t)j * n + h;
-            else cidx[(size_t)(crp[(size_t)h] + j - ncs)] = (int32_t)t;
-        }
-        CSRK_TRY(stage_h2d(pn->tile.p, ht.data(), (size_t)n_tiles * sizeof(PanelTile), nullptr));
-        if (listed) {
-            CSRK_TRY(pn->crp.alloc(crp.size() * 4));
-            CSRK_TRY(pn->cidx.alloc(cidx.size() * 4));
-            CSRK_TRY(stage_h2d(pn->crp.p, crp.data(), crp.size() * 4, nullptr));
-            CSRK_TRY(stage_h2d(pn->cidx.p, cidx.data(), cidx.size() * 4, nullptr));
-        }
-    }
+    return CSRK_OK;
+}
+
+// what a product writes: the workgroup list, the tiles' carries, the partials with their pn->ncs carry rows
+static int panel_outputs(Panel *pn, const std::vector<PanelGroup> &groups, int32_t n, int64_t pairs, int64_t n_tiles, hipStream_t s)
+{
     pn->groups = (int64_t)groups.size();
-    pn->pad_groups = 0;
-    for (const PanelGroup &gq : groups) pn->pad_groups += gq.nt == 0;
     CSRK_TRY(pn->group.alloc(groups.size() * sizeof(PanelGroup)));
     CSRK_TRY(stage_h2d(pn->group.p, groups.data(), groups.size() * sizeof(PanelGroup), s));
     CSRK_TRY(pn->carry_row.alloc((size_t)n_tiles * 4));
     CSRK_TRY(pn->carry_val.alloc((size_t)n_tiles * 8));
-    CSRK_TRY(pn->y.alloc((size_t)(pairs + (int64_t)ncs * n) * 8));
-    if (ncs) {      // -0.0 where no tile writes (x + -0.0 = x for every x)
-        std::vector<double> neg0((size_t)ncs * n, -0.0);
+    CSRK_TRY(pn->y.alloc((size_t)(pairs + (int64_t)pn->ncs * n) * 8));
+    if (pn->ncs) {      // -0.0 where no tile writes (x + -0.0 = x for every x)
+        std::vector<double> neg0((size_t)pn->ncs * n, -0.0);
         CSRK_TRY(stage_h2d(pn->y.as<double>() + pairs, neg0.data(), neg0.size() * 8, s));
     }
-    pn->ncs = ncs;
+    return CSRK_OK;
+}
+
+// Build one panel tier: M' (column-block-major copy of the listed rows, float64 values), its tiles and
+// the workgroup list.  `xcd_streams`: order the groups so that column block b is served by workgroups
+// with blockIdx % 8 == b % 8.
+template <class P, int VT>
+static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, int64_t nnz_rows, int32_t cb, int tpw,
+                       bool xcd_streams, const SpmvKnobs &knobs, hipStream_t s)
+{
+    PlanTrace tr(knobs);
+    const int32_t n = (int32_t)rows.size();
+    const int32_t nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, cb);
+    const int64_t pairs = (int64_t)n * nb;
+    CSRK_TRY(pn->row_list.alloc((size_t)n * 4));
+    CSRK_TRY(stage_h2d(pn->row_list.p, rows.data(), (size_t)n * 4, s));
+    DevBuf off, bends;
+    CSRK_TRY((panel_matrix<P, VT>(m, pn, n, nb, cb, nnz_rows, off, s)));
+    std::vector<int64_t> t0;      // tiles before each block: a block's merge path is its entries and n row ends
+    CSRK_TRY(block_tile_starts(off, n, nb, MERGE_ITEMS, n, bends, t0, s));
+    const int64_t n_tiles = t0[(size_t)nb];
+    tr.lap("  tier 1: count, scan, fill");
+    CSRK_TRY(panel_tiles(pn, n, nb, cb, bends, n_tiles, s));
+    tr.lap("  tier 1: tiles, column order");
+    const std::vector<PanelGroup> groups = spmvlayout::panel_groups(t0.data(), nb, tpw, xcd_streams, HEAVY_STREAMS, &pn->pad_groups);
+    CSRK_TRY(panel_carry_slots(pn, n, pairs, n_tiles));
+    CSRK_TRY(panel_outputs(pn, groups, n, pairs, n_tiles, s));
     CSRK_HIP(hipStreamSynchronize(s));     // `groups`, `t0` are host temporaries of async copies
     tr.lap("  tier 1: groups, carries (host)");
     pn->on = true;
@@ -1053,137 +1080,134 @@ static int build_panel(Matrix *m, Panel *pn, const std::vector<int32_t> &rows, i
     return CSRK_OK;
 }
 
-// Build one accumulator-form group: the listed heavy rows (<= ACC_MAXROWS, ascending) as a tiled,
-// column-block-major (value, packed index) stream plus the persistent workgroups' segment lists.
-// wg_want: the group's workgroups when it shares its launch with other groups (0: one per CU); form: what packable float64
-// values are stored as -- ACC_FORM_RAW: the raw stream whatever the values (another group of the launch could not be packed),
-// ACC_FORM_FIX56: 9-byte entries, ACC_FORM_NIB: 8.5-byte entries (the launch's choice: accgroups::choose_nib).
+// ---- tier 0 (accumulator form): build_acc_panel and its steps -------------------------------------
+// form: what packable float64 values are stored as -- ACC_FORM_RAW: the raw stream whatever the values (another group of the
+// launch could not be packed), ACC_FORM_FIX56: 9-byte entries, ACC_FORM_NIB: 8.5-byte entries (the launch's choice:
+// accgroups::choose_nib).
 enum { ACC_FORM_RAW = 0, ACC_FORM_FIX56 = 1, ACC_FORM_NIB = 2 };
-template <class P, int VT>
-static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const int64_t *lens, int32_t n, int64_t nnz_rows,
-                           hipStream_t s, int32_t wg_want = 0, int form = ACC_FORM_FIX56)
-{
-    ap->fix56 = false;
-    ap->nib = false;
-    ap->fx_g = 0;
-    const P *rp = (const P *)m->d_rowptrs;
-    const int32_t nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB);
-    PlanTrace tr;
-    const int64_t pairs = (int64_t)n * nb;
-    CSRK_TRY(ap->row_list.alloc((size_t)n * 4));
-    CSRK_TRY(stage_h2d(ap->row_list.p, rows, (size_t)n * 4, s));
-    DevBuf off, bends, pstart, d_trow, d_tpiece;
-    CSRK_TRY(off.alloc((size_t)(pairs + 1) * 8));
-    // block starts inside every row (one pass over the rows' entries), then the pair counts
-    std::vector<int32_t> trow, tpiece;
-    for (int32_t c = 0; c < n; c++)
-        for (int64_t pc = 0; pc * ACC_PIECE < lens[c]; pc++) {
-            trow.push_back(c);
-            tpiece.push_back((int32_t)pc);
-        }
-    const int64_t n_tasks = (int64_t)trow.size();
-    CSRK_TRY(pstart.alloc((size_t)(pairs + n) * 4));
-    CSRK_TRY(d_trow.alloc((size_t)(n_tasks ? n_tasks : 1) * 4));
-    CSRK_TRY(d_tpiece.alloc((size_t)(n_tasks ? n_tasks : 1) * 4));
-    CSRK_TRY(stage_h2d(d_trow.p, trow.data(), (size_t)n_tasks * 4, s));
-    CSRK_TRY(stage_h2d(d_tpiece.p, tpiece.data(), (size_t)n_tasks * 4, s));
-    acc_pairstart_kernel<P><<<(unsigned)(ceil_div(ceil_div(n_tasks * WAVE, 256), 8) * 8), 256, 0, s>>>(
-        rp, m->d_colinds, ap->row_list.as<int32_t>(), n, nb, ACC_CB, d_trow.as<int32_t>(), d_tpiece.as<int32_t>(), n_tasks,
-        pstart.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    tr.lap("  tier 0: pair starts");
-    acc_paircount_kernel<<<(unsigned)ceil_div(pairs, 256), 256, 0, s>>>(pstart.as<int32_t>(), pairs, n, off.as<int64_t>());
-    CSRK_LAUNCH_CHECK();
-    DevBuf gap;
-    CSRK_TRY(gap.alloc((size_t)pairs * 4));
-    acc_gap_kernel<<<(unsigned)ceil_div((int64_t)nb * WAVE, 256), 256, 0, s>>>(off.as<int64_t>(), n, nb, gap.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    CSRK_TRY(exclusive_scan_i64(off.as<int64_t>(), off.as<int64_t>(), pairs, s));
-    CSRK_TRY(bends.alloc((size_t)(nb + 1) * 8));
-    panel_blockends_kernel<<<(unsigned)ceil_div(nb + 1, 256), 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>());
-    CSRK_LAUNCH_CHECK();
-    std::vector<int64_t> be((size_t)nb + 1), t0((size_t)nb + 1);
-    CSRK_TRY(stage_d2h(be.data(), bends.p, (size_t)(nb + 1) * 8, s));
-    CSRK_HIP(hipStreamSynchronize(s));
-    t0[0] = 0;
-    for (int32_t b = 0; b < nb; b++) t0[b + 1] = t0[b] + ceil_div(be[b + 1] - be[b], ACC_TILE);
-    const int64_t n_tiles = t0[nb];
-    CSRK_TRY(stage_h2d(bends.p, t0.data(), (size_t)(nb + 1) * 8, s));
-    tr.lap("  tier 0: counts, gaps, scan");
-    // persistent workgroups: one per CU, equal shares of the tiles (stored interleaved: acc_phys_tile), cut into one-block
-    // segments
-    int cus = 0;
-    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    int64_t n_wg = wg_want > 0 ? wg_want : cus > 0 ? cus : 256;
-    if (n_wg > n_tiles) n_wg = n_tiles;
-    if (n_wg < 1) n_wg = 1;
-    std::vector<int64_t> wg_t0((size_t)n_wg + 1);
-    int64_t share_max = 0;
-    for (int64_t w = 0; w <= n_wg; w++) wg_t0[(size_t)w] = n_tiles * w / n_wg;
-    for (int64_t w = 0; w < n_wg; w++) share_max = std::max(share_max, wg_t0[(size_t)w + 1] - wg_t0[(size_t)w]);
-    const int64_t n_phys = share_max * n_wg;      // stored tiles (the last sweep has holes where a share is one tile shorter)
-    DevBuf d_wg_t0;
-    CSRK_TRY(d_wg_t0.alloc((size_t)(n_wg + 1) * 8));
-    CSRK_TRY(stage_h2d(d_wg_t0.p, wg_t0.data(), (size_t)(n_wg + 1) * 8, s));
-    // a float32 matrix keeps float32 values in the stream (6 B per entry; widened in the kernel, exactly)
-    ap->f32 = VT == CSRK_VAL_F32;
-    // float64 values that lie on one binary grid are kept in 7 bytes (fix56.h: 9 B per entry; decoded exactly).  One switch for
-    // the whole group: the grid test over its values, and CSRK_SPMV_FIX56=0 forbids the form (tests, measurements)
+
+// One group's plan-time temporaries, in the order they are released in reverse, and what its steps share.
+struct AccBuild {
+    DevBuf off, bends, pstart, d_trow, d_tpiece, gap, d_wg_t0;
     DevBuf fx;      // int32[4]: the grid test's bad flag, lowest and highest set bit; the verification's mismatch flag
-    CSRK_TRY(fx.alloc(16));
-    if (VT == CSRK_VAL_F64 && n > 0 && form != ACC_FORM_RAW) {
-        const char *env = getenv("CSRK_SPMV_FIX56");
-        if (!(env && env[0] == '0')) {
-            int32_t h[4] = {0, INT32_MAX, INT32_MIN, 0};
-            CSRK_TRY(stage_h2d(fx.p, h, sizeof h, s));
-            acc_range_kernel<P><<<dim3((unsigned)n, 16), 256, 0, s>>>(rp, (const double *)m->d_values, ap->row_list.as<int32_t>(),
-                                                                     fx.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            CSRK_TRY(stage_d2h(h, fx.p, sizeof h, s));
-            CSRK_HIP(hipStreamSynchronize(s));
-            fix56::Range r;
-            r.bad = h[0];
-            r.lo = h[1];
-            r.hi = h[2];
-            ap->fix56 = fix56::packable(r, ap->fx_g);
-            ap->nib = ap->fix56 && form == ACC_FORM_NIB;
-            tr.lap("  tier 0: value grid test");
-        }
-    }
-    CSRK_TRY(ap->idx.alloc((size_t)n_phys * ACC_TILE * 2));
-    CSRK_TRY(ap->tile_row0.alloc((size_t)(n_tiles ? n_tiles : 1) * 4));
+    int32_t n = 0, nb = 0;
+    int64_t pairs = 0, n_tiles = 0;
+    std::vector<int64_t> t0;      // tiles before each column block
+    spmvlayout::WgShares sh;
+};
+
+// block starts inside every row (one pass over the rows' entries, a task per ACC_PIECE entries of a row)
+template <class P>
+static int acc_pair_starts(Matrix *m, AccPanel *ap, const int64_t *lens, AccBuild &B, hipStream_t s)
+{
+    CSRK_TRY(B.off.alloc((size_t)(B.pairs + 1) * 8));
+    std::vector<int32_t> trow, tpiece;
+    spmvlayout::acc_tasks(lens, B.n, ACC_PIECE, trow, tpiece);
+    const int64_t n_tasks = (int64_t)trow.size();
+    CSRK_TRY(B.pstart.alloc((size_t)(B.pairs + B.n) * 4));
+    CSRK_TRY(B.d_trow.alloc((size_t)(n_tasks ? n_tasks : 1) * 4));
+    CSRK_TRY(B.d_tpiece.alloc((size_t)(n_tasks ? n_tasks : 1) * 4));
+    CSRK_TRY(stage_h2d(B.d_trow.p, trow.data(), (size_t)n_tasks * 4, s));
+    CSRK_TRY(stage_h2d(B.d_tpiece.p, tpiece.data(), (size_t)n_tasks * 4, s));
+    acc_pairstart_kernel<P><<<(unsigned)(ceil_div(ceil_div(n_tasks * WAVE, 256), 8) * 8), 256, 0, s>>>(
+        (const P *)m->d_rowptrs, m->d_colinds, ap->row_list.as<int32_t>(), B.n, B.nb, ACC_CB, B.d_trow.as<int32_t>(),
+        B.d_tpiece.as<int32_t>(), n_tasks, B.pstart.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the pair counts, the padding gaps between the pairs of a block, the counts' scan, and the tiles before each block
+static int acc_pair_counts(AccBuild &B, hipStream_t s)
+{
+    acc_paircount_kernel<<<(unsigned)ceil_div(B.pairs, 256), 256, 0, s>>>(B.pstart.as<int32_t>(), B.pairs, B.n, B.off.as<int64_t>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(B.gap.alloc((size_t)B.pairs * 4));
+    acc_gap_kernel<<<(unsigned)ceil_div((int64_t)B.nb * WAVE, 256), 256, 0, s>>>(B.off.as<int64_t>(), B.n, B.nb, B.gap.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(exclusive_scan_i64(B.off.as<int64_t>(), B.off.as<int64_t>(), B.pairs, s));
+    CSRK_TRY(block_tile_starts(B.off, B.n, B.nb, ACC_TILE, 0, B.bends, B.t0, s));
+    B.n_tiles = B.t0[(size_t)B.nb];
+    return CSRK_OK;
+}
+
+// persistent workgroups: one per CU (or wg_want), equal shares of the tiles (stored interleaved: acc_phys_tile)
+static int acc_shares(Matrix *m, int32_t wg_want, AccBuild &B, hipStream_t s)
+{
+    int cus = 0;
+    CSRK_TRY(device_cus(m, &cus));
+    B.sh = spmvlayout::wg_shares(B.n_tiles, wg_want, cus);
+    CSRK_TRY(B.d_wg_t0.alloc((size_t)(B.sh.n_wg + 1) * 8));
+    CSRK_TRY(stage_h2d(B.d_wg_t0.p, B.sh.wg_t0.data(), (size_t)(B.sh.n_wg + 1) * 8, s));
+    return CSRK_OK;
+}
+
+// float64 values that lie on one binary grid are kept in 7 bytes (fix56.h: 9 B per entry; decoded exactly).  One switch for
+// the whole group: the grid test over its values, and CSRK_SPMV_FIX56=0 forbids the form (tests, measurements)
+template <class P, int VT>
+static int acc_value_form(Matrix *m, AccPanel *ap, int form, const SpmvKnobs &knobs, AccBuild &B, PlanTrace &tr, hipStream_t s)
+{
+    CSRK_TRY(B.fx.alloc(16));
+    if (!(VT == CSRK_VAL_F64 && B.n > 0 && form != ACC_FORM_RAW) || knobs.fix56_off) return CSRK_OK;
+    int32_t h[4] = {0, INT32_MAX, INT32_MIN, 0};
+    CSRK_TRY(stage_h2d(B.fx.p, h, sizeof h, s));
+    acc_range_kernel<P><<<dim3((unsigned)B.n, 16), 256, 0, s>>>((const P *)m->d_rowptrs, (const double *)m->d_values,
+                                                               ap->row_list.as<int32_t>(), B.fx.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(stage_d2h(h, B.fx.p, sizeof h, s));
+    CSRK_HIP(hipStreamSynchronize(s));
+    fix56::Range r;
+    r.bad = h[0];
+    r.lo = h[1];
+    r.hi = h[2];
+    ap->fix56 = fix56::packable(r, ap->fx_g);
+    ap->nib = ap->fix56 && form == ACC_FORM_NIB;
+    tr.lap("  tier 0: value grid test");
+    return CSRK_OK;
+}
+
+// the group's entries into tiles of SV values and 16-bit index words, then the padding of every block's last tile;
+// VERIFY: nothing is written, every stored entry is decoded as the product decodes it and compared with the source (fx[3])
+template <class P, int VT, class SV, bool VERIFY>
+static int acc_fill(Matrix *m, AccPanel *ap, AccBuild &B, hipStream_t s)
+{
+    const int32_t n = B.n, nb = B.nb, n_wg = (int32_t)B.sh.n_wg;
     const int32_t fill_waves = (int32_t)ceil_div(n, WAVE);      // wavefronts per block: 64 pairs each
-#define ACC_FILL(SV, VERIFY)                                                                                           \
-    do {                                                                                                               \
-        acc_fill_kernel<P, VT, SV, VERIFY><<<(unsigned)ceil_div((int64_t)nb * fill_waves * WAVE, 256), 256, 0, s>>>(   \
-            rp, m->d_colinds, m->d_values, ap->row_list.as<int32_t>(), n, nb, ACC_CB, off.as<int64_t>(),               \
-            bends.as<int64_t>(), pstart.as<int32_t>(), gap.as<int32_t>(), ap->vals.as<SV>(), ap->idx.as<uint16_t>(),   \
-            ap->tile_row0.as<int32_t>(), d_wg_t0.as<int64_t>(), (int32_t)n_wg, fill_waves, ap->fx_g,                   \
-            fx.as<int32_t>() + 3);                                                                                     \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-        acc_pad_kernel<SV, VERIFY><<<(unsigned)nb, 256, 0, s>>>(off.as<int64_t>(), n, nb, bends.as<int64_t>(),         \
-                                                                ap->vals.as<SV>(), ap->idx.as<uint16_t>(),             \
-                                                                d_wg_t0.as<int64_t>(), (int32_t)n_wg, ap->fx_g,        \
-                                                                fx.as<int32_t>() + 3);                                 \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-    } while (0)
+    acc_fill_kernel<P, VT, SV, VERIFY><<<(unsigned)ceil_div((int64_t)nb * fill_waves * WAVE, 256), 256, 0, s>>>(
+        (const P *)m->d_rowptrs, m->d_colinds, m->d_values, ap->row_list.as<int32_t>(), n, nb, ACC_CB, B.off.as<int64_t>(),
+        B.bends.as<int64_t>(), B.pstart.as<int32_t>(), B.gap.as<int32_t>(), ap->vals.as<SV>(), ap->idx.as<uint16_t>(),
+        ap->tile_row0.as<int32_t>(), B.d_wg_t0.as<int64_t>(), n_wg, fill_waves, ap->fx_g, B.fx.as<int32_t>() + 3);
+    CSRK_LAUNCH_CHECK();
+    acc_pad_kernel<SV, VERIFY><<<(unsigned)nb, 256, 0, s>>>(B.off.as<int64_t>(), n, nb, B.bends.as<int64_t>(), ap->vals.as<SV>(),
+                                                            ap->idx.as<uint16_t>(), B.d_wg_t0.as<int64_t>(), n_wg, ap->fx_g,
+                                                            B.fx.as<int32_t>() + 3);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// The stream in the form acc_value_form chose.  A packed form is the library's own proof of "exact", on every plan: every
+// stored entry decoded as the product decodes it, against the source (the 8.5-byte form: its column and row step too); a
+// single mismatch and the group is filled raw.
+template <class P, int VT>
+static int acc_fill_stream(Matrix *m, AccPanel *ap, AccBuild &B, PlanTrace &tr, hipStream_t s)
+{
+    const int64_t n_phys = B.sh.n_phys;
+    CSRK_TRY(ap->idx.alloc((size_t)n_phys * ACC_TILE * 2));
+    CSRK_TRY(ap->tile_row0.alloc((size_t)(B.n_tiles ? B.n_tiles : 1) * 4));
     if (ap->fix56) {
-        // the library's own proof of "exact", on every plan: every stored entry decoded as the product decodes it, against
-        // the source (the 8.5-byte form: its column and row step too); a single mismatch and the group is rebuilt raw
         int32_t mismatch = 1;
         if (ap->nib) {
             CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::nib::TILE_BYTES));
             CSRK_HIP(hipMemsetAsync(ap->vals.p, 0, (size_t)n_phys * fix56::nib::TILE_BYTES, s));      // (the nibbles are or-ed in)
-            ACC_FILL(fix56::nib::Bytes, false);
+            CSRK_TRY((acc_fill<P, VT, fix56::nib::Bytes, false>(m, ap, B, s)));
             tr.lap("  tier 0: fill (nib)");
-            ACC_FILL(fix56::nib::Bytes, true);
+            CSRK_TRY((acc_fill<P, VT, fix56::nib::Bytes, true>(m, ap, B, s)));
         } else {
             CSRK_TRY(ap->vals.alloc((size_t)n_phys * fix56::TILE_BYTES));
-            ACC_FILL(fix56::Packed, false);
+            CSRK_TRY((acc_fill<P, VT, fix56::Packed, false>(m, ap, B, s)));
             tr.lap("  tier 0: fill (fix56)");
-            ACC_FILL(fix56::Packed, true);
+            CSRK_TRY((acc_fill<P, VT, fix56::Packed, true>(m, ap, B, s)));
         }
-        CSRK_TRY(stage_d2h(&mismatch, fx.as<int32_t>() + 3, 4, s));
+        CSRK_TRY(stage_d2h(&mismatch, B.fx.as<int32_t>() + 3, 4, s));
         CSRK_HIP(hipStreamSynchronize(s));
         tr.lap(ap->nib ? "  tier 0: verify (nib)" : "  tier 0: verify (fix56)");
         if (mismatch) {
@@ -1193,133 +1217,158 @@ static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const i
     }
     if (!ap->fix56) {
         CSRK_TRY(ap->vals.alloc((size_t)n_phys * ACC_TILE * (ap->f32 ? 4 : 8)));
-        if (ap->f32) ACC_FILL(float, false);
-        else ACC_FILL(double, false);
+        if (ap->f32) CSRK_TRY((acc_fill<P, VT, float, false>(m, ap, B, s)));
+        else CSRK_TRY((acc_fill<P, VT, double, false>(m, ap, B, s)));
         tr.lap("  tier 0: fill");
     }
-#undef ACC_FILL
+    return CSRK_OK;
+}
+
+// the workgroups' shares cut into one-block segments (spmvlayout::acc_segments), the partials, the kernel's LDS
+static int acc_segment_tables(AccPanel *ap, AccBuild &B, hipStream_t s)
+{
     std::vector<AccSeg> segs;
-    std::vector<int32_t> wg_seg((size_t)n_wg + 1);
-    int32_t b = 0;
-    for (int64_t w = 0; w < n_wg; w++) {
-        wg_seg[(size_t)w] = (int32_t)segs.size();
-        int64_t t = wg_t0[(size_t)w];
-        const int64_t t_end = wg_t0[(size_t)w + 1];
-        while (t < t_end) {
-            while (t0[b + 1] <= t) b++;
-            int64_t e = t_end < t0[b + 1] ? t_end : t0[b + 1];
-            if (e - t > ACC_SEG_TILES) e = t + ACC_SEG_TILES;
-            AccSeg sg;
-            sg.tile0 = t;
-            sg.ptile0 = (t - wg_t0[(size_t)w]) * n_wg + w;
-            sg.ntiles = (int32_t)(e - t);
-            sg.blk = b;
-            segs.push_back(sg);
-            t = e;
-        }
-    }
-    wg_seg[(size_t)n_wg] = (int32_t)segs.size();
+    std::vector<int32_t> wg_seg;
+    spmvlayout::acc_segments(B.sh.wg_t0, B.t0.data(), ACC_SEG_TILES, segs, wg_seg);
     CSRK_TRY(ap->segs.alloc(segs.size() * sizeof(AccSeg)));
     CSRK_TRY(ap->wg_seg.alloc(wg_seg.size() * 4));
     CSRK_TRY(stage_h2d(ap->segs.p, segs.data(), segs.size() * sizeof(AccSeg), s));
     CSRK_TRY(stage_h2d(ap->wg_seg.p, wg_seg.data(), wg_seg.size() * 4, s));
-    CSRK_TRY(ap->partial.alloc((size_t)n_wg * n * 8));
-    CSRK_TRY(ap->z.alloc((size_t)n * 8));
-    ap->lds = (size_t)(ACC_CB + 2) * 8 + (size_t)((n + 1) & ~1) * 8 + (size_t)ACC_SEG_TILES * 12;
+    CSRK_TRY(ap->partial.alloc((size_t)B.sh.n_wg * B.n * 8));
+    CSRK_TRY(ap->z.alloc((size_t)B.n * 8));
+    ap->lds = spmvlayout::acc_lds_bytes(ACC_CB, B.n, ACC_SEG_TILES);
     CSRK_TRY(spmv_kernel_attributes());
     CSRK_HIP(hipStreamSynchronize(s));     // `segs`, `wg_seg`, `t0` are host temporaries of async copies
-    ap->nrow = n;
-    ap->nb = nb;
-    ap->n_wg = (int32_t)n_wg;
-    ap->tiles = n_tiles;
-    ap->nnz = nnz_rows;
     ap->n_segs = (int64_t)segs.size();
+    return CSRK_OK;
+}
+
+// Build one accumulator-form group: the listed heavy rows (<= ACC_MAXROWS, ascending) as a tiled,
+// column-block-major (value, packed index) stream plus the persistent workgroups' segment lists.
+// wg_want: the group's workgroups when it shares its launch with other groups (0: one per CU); form: above.
+template <class P, int VT>
+static int build_acc_panel(Matrix *m, AccPanel *ap, const int32_t *rows, const int64_t *lens, int32_t n, int64_t nnz_rows,
+                           const SpmvKnobs &knobs, hipStream_t s, int32_t wg_want = 0, int form = ACC_FORM_FIX56)
+{
+    ap->fix56 = false;
+    ap->nib = false;
+    ap->fx_g = 0;
+    PlanTrace tr(knobs);
+    CSRK_TRY(ap->row_list.alloc((size_t)n * 4));
+    CSRK_TRY(stage_h2d(ap->row_list.p, rows, (size_t)n * 4, s));
+    AccBuild B;
+    B.n = n;
+    B.nb = (int32_t)ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB);
+    B.pairs = (int64_t)n * B.nb;
+    CSRK_TRY(acc_pair_starts<P>(m, ap, lens, B, s));
+    tr.lap("  tier 0: pair starts");
+    CSRK_TRY(acc_pair_counts(B, s));
+    tr.lap("  tier 0: counts, gaps, scan");
+    CSRK_TRY(acc_shares(m, wg_want, B, s));
+    // a float32 matrix keeps float32 values in the stream (6 B per entry; widened in the kernel, exactly)
+    ap->f32 = VT == CSRK_VAL_F32;
+    CSRK_TRY((acc_value_form<P, VT>(m, ap, form, knobs, B, tr, s)));
+    CSRK_TRY((acc_fill_stream<P, VT>(m, ap, B, tr, s)));
+    CSRK_TRY(acc_segment_tables(ap, B, s));
+    ap->nrow = n;
+    ap->nb = B.nb;
+    ap->n_wg = (int32_t)B.sh.n_wg;
+    ap->tiles = B.n_tiles;
+    ap->nnz = nnz_rows;
     if (tr.on)
         fprintf(stderr, "[csrk plan]   tier 0 group: rows %d entries %lld workgroups %lld tiles %lld, %.1f per segment%s\n", n,
-                (long long)nnz_rows, (long long)n_wg, (long long)n_tiles, segs.empty() ? 0.0 : (double)n_tiles / (double)segs.size(),
+                (long long)nnz_rows, (long long)B.sh.n_wg, (long long)B.n_tiles,
+                ap->n_segs ? (double)B.n_tiles / (double)ap->n_segs : 0.0,
                 ap->nib ? " (nib)" : ap->fix56 ? " (fix56)" : ap->f32 ? " (float32)" : " (raw)");
     tr.lap("  tier 0: segments");
     return CSRK_OK;
 }
 
-// CSRK_SPMV_NIB, read when a plan is built: 1 = packable groups take the 8.5-byte entries, 0 = never, unset (-1) = where
-// accgroups::choose_nib says they pay.  CSRK_SPMV_FIX56=0 forbids every packed form.
-static int acc_nib_knob()
-{
-    const char *env = getenv("CSRK_SPMV_NIB");
-    if (!env || !env[0]) return -1;
-    return env[0] == '0' ? 0 : 1;
-}
-
-// Tier 0's groups, read when a plan is built: CSRK_ACC_GROUPS = groups that share one launch of the accumulator kernel
-// (1 .. accgroups::MAX_GROUPS); CSRK_ACC_GROUP_ROWS = rows a group holds (<= ACC_MAXROWS; a test hook: small matrices
-// then fill several groups).
-static int acc_groups_knob()
-{
-    const char *e = getenv("CSRK_ACC_GROUPS");
-    const int g = e ? atoi(e) : ACC_GROUPS_DEFAULT;
-    return g < 1 ? 1 : g > accgroups::MAX_GROUPS ? accgroups::MAX_GROUPS : g;
-}
-static int32_t acc_group_rows_knob()
-{
-    const char *e = getenv("CSRK_ACC_GROUP_ROWS");
-    const int r = e ? atoi(e) : ACC_MAXROWS;
-    return r < 1 || r > ACC_MAXROWS ? ACC_MAXROWS : r;
-}
-
-// Cut the long rows out of the merge path and build their panel tiers.
-
+// ---- the long-row split: build_heavy_split and its steps ------------------------------------------
+// which rows are cut out (at least cut_min entries): flags, their scans -> the cut rows and their entries in all
 template <class P>
-static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_tier1 = true)
+static int split_flags(Matrix *m, int cut_min, DevBuf &flag, DevBuf &hlen, int32_t *n_cut, int64_t *nnz_cut, hipStream_t s)
 {
-    p->n_heavy = 0;
-    const char *env = getenv("CSRK_SPMV_HEAVY_SPLIT");
-    if (env && env[0] == '0') return CSRK_OK;
-    HEAVY_MIN = 2048;
-    TIERB_MIN = TIERB_MIN_DEFAULT;
-    // (test hooks, not tuning switches: a small matrix gets more "heavy" rows than one accumulator group holds, or no tier 1)
-    if (const char *e = getenv("CSRK_HEAVY_MIN")) HEAVY_MIN = atoi(e) > 64 ? atoi(e) : 64;
-    if (const char *e = getenv("CSRK_TIERB_MIN")) TIERB_MIN = atoi(e) >= 0 ? atoi(e) : 0;
-    const bool tier1 = allow_tier1 && TIERB_MIN > 0 && TIERB_MIN < HEAVY_MIN;
-    const int cut_min = tier1 ? TIERB_MIN : HEAVY_MIN;
-    if (m->nrows == 0 || m->nnz < cut_min) return CSRK_OK;
-    // The split pays for itself only when x does not fit in an XCD's 4 MiB L2: otherwise every gather
-    // is an L2 hit already and the panels only add (block, row) overhead (MovieLens-25M shape, x = 472 KB:
-    // 0.146 ms on the single merge path against 0.176-0.53 ms split; measured).  CSRK_SPMV_HEAVY_SPLIT=1 forces it.
-    if ((int64_t)m->ncols * 8 <= (4ll << 20) && !(env && env[0] == '1')) return CSRK_OK;
-    const P *rp = (const P *)m->d_rowptrs;
     const int32_t nr = m->nrows;
-    const unsigned g1 = (unsigned)ceil_div((int64_t)nr + 1, 256);
-    PlanTrace tr;
-    DevBuf flag, hlen, bad, clen;
     CSRK_TRY(flag.alloc((size_t)(nr + 2) * 4));
     CSRK_TRY(hlen.alloc((size_t)(nr + 2) * 8));
-    heavy_flag_kernel<P><<<g1, 256, 0, s>>>(rp, nr, flag.as<int32_t>(), hlen.as<int64_t>(), cut_min);
+    heavy_flag_kernel<P><<<(unsigned)ceil_div((int64_t)nr + 1, 256), 256, 0, s>>>((const P *)m->d_rowptrs, nr, flag.as<int32_t>(),
+                                                                                 hlen.as<int64_t>(), cut_min);
     CSRK_LAUNCH_CHECK();
     CSRK_TRY(exclusive_scan_i32(flag.as<int32_t>(), flag.as<int32_t>(), nr, s));      // -> cut-row index
     CSRK_TRY(exclusive_scan_i64(hlen.as<int64_t>(), hlen.as<int64_t>(), nr, s));      // -> cut entries before
-    int32_t n_cut = 0;
-    int64_t nnz_cut = 0;
-    CSRK_TRY(stage_d2h(&n_cut, flag.as<int32_t>() + nr, 4, s));
-    CSRK_TRY(stage_d2h(&nnz_cut, hlen.as<int64_t>() + nr, 8, s));
+    CSRK_TRY(stage_d2h(n_cut, flag.as<int32_t>() + nr, 4, s));
+    CSRK_TRY(stage_d2h(nnz_cut, hlen.as<int64_t>() + nr, 8, s));
     CSRK_HIP(hipStreamSynchronize(s));
-    tr.lap("  split: flags + scans");
-    if (n_cut == 0) return CSRK_OK;
+    return CSRK_OK;
+}
 
+// the light view (row pointers with the cut rows collapsed), the cut rows' tables, and whether their columns ascend
+template <class P>
+static int split_view(Matrix *m, SpmvPlan *p, int32_t n_cut, const DevBuf &flag, const DevBuf &hlen, DevBuf &bad, DevBuf &clen,
+                      hipStream_t s)
+{
+    const P *rp = (const P *)m->d_rowptrs;
+    const int32_t nr = m->nrows;
     CSRK_TRY(p->rp_light.alloc((size_t)(nr + 1) * sizeof(P)));
     CSRK_TRY(p->heavy_row.alloc((size_t)n_cut * 4));
     CSRK_TRY(p->cut_pos.alloc((size_t)n_cut * 8));
     CSRK_TRY(p->cut_cum.alloc((size_t)(n_cut + 1) * 8));
     CSRK_TRY(clen.alloc((size_t)n_cut * 8));
-    heavy_view_kernel<P><<<g1, 256, 0, s>>>(rp, nr, flag.as<int32_t>(), hlen.as<int64_t>(), p->rp_light.as<P>(),
-                                          p->heavy_row.as<int32_t>(), p->cut_pos.as<int64_t>(),
-                                          p->cut_cum.as<int64_t>(), clen.as<int64_t>(), n_cut);
+    heavy_view_kernel<P><<<(unsigned)ceil_div((int64_t)nr + 1, 256), 256, 0, s>>>(
+        rp, nr, flag.as<int32_t>(), hlen.as<int64_t>(), p->rp_light.as<P>(), p->heavy_row.as<int32_t>(), p->cut_pos.as<int64_t>(),
+        p->cut_cum.as<int64_t>(), clen.as<int64_t>(), n_cut);
     CSRK_LAUNCH_CHECK();
     CSRK_TRY(bad.alloc(4));
     CSRK_HIP(hipMemsetAsync(bad.p, 0, 4, s));
     heavy_sorted_kernel<P><<<(unsigned)n_cut, 1024, 0, s>>>(rp, m->d_colinds, p->heavy_row.as<int32_t>(), n_cut,
                                                          bad.as<int32_t>());
     CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// Tier 0's groups side by side in one launch: what CSRK_ACC_GROUPS says, else as many (ACC_GROUPS_DEFAULT at most) as keep
+// the segments long enough to pay (accgroups::choose_groups).  `extend`: tier 0 may be extended below heavy_min.
+static int split_acc_groups(Matrix *m, const SpmvKnobs &knobs, const std::vector<int64_t> &lens, bool extend, int cut_min,
+                            int heavy_min, int *groups)
+{
+    *groups = knobs.acc_groups;
+    if (knobs.acc_groups_set) return CSRK_OK;
+    int cus = 0;
+    CSRK_TRY(device_cus(m, &cus));
+    *groups = accgroups::choose_groups(lens.data(), (int32_t)lens.size(), ACC_GROUPS_DEFAULT, knobs.acc_group_rows,
+                                       extend ? (int64_t)std::max(ACC_FLOOR, cut_min) : (int64_t)heavy_min,
+                                       ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB), cus);
+    return CSRK_OK;
+}
+
+// Cut the long rows out of the merge path and list them for their tiers (build_tiers builds those).  The two thresholds
+// are locals, seeded from the knobs: tier 0's may be lowered for this matrix (spmvlayout::tier0_threshold), and what was
+// chosen goes to p->heavy_min / p->tier1_min.
+template <class P>
+static int build_heavy_split(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s, bool allow_tier1 = true)
+{
+    p->n_heavy = 0;
+    if (knobs.heavy_split == 0) return CSRK_OK;
+    // (CSRK_HEAVY_MIN, CSRK_TIERB_MIN: test hooks, not tuning switches: a small matrix gets more "heavy" rows than one
+    // accumulator group holds, or no tier 1)
+    int heavy_min = knobs.heavy_min;
+    const int tierb_min = knobs.tierb_min;
+    const bool tier1 = allow_tier1 && tierb_min > 0 && tierb_min < heavy_min;
+    const int cut_min = tier1 ? tierb_min : heavy_min;
+    if (m->nrows == 0 || m->nnz < cut_min) return CSRK_OK;
+    // The split pays for itself only when x does not fit in an XCD's 4 MiB L2: otherwise every gather
+    // is an L2 hit already and the panels only add (block, row) overhead (MovieLens-25M shape, x = 472 KB:
+    // 0.146 ms on the single merge path against 0.176-0.53 ms split; measured).  CSRK_SPMV_HEAVY_SPLIT=1 forces it.
+    if (spmvlayout::x_fits_l2(m->ncols) && knobs.heavy_split != 1) return CSRK_OK;
+    PlanTrace tr(knobs);
+    DevBuf flag, hlen, bad, clen;
+    int32_t n_cut = 0;
+    int64_t nnz_cut = 0;
+    CSRK_TRY(split_flags<P>(m, cut_min, flag, hlen, &n_cut, &nnz_cut, s));
+    tr.lap("  split: flags + scans");
+    if (n_cut == 0) return CSRK_OK;
+    CSRK_TRY(split_view<P>(m, p, n_cut, flag, hlen, bad, clen, s));
     tr.lap("  split: view + sorted kernels");
     int32_t is_bad = 0;
     std::vector<int32_t> rows((size_t)n_cut);
@@ -1332,77 +1381,24 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
     tr.lap("  split: copies to the host");
     if (is_bad) return CSRK_OK;      // unsorted columns in a long row: column blocking needs order
 
-    // tier 0: accumulator form (groups of <= ACC_MAXROWS rows).  The accumulator form costs 1.8 ps per entry against 4.8 for tier 1 (measured, headline matrix), and
-    // one group holds up to ACC_MAXROWS rows at no extra window traffic: when fewer rows than that reach
-    // HEAVY_MIN, tier 0 is extended downwards to the ACC_MAXROWS longest rows (not below ACC_FLOOR).
-    // With G groups side by side in one launch (build_acc_groups) the tier holds G times as many rows.  G is what
-    // CSRK_ACC_GROUPS says, else as many groups (ACC_GROUPS_DEFAULT at most) as keep the segments long enough to pay
-    // (accgroups::choose_groups).
-    p->acc_groups = acc_groups_knob();
-    if (!getenv("CSRK_ACC_GROUPS")) {
-        int cus = 0;
-        CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-        const bool extend = tier1 && !getenv("CSRK_HEAVY_MIN");
-        p->acc_groups = accgroups::choose_groups(lens.data(), n_cut, ACC_GROUPS_DEFAULT, acc_group_rows_knob(),
-                                                 extend ? (int64_t)std::max(ACC_FLOOR, cut_min) : (int64_t)HEAVY_MIN,
-                                                 ceil_div(m->ncols > 0 ? m->ncols : 1, ACC_CB), cus > 0 ? cus : 256);
-    }
-    const int64_t t0_cap = (int64_t)p->acc_groups * acc_group_rows_knob();
-    if (tier1 && !getenv("CSRK_HEAVY_MIN")) {
-        int64_t n_min = 0;
-        for (int32_t c = 0; c < n_cut; c++) n_min += lens[c] >= HEAVY_MIN;
-        if (n_min < t0_cap && n_cut > n_min) {
-            const size_t kth = (size_t)(n_cut < t0_cap ? n_cut : t0_cap) - 1;
-            // the kth longest row's length: a histogram of the lengths below 2^16 decides it (nth_element over 10^5 rows was
-            // 0.4 ms of the plan), unless the kth row is longer than that
-            int64_t thr = -1;
-            {
-                constexpr int64_t HB = 1 << 16;
-                std::vector<int32_t> hist((size_t)HB + 1, 0);
-                for (int32_t c = 0; c < n_cut; c++) hist[(size_t)(lens[c] < HB ? lens[c] : HB)]++;
-                int64_t seen = hist[(size_t)HB];
-                if (seen <= (int64_t)kth)
-                    for (int64_t v = HB - 1; v >= 0; v--) {
-                        seen += hist[(size_t)v];
-                        if (seen > (int64_t)kth) {
-                            thr = v;
-                            break;
-                        }
-                    }
-            }
-            if (thr < 0) {
-                std::vector<int64_t> sl(lens);
-                std::nth_element(sl.begin(), sl.begin() + kth, sl.end(), [](int64_t a, int64_t b) { return a > b; });
-                thr = sl[kth];
-            }
-            // rows tied with the kth must not push the group over its capacity
-            int64_t n_ge = 0;
-            for (int32_t c = 0; c < n_cut; c++) n_ge += lens[c] >= thr;
-            if (n_ge > t0_cap) thr++;
-            thr = thr < ACC_FLOOR ? ACC_FLOOR : thr;
-            if (thr < HEAVY_MIN) HEAVY_MIN = (int)thr;
-        }
-    }
-    p->heavy_min = HEAVY_MIN;
-    p->tier1_min = TIERB_MIN;
-    std::vector<int32_t> r0, r1;     // tier 0: >= HEAVY_MIN entries; tier 1: the rest of the cut rows
+    // tier 0: accumulator form (groups of <= ACC_MAXROWS rows).  The accumulator form costs 1.8 ps per entry against 4.8 for
+    // tier 1 (measured, headline matrix), and one group holds up to ACC_MAXROWS rows at no extra window traffic: when fewer
+    // rows than the tier holds reach heavy_min, tier 0 is extended downwards to its longest rows (not below ACC_FLOOR).
+    // With G groups side by side in one launch (build_acc_groups) the tier holds G times as many rows.  Setting
+    // CSRK_HEAVY_MIN at all turns the extension off.
+    const bool extend = tier1 && !knobs.heavy_min_set;
+    CSRK_TRY(split_acc_groups(m, knobs, lens, extend, cut_min, heavy_min, &p->acc_groups));
+    const int64_t t0_cap = (int64_t)p->acc_groups * knobs.acc_group_rows;
+    if (extend) heavy_min = spmvlayout::tier0_threshold(lens.data(), n_cut, t0_cap, heavy_min, ACC_FLOOR);
+    p->heavy_min = heavy_min;
+    p->tier1_min = tierb_min;
+    std::vector<int32_t> r0, r1;     // tier 0: >= heavy_min entries; tier 1: the rest of the cut rows
     std::vector<int64_t> len0;
     int64_t nnz1 = 0;
-    r0.reserve((size_t)n_cut);
-    r1.reserve((size_t)n_cut);
-    len0.reserve((size_t)n_cut);
-    for (int32_t c = 0; c < n_cut; c++) {
-        if (lens[c] >= HEAVY_MIN) {
-            r0.push_back(rows[c]);
-            len0.push_back(lens[c]);
-        } else {
-            r1.push_back(rows[c]);
-            nnz1 += lens[c];
-        }
-    }
-    const int64_t pair_cap = 256ll << 20;
-    const int64_t pairs1 = (int64_t)r1.size() * ceil_div(m->ncols > 0 ? m->ncols : 1, PANEL_CB1);
-    if (pairs1 > pair_cap && tier1) return build_heavy_split<P>(m, p, s, false);
+    spmvlayout::split_rows(rows.data(), lens.data(), n_cut, heavy_min, r0, len0, r1, &nnz1);
+    // Too many (block, row) pairs for tier 1: once more without it.  The second pass re-reads nothing -- the same knobs,
+    // its own thresholds seeded from them -- and runs the same launches again with heavy_min as the only cut.
+    if (tier1 && !spmvlayout::tier1_pairs_fit((int64_t)r1.size(), m->ncols, PANEL_CB1)) return build_heavy_split<P>(m, p, knobs, s, false);
 
     p->n_heavy = n_cut;
     p->nnz_light = m->nnz - nnz_cut;
@@ -1418,15 +1414,14 @@ static int build_heavy_split(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_t
 // them, hold values of one form, and their workgroups are placed so that those of one column range share an XCD
 // (accgroups::place_wgs).  One group in a launch is built as it always was: a workgroup per CU, no map.
 template <class P, int VT>
-static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
+static int build_acc_groups(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s)
 {
     const std::vector<int32_t> &r0 = p->t0_rows;
     const std::vector<int64_t> &len0 = p->t0_lens;
     if (r0.empty()) return CSRK_OK;
-    const accgroups::Deal deal = accgroups::deal_rows(len0.data(), (int32_t)r0.size(), p->acc_groups, acc_group_rows_knob());
+    const accgroups::Deal deal = accgroups::deal_rows(len0.data(), (int32_t)r0.size(), p->acc_groups, knobs.acc_group_rows);
     int cus = 0;
-    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    if (cus <= 0) cus = 256;
+    CSRK_TRY(device_cus(m, &cus));
     std::vector<int32_t> rows;
     std::vector<int64_t> lens;
     for (size_t j = 0; j + 1 < deal.first.size(); j++) {
@@ -1436,7 +1431,7 @@ static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
         int64_t launch_entries = 0;
         for (int g = 0; g < gb; g++)
             for (int32_t pos : deal.groups[(size_t)(k0 + g)]) launch_entries += len0[(size_t)pos];
-        const int packed = accgroups::choose_nib(acc_nib_knob(), launch_entries, cus) ? ACC_FORM_NIB : ACC_FORM_FIX56;
+        const int packed = accgroups::choose_nib(knobs.nib, launch_entries, cus) ? ACC_FORM_NIB : ACC_FORM_FIX56;
         auto build = [&](int g, int form) -> int {
             const std::vector<int32_t> &pos = deal.groups[(size_t)(k0 + g)];
             rows.resize(pos.size());
@@ -1447,7 +1442,7 @@ static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
                 lens[i] = len0[(size_t)pos[i]];
                 gn += lens[i];
             }
-            return build_acc_panel<P, VT>(m, p->acc[a0 + (size_t)g], rows.data(), lens.data(), (int32_t)pos.size(), gn, s,
+            return build_acc_panel<P, VT>(m, p->acc[a0 + (size_t)g], rows.data(), lens.data(), (int32_t)pos.size(), gn, knobs, s,
                                           gb > 1 ? accgroups::group_wgs(cus, gb, g) : 0, form);
         };
         bool any_raw = false;
@@ -1478,51 +1473,25 @@ static int build_acc_groups(Matrix *m, SpmvPlan *p, hipStream_t s)
     return CSRK_OK;
 }
 
-// Build the tiers of the rows build_heavy_split cut out.
+// Build the tiers of the rows build_heavy_split cut out: tier 0's groups, then tier 1's panel.
 template <class P>
-static int build_tiers(Matrix *m, SpmvPlan *p, hipStream_t s)
+static int build_tiers(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s)
 {
     if (!p->n_heavy) return CSRK_OK;
-    const std::vector<int32_t> &r1 = p->t1_rows;
-    const int64_t nnz1 = p->t1_nnz;
-#define BUILD(VT)                                                                                                  \
-    do {                                                                                                           \
-        CSRK_TRY((build_acc_groups<P, VT>(m, p, s)));                                                              \
-        if (!r1.empty()) CSRK_TRY((build_panel<P, VT>(m, &p->tier1, r1, nnz1, PANEL_CB1, 1, true, s)));            \
-    } while (0)
-    if (m->val_type == CSRK_VAL_F64) BUILD(CSRK_VAL_F64);
-    else if (m->val_type == CSRK_VAL_F32) BUILD(CSRK_VAL_F32);
-    else BUILD(CSRK_VAL_NONE);
-#undef BUILD
-    return CSRK_OK;
+    return with_val_type(m->val_type, [&](auto vt) -> int {
+        constexpr int VT = decltype(vt)::value;
+        CSRK_TRY((build_acc_groups<P, VT>(m, p, knobs, s)));
+        if (!p->t1_rows.empty()) CSRK_TRY((build_panel<P, VT>(m, &p->tier1, p->t1_rows, p->t1_nnz, PANEL_CB1, 1, true, knobs, s)));
+        return CSRK_OK;
+    });
 }
 
-// Pick the (at most HOT_SLOTS) most referenced columns and renumber them in a copy of colinds.  Built
-// with the lazy plan (second launch on a handle).  Skipped when x is small enough to live in L1/L2
-// next to the streams anyway, when the matrix is small, or when the cached columns would carry less
-// than a fifth of the entries (no popularity skew: nothing to gain, and the persistent grid has fewer
-// wavefronts in flight than the plain one).  CSRK_SPMV_HOT=0 disables, =1 forces.
+// ---- the hot-column pack: build_hot_cache and its steps -------------------------------------------
+// sampled reference counts per column (hot_count_kernel); *n_samples = entries counted
 template <class P>
-static int build_hot_cache(Matrix *m, SpmvPlan *p, hipStream_t s)
+static int hot_counts(Matrix *m, SpmvPlan *p, DevBuf &cnt, DevBuf &census, int64_t *n_samples, hipStream_t s)
 {
-    p->n_hot = 0;
-    const char *env = getenv("CSRK_SPMV_HOT");
-    if (env && env[0] == '0') return CSRK_OK;
-    const bool force = env && env[0] == '1';
-    if (m->nnz < 2 || m->ncols < 1) return CSRK_OK;
-    PlanTrace tr;
-    int64_t HOT_SLOTS = HOT_SLOTS_MAX;   // 4 MiB of packed x, most popular first (light stream, LDS for the first 8192: 64k 0.340,
-                                  // 256k 0.308, 512k 0.302, 1M 0.297, 2M 0.297 ms, but the per-call pack costs more than that gains past 512k)
-                                  // earlier sweep, tile kernel, 512 KiB of packed x (measured on the headline matrix: 16k 0.431, 64k 0.422,
-                                  // 256k 0.430, 1M 0.439, 4M 0.460 ms for the tile kernel; none 0.481)
-    p->hot_slots = (int32_t)HOT_SLOTS;
-    // x that fits in L2 whole needs no packing
-    if (!force && (m->nnz < (1 << 20) || (int64_t)m->ncols * 8 <= (4ll << 20))) return CSRK_OK;
     const int32_t nc = m->ncols;
-    DevBuf cnt, slot, census;
-    CSRK_TRY(cnt.alloc((size_t)(nc + 1) * 4));
-    CSRK_TRY(slot.alloc((size_t)(nc + 2) * 4));
-    CSRK_TRY(census.alloc(16));
     CSRK_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(nc + 1) * 4, s));
     CSRK_HIP(hipMemsetAsync(census.p, 0, 16, s));
     const int64_t row_stride = p->nnz_light > (1ll << 25) ? p->nnz_light >> 25 : 1;
@@ -1534,22 +1503,29 @@ static int build_hot_cache(Matrix *m, SpmvPlan *p, hipStream_t s)
     unsigned long long n_samples_u = 0;
     CSRK_TRY(stage_d2h(&n_samples_u, census.p, 8, s));
     CSRK_HIP(hipStreamSynchronize(s));
-    const int64_t n_samples = (int64_t)n_samples_u;
-    tr.lap("  hot: column counts");
-    if (n_samples == 0) return CSRK_OK;
-    // smallest threshold (>= 2 references in the sample) that leaves at most HOT_SLOTS columns
-    auto census_at = [&](int32_t thr, unsigned long long out[2]) -> int {
-        CSRK_HIP(hipMemsetAsync(census.p, 0, 16, s));
-        hot_census_kernel<<<1024, 256, 0, s>>>(cnt.as<int32_t>(), nc, thr, census.as<unsigned long long>());
-        CSRK_LAUNCH_CHECK();
-        CSRK_TRY(stage_d2h(out, census.p, 16, s));
-        CSRK_HIP(hipStreamSynchronize(s));
-        return CSRK_OK;
-    };
-    unsigned long long c[2];
-    int64_t lo = 2, hi = n_samples + 1;     // invariant: census(hi).n <= HOT_SLOTS
-    // one histogram pass decides it unless more than HOT_SLOTS columns sit in the shared top bin (then: the search below)
-    bool decided = false;
+    *n_samples = (int64_t)n_samples_u;
+    return CSRK_OK;
+}
+
+// out[0] = columns with count >= thr, out[1] = the sum of their counts: one launch and one round trip
+static int hot_census_at(const DevBuf &cnt, DevBuf &census, int32_t nc, int32_t thr, unsigned long long out[2], hipStream_t s)
+{
+    CSRK_HIP(hipMemsetAsync(census.p, 0, 16, s));
+    hot_census_kernel<<<1024, 256, 0, s>>>(cnt.as<int32_t>(), nc, thr, census.as<unsigned long long>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(stage_d2h(out, census.p, 16, s));
+    CSRK_HIP(hipStreamSynchronize(s));
+    return CSRK_OK;
+}
+
+// The smallest threshold (>= 2 references in the sample) that leaves at most `slots` columns; c[0] = those columns, c[1]
+// = their references.  One histogram pass decides it (spmvlayout::hot_threshold_from_hist) unless more than `slots` columns
+// sit in the histogram's shared top bin: then a binary search, a census launch per probe.
+static int hot_threshold(const DevBuf &cnt, DevBuf &census, int32_t nc, int64_t n_samples, int64_t slots, int32_t *thr,
+                         unsigned long long c[2], hipStream_t s)
+{
+    int64_t lo = 2, hi = n_samples + 1;     // invariant: census(hi).n <= slots
+    spmvlayout::HotThreshold ht;
     {
         DevBuf hist;
         CSRK_TRY(hist.alloc((size_t)2 * (HOT_HIST + 1) * 8));
@@ -1560,76 +1536,107 @@ static int build_hot_cache(Matrix *m, SpmvPlan *p, hipStream_t s)
         std::vector<unsigned long long> hh((size_t)2 * (HOT_HIST + 1));
         CSRK_TRY(stage_d2h(hh.data(), hist.p, hh.size() * 8, s));
         CSRK_HIP(hipStreamSynchronize(s));
-        const unsigned long long *hn = hh.data(), *hs = hh.data() + (HOT_HIST + 1);
-        if (hn[HOT_HIST] <= (unsigned long long)HOT_SLOTS) {
-            unsigned long long n_ge = 0, s_ge = 0;      // columns / references with count >= v
-            int64_t thr0 = HOT_HIST;                     // smallest threshold >= 2 that leaves at most HOT_SLOTS columns
-            n_ge = hn[HOT_HIST];
-            s_ge = hs[HOT_HIST];
-            for (int64_t v = HOT_HIST - 1; v >= 2; v--) {
-                if (n_ge + hn[v] > (unsigned long long)HOT_SLOTS) break;
-                n_ge += hn[v];
-                s_ge += hs[v];
-                thr0 = v;
+        ht = spmvlayout::hot_threshold_from_hist(hh.data(), hh.data() + (HOT_HIST + 1), HOT_HIST, slots);
+    }
+    if (ht.decided) {
+        lo = ht.thr;
+        c[0] = ht.cols;
+        c[1] = ht.refs;
+    } else {
+        CSRK_TRY(hot_census_at(cnt, census, nc, (int32_t)lo, c, s));
+        if (c[0] > (unsigned long long)slots) {
+            while (lo + 1 < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                CSRK_TRY(hot_census_at(cnt, census, nc, spmvlayout::clamp_i32(mid), c, s));
+                if (c[0] <= (unsigned long long)slots)
+                    hi = mid;
+                else
+                    lo = mid;
             }
-            lo = thr0;
-            c[0] = n_ge;
-            c[1] = s_ge;
-            decided = true;
+            CSRK_TRY(hot_census_at(cnt, census, nc, spmvlayout::clamp_i32(hi), c, s));
+            lo = hi;
         }
     }
-    if (!decided) CSRK_TRY(census_at((int32_t)lo, c));
-    if (!decided && c[0] > (unsigned long long)HOT_SLOTS) {
-        while (lo + 1 < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            CSRK_TRY(census_at((int32_t)(mid > INT32_MAX ? INT32_MAX : mid), c));
-            if (c[0] <= (unsigned long long)HOT_SLOTS)
-                hi = mid;
-            else
-                lo = mid;
-        }
-        CSRK_TRY(census_at((int32_t)(hi > INT32_MAX ? INT32_MAX : hi), c));
-        lo = hi;
-    }
-    const int32_t thr = (int32_t)(lo > INT32_MAX ? INT32_MAX : lo);
-    const int32_t n_hot = (int32_t)c[0];
-    tr.lap("  hot: threshold");
-    p->hot_cover = n_samples ? (double)c[1] / (double)n_samples : 0.0;
-    if (n_hot == 0 || (!force && p->hot_cover < 0.2)) return CSRK_OK;
+    *thr = spmvlayout::clamp_i32(lo);
+    return CSRK_OK;
+}
 
-    // Slots in order of popularity (count descending, column ascending among equals): the first
-    // LS_HOT_LDS slots are the ones the light stream keeps in LDS, and the packed lines that follow
-    // are referenced less and less often, so what L2 fails to retain is the pack's tail.
+// The packed columns, in column order (hot_cols, with their counts in hcnt), then in order of popularity: stable, count
+// descending (hot_sort_*_kernel): four 8-bit passes, ping-pong between (hcnt, hot_cols) and (k2, v2)
+static int hot_order(SpmvPlan *p, const DevBuf &cnt, DevBuf &slot, DevBuf &hcnt, int32_t nc, int32_t thr, int32_t n_hot, hipStream_t s)
+{
     const unsigned gc = (unsigned)ceil_div((int64_t)nc + 1, 256);
     hot_flag_kernel<<<gc, 256, 0, s>>>(cnt.as<int32_t>(), nc, thr, slot.as<int32_t>());
     CSRK_LAUNCH_CHECK();
     CSRK_TRY(exclusive_scan_i32(slot.as<int32_t>(), slot.as<int32_t>(), nc, s));
     CSRK_TRY(p->hot_cols.alloc((size_t)n_hot * 4));
-    DevBuf hcnt;
     CSRK_TRY(hcnt.alloc((size_t)n_hot * 4));
     hot_list_kernel<<<gc, 256, 0, s>>>(cnt.as<int32_t>(), slot.as<int32_t>(), nc, thr, p->hot_cols.as<int32_t>(),
                                       hcnt.as<int32_t>());
     CSRK_LAUNCH_CHECK();
-    {
-        // stable, count descending (hot_sort_*_kernel): four 8-bit passes, ping-pong between (hcnt, hot_cols) and (k2, v2)
-        const int32_t nchunk = (int32_t)ceil_div(n_hot, HS_CHUNK);
-        DevBuf k2, v2, dc;
-        CSRK_TRY(k2.alloc((size_t)n_hot * 4));
-        CSRK_TRY(v2.alloc((size_t)n_hot * 4));
-        CSRK_TRY(dc.alloc((size_t)(256 * (int64_t)nchunk + 1) * 4));
-        uint32_t *ka = hcnt.as<uint32_t>(), *kb = k2.as<uint32_t>();
-        int32_t *va = p->hot_cols.as<int32_t>(), *vb = v2.as<int32_t>();
-        for (int pass = 0; pass < 4; pass++) {
-            hot_sort_count_kernel<<<(unsigned)nchunk, WAVE, 0, s>>>(ka, n_hot, 8 * pass, nchunk, dc.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            CSRK_TRY(exclusive_scan_i32(dc.as<int32_t>(), dc.as<int32_t>(), 256 * (int64_t)nchunk, s));
-            hot_sort_place_kernel<<<(unsigned)nchunk, WAVE, 0, s>>>(ka, va, n_hot, 8 * pass, nchunk, dc.as<int32_t>(), kb, vb);
-            CSRK_LAUNCH_CHECK();
-            std::swap(ka, kb);
-            std::swap(va, vb);
-        }
-        CSRK_HIP(hipStreamSynchronize(s));      // k2, v2, dc are freed here (the sorted columns are back in hot_cols)
+    const int32_t nchunk = (int32_t)ceil_div(n_hot, HS_CHUNK);
+    DevBuf k2, v2, dc;
+    CSRK_TRY(k2.alloc((size_t)n_hot * 4));
+    CSRK_TRY(v2.alloc((size_t)n_hot * 4));
+    CSRK_TRY(dc.alloc((size_t)(256 * (int64_t)nchunk + 1) * 4));
+    uint32_t *ka = hcnt.as<uint32_t>(), *kb = k2.as<uint32_t>();
+    int32_t *va = p->hot_cols.as<int32_t>(), *vb = v2.as<int32_t>();
+    for (int pass = 0; pass < 4; pass++) {
+        hot_sort_count_kernel<<<(unsigned)nchunk, WAVE, 0, s>>>(ka, n_hot, 8 * pass, nchunk, dc.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(exclusive_scan_i32(dc.as<int32_t>(), dc.as<int32_t>(), 256 * (int64_t)nchunk, s));
+        hot_sort_place_kernel<<<(unsigned)nchunk, WAVE, 0, s>>>(ka, va, n_hot, 8 * pass, nchunk, dc.as<int32_t>(), kb, vb);
+        CSRK_LAUNCH_CHECK();
+        std::swap(ka, kb);
+        std::swap(va, vb);
     }
+    CSRK_HIP(hipStreamSynchronize(s));      // k2, v2, dc are freed here (the sorted columns are back in hot_cols)
+    return CSRK_OK;
+}
+
+// Pick the (at most HOT_SLOTS_MAX) most referenced columns and renumber them in a copy of colinds.  Built
+// with the lazy plan (second launch on a handle).  Skipped when x is small enough to live in L1/L2
+// next to the streams anyway, when the matrix is small, or when the cached columns would carry less
+// than a fifth of the entries (no popularity skew: nothing to gain, and the persistent grid has fewer
+// wavefronts in flight than the plain one).  CSRK_SPMV_HOT=0 disables, =1 forces.
+template <class P>
+static int build_hot_cache(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s)
+{
+    p->n_hot = 0;
+    if (knobs.hot == 0) return CSRK_OK;
+    const bool force = knobs.hot == 1;
+    if (m->nnz < 2 || m->ncols < 1) return CSRK_OK;
+    PlanTrace tr(knobs);
+    // 4 MiB of packed x, most popular first (light stream, LDS for the first 8192: 64k 0.340, 256k 0.308, 512k 0.302, 1M 0.297,
+    // 2M 0.297 ms, but the per-call pack costs more than that gains past 512k); earlier sweep, tile kernel, 512 KiB of packed
+    // x (measured on the headline matrix: 16k 0.431, 64k 0.422, 256k 0.430, 1M 0.439, 4M 0.460 ms for the tile kernel; none
+    // 0.481)
+    const int64_t slots = HOT_SLOTS_MAX;
+    p->hot_slots = (int32_t)slots;
+    // x that fits in L2 whole needs no packing
+    if (!force && !spmvlayout::pack_worth_counting(m->nnz, m->ncols)) return CSRK_OK;
+    const int32_t nc = m->ncols;
+    DevBuf cnt, slot, census;
+    CSRK_TRY(cnt.alloc((size_t)(nc + 1) * 4));
+    CSRK_TRY(slot.alloc((size_t)(nc + 2) * 4));
+    CSRK_TRY(census.alloc(16));
+    int64_t n_samples = 0;
+    CSRK_TRY(hot_counts<P>(m, p, cnt, census, &n_samples, s));
+    tr.lap("  hot: column counts");
+    if (n_samples == 0) return CSRK_OK;
+    int32_t thr = 0;
+    unsigned long long c[2] = {0, 0};
+    CSRK_TRY(hot_threshold(cnt, census, nc, n_samples, slots, &thr, c, s));
+    const int32_t n_hot = (int32_t)c[0];
+    tr.lap("  hot: threshold");
+    p->hot_cover = n_samples ? (double)c[1] / (double)n_samples : 0.0;
+    if (n_hot == 0 || (!force && !spmvlayout::pack_cover_pays(p->hot_cover))) return CSRK_OK;
+
+    // Slots in order of popularity (count descending, column ascending among equals): the first
+    // LS_HOT_LDS slots are the ones the light stream keeps in LDS, and the packed lines that follow
+    // are referenced less and less often, so what L2 fails to retain is the pack's tail.
+    DevBuf hcnt;
+    CSRK_TRY(hot_order(p, cnt, slot, hcnt, nc, thr, n_hot, s));
     tr.lap("  hot: list, order by count");
     // column -> slot map (-1: not packed); the light stream's fill reads it, as does the renumbered colinds copy
     // the tile kernel needs when no stream is built
@@ -1638,25 +1645,25 @@ static int build_hot_cache(Matrix *m, SpmvPlan *p, hipStream_t s)
     hot_slot_kernel<<<(unsigned)ceil_div(n_hot, 256), 256, 0, s>>>(p->hot_cols.as<int32_t>(), n_hot, p->hot_slot.as<int32_t>());
     CSRK_LAUNCH_CHECK();
     CSRK_TRY(p->xh.alloc((size_t)n_hot * 8));
-    const int32_t n_top = n_hot < LS_HOT_LDS ? n_hot : LS_HOT_LDS;
     p->n_hot = n_hot;
-    p->n_hot_lds = n_top;
+    p->n_hot_lds = n_hot < LS_HOT_LDS ? n_hot : LS_HOT_LDS;
     CSRK_HIP(hipStreamSynchronize(s));     // hcnt is freed on return
     return CSRK_OK;
 }
 
+// ---- the light stream: build_stream, build_cold_stage, build_light_stream -------------------------
 // Build the arrays of the light stream from a view: view row r (r < nrows_view) is the source entries
 // src[r] .. src[r] + (rpv[r+1] - rpv[r]) of (ci, vs); n_ent entries in n_tiles tiles.
 template <class P, int VT>
 static int build_stream(Matrix *m, LightStream *ls, const P *src, const P *rpv, int32_t nrows_view, const int32_t *ci,
-                        const void *vs, int64_t n_ent, int64_t n_tiles, int32_t n_out, const int32_t *slot_map, hipStream_t s,
-                        const P *rp_len = nullptr)
+                        const void *vs, int64_t n_ent, int64_t n_tiles, int32_t n_out, const int32_t *slot_map,
+                        const SpmvKnobs &knobs, hipStream_t s, const P *rp_len = nullptr)
 {
     // rp_len (dense rows): rpv gives every row of the view at least one slot; a row that is empty in rp_len is one padding
     // entry.  Run k is then row k, and no row-id table is built.
     ls->on = false;
     ls->dense = rp_len != nullptr;
-    PlanTrace tr;
+    PlanTrace tr(knobs);
     DevBuf ridx;
     CSRK_TRY(ridx.alloc((size_t)(nrows_view + 2) * 4));
     const unsigned gr = (unsigned)ceil_div((int64_t)nrows_view + 1, 256);
@@ -1696,15 +1703,14 @@ static int build_stream(Matrix *m, LightStream *ls, const P *src, const P *rpv, 
     CSRK_TRY(ls->carry_row.alloc((size_t)n_tiles * 4));
     CSRK_TRY(ls->carry_val.alloc((size_t)n_tiles * 8));
     int cus = 0;
-    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    int64_t wgs = (int64_t)(cus > 0 ? cus : 256);
+    CSRK_TRY(device_cus(m, &cus));
     CSRK_TRY(spmv_kernel_attributes());
-    const int64_t need = ceil_div(n_tiles, LS_THREADS / WAVE);
-    ls->grid = (unsigned)(wgs < need ? wgs : need);
+    const int64_t need = ceil_div(n_tiles, LS_THREADS / WAVE);      // one persistent workgroup per CU at most
+    ls->grid = (unsigned)((int64_t)cus < need ? (int64_t)cus : need);
     ls->n_tiles = n_tiles;
     ls->n_runs = n_runs;
     ls->n_out = n_out;
-    CSRK_HIP(hipStreamSynchronize(s));      // ridx, dphys are freed on return; *phys is a host temporary
+    CSRK_HIP(hipStreamSynchronize(s));      // ridx, tile_row are freed on return
     tr.lap("  light: runs, fill");
     ls->on = true;
     return CSRK_OK;
@@ -1862,78 +1868,51 @@ __global__ __launch_bounds__(256) void ls_idx24_kernel(const uint32_t *__restric
     ((u32x2_t *)(tp + ACC_TILE * 2))[lane] = hi;
 }
 
-static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols, int32_t n_hot, hipStream_t s)
-{
-    ls->idx24 = false;
-    ls->n_cold = 0;
-    ls->stage_tiles = 0;
-    ls->n_rounds = 0;
-    ls->max_wg_rounds = 0;
-    const char *env = getenv("CSRK_LS_STAGE");
-    if (env && env[0] == '0') return CSRK_OK;
-    const int64_t n_words = ls->n_tiles * ACC_TILE;
-    // a number of column blocks that fills the chip a whole number of times (two workgroups per CU), each window
-    // at most LS_STAGE_WMAX columns
-    int cus = 0;
-    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    const int64_t wave_of_wgs = 2 * (int64_t)(cus > 0 ? cus : 256);
-    const int64_t nblk_goal = wave_of_wgs * ceil_div((int64_t)m->ncols, wave_of_wgs * LS_STAGE_WMAX);
-    const int64_t W = ceil_div(ceil_div((int64_t)m->ncols, nblk_goal), 16) * 16;
-    const int64_t nblk = ceil_div((int64_t)m->ncols, W);
-    // (the smallest rounds make the most buckets; a balanced layout adds at most one round per workgroup)
-    const int64_t nb_max = (ceil_div(ls->n_tiles, LS_STAGE_TILES < LS_THREADS / WAVE ? LS_STAGE_TILES : LS_THREADS / WAVE) + (int64_t)ls->grid + 2) * nblk;
-    if (nb_max < 1 || nb_max > (int64_t)1 << 26) return CSRK_OK;
-    size_t mfree = 0, mtotal = 0;
-    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
-    if ((size_t)n_words * 20 + (size_t)nb_max * 16 + (64u << 20) > mfree) return CSRK_OK;
-    if (ls->n_tiles >= INT32_MAX) return CSRK_OK;
-    PlanTrace tr;
+// Cold staging of one light stream (spmv_plan.h, "cold staging"): the temporaries in the order they are released in
+// reverse, the column blocks, and the rounds of the last count pass.  build_cold_stage runs the steps.
+struct ColdStage {
+    static constexpr int NW = LS_THREADS / WAVE;      // a round is a whole number of tiles per wavefront
+    static_assert(NW * ACC_TILE <= LS_RND_CAP, "the smallest round must fit the LDS round buffer");
+    LightStream *ls;
+    hipStream_t s;
     DevBuf cnt, cntT, off, offp, tot, tile_round, d_rt0;
-    CSRK_TRY(tile_round.alloc((size_t)ls->n_tiles * 4));
-    CSRK_TRY(d_rt0.alloc((size_t)(ls->n_tiles + 2) * 4));
-    CSRK_TRY(offp.alloc((size_t)n_hot * 4));
-    CSRK_TRY(cnt.alloc((size_t)(nb_max + 1) * 4));
-    CSRK_TRY(cntT.alloc((size_t)(nb_max + 1) * 4));
-    CSRK_TRY(off.alloc((size_t)n_words * 4));
-    CSRK_TRY(tot.alloc((size_t)(nb_max + 1) * 8));
-    const unsigned gw = (unsigned)ceil_div(n_words, 256);
+    spmvlayout::StageBlocks sb;      // W columns per block, nblk blocks, nb_max (round, block) buckets at most
+    int64_t n_words = 0;
     int stage_tiles = LS_STAGE_TILES;
     int64_t nround_ls = 0, nround = 0, nb = 0, n_cold = 0;      // n_cold = where the virtual round starts
-    // counts per (round, block) bucket for rounds of `nt` tiles; the old count is an entry's place inside its bucket
-    // Rounds of at most `nt` tiles: every workgroup of the stream's persistent grid gets an equal share of the tiles, cut
-    // into equal rounds (whole tiles per wavefront).
-    std::vector<int32_t> h_rt0, h_wr0;
-    constexpr int NW_ = LS_THREADS / WAVE;
-    auto make_rounds = [&](int nt) {
-        h_rt0.clear();
-        h_wr0.clear();
-        const int64_t G = ls->grid;
-        for (int64_t w = 0; w < G; w++) {
-            const int64_t tb = ls->n_tiles * w / G, te = ls->n_tiles * (w + 1) / G;
-            h_wr0.push_back((int32_t)h_rt0.size());
-            if (te > tb) {
-                const int64_t k = ceil_div(te - tb, nt);
-                const int64_t per = ceil_div(ceil_div(te - tb, k), NW_) * NW_;
-                for (int64_t t = tb; t < te; t += per) h_rt0.push_back((int32_t)t);
-            }
-        }
-        h_wr0.push_back((int32_t)h_rt0.size());
-        nround_ls = (int64_t)h_rt0.size();
-        h_rt0.push_back((int32_t)ls->n_tiles);
-    };
-    auto count_pass = [&](int nt, int64_t *max_round) -> int {
+    std::vector<int32_t> h_rt0, h_wr0;                          // round_tile0, wg_round0 (spmvlayout::stage_rounds)
+
+    void make_rounds(int nt) { nround_ls = spmvlayout::stage_rounds(ls->n_tiles, ls->grid, nt, NW, h_rt0, h_wr0); }
+
+    int alloc(int32_t n_hot)
+    {
+        CSRK_TRY(tile_round.alloc((size_t)ls->n_tiles * 4));
+        CSRK_TRY(d_rt0.alloc((size_t)(ls->n_tiles + 2) * 4));
+        CSRK_TRY(offp.alloc((size_t)n_hot * 4));
+        CSRK_TRY(cnt.alloc((size_t)(sb.nb_max + 1) * 4));
+        CSRK_TRY(cntT.alloc((size_t)(sb.nb_max + 1) * 4));
+        CSRK_TRY(off.alloc((size_t)n_words * 4));
+        CSRK_TRY(tot.alloc((size_t)(sb.nb_max + 1) * 8));
+        return CSRK_OK;
+    }
+
+    // counts per (round, block) bucket for rounds of `nt` tiles; the old count is an entry's place inside its bucket.
+    // *max_round = the staged values of the fullest round.
+    int count_pass(int nt, int64_t *max_round)
+    {
+        const int64_t nblk = sb.nblk;
         stage_tiles = nt;
         make_rounds(nt);
         nround = nround_ls + 1;      // + the virtual round of the packed columns
         nb = nround * nblk;
-        if (nb > nb_max) return CSRK_ERR_INVALID;      // (cannot happen: a round holds at least LS_STAGE_TILES or NW tiles)
+        if (nb > sb.nb_max) return CSRK_ERR_INVALID;      // (cannot happen: a round holds at least LS_STAGE_TILES or NW tiles)
         CSRK_TRY(stage_h2d(d_rt0.p, h_rt0.data(), h_rt0.size() * 4, s));
         ls_tile_round_kernel<<<(unsigned)ceil_div(ls->n_tiles, 256), 256, 0, s>>>(d_rt0.as<int32_t>(), (int32_t)nround_ls, ls->n_tiles,
                                                                                 tile_round.as<int32_t>());
         CSRK_LAUNCH_CHECK();
         CSRK_HIP(hipMemsetAsync(cnt.p, 0, (size_t)(nb + 1) * 4, s));
-        ls_cold_count_kernel<<<gw, 256, 0, s>>>(ls->idx.as<uint32_t>(), n_words, (int32_t)nblk, (int32_t)W, tile_round.as<int32_t>(),
-                                               cnt.as<int32_t>(), off.as<int32_t>());
+        ls_cold_count_kernel<<<(unsigned)ceil_div(n_words, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), n_words, (int32_t)nblk, (int32_t)sb.W,
+                                                                            tile_round.as<int32_t>(), cnt.as<int32_t>(), off.as<int32_t>());
         CSRK_LAUNCH_CHECK();
         // the counts are 32-bit: total them in 64 bits before trusting the 32-bit scans
         CSRK_TRY(exclusive_scan_i32_to_i64(cnt.as<int32_t>(), tot.as<int64_t>(), nround_ls * nblk, s));
@@ -1949,108 +1928,188 @@ static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols,
         *max_round = 0;
         for (int64_t r = 0; r < nround_ls; r++) *max_round = std::max(*max_round, rs[(size_t)r + 1] - rs[(size_t)r]);
         return CSRK_OK;
-    };
-    // the largest rounds whose staged values fit the LDS round buffer (a round of one tile per wavefront always does)
-    int64_t max_round = 0;
+    }
+
+    // where to start: the largest round size that fits by the tiles' own cold counts (then one count pass confirms it)
+    int first_round_size(int *nt_first)
     {
-        constexpr int NW = LS_THREADS / WAVE;      // a round is a whole number of tiles per wavefront
-        static_assert(NW * ACC_TILE <= LS_RND_CAP, "the smallest round must fit the LDS round buffer");
-        bool fits = false;
-        // where to start: the largest size that fits by the tiles' own cold counts (then one count pass confirms it)
-        int nt_first = LS_RND_MAXTILES / NW * NW;
-        {
-            DevBuf tcold, tpre;
-            CSRK_TRY(tcold.alloc((size_t)(ls->n_tiles + 1) * 4));
-            CSRK_TRY(tpre.alloc((size_t)(ls->n_tiles + 2) * 8));
-            ls_tile_cold_kernel<<<(unsigned)ceil_div(ls->n_tiles * WAVE, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), ls->n_tiles,
-                                                                                          tcold.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-            CSRK_TRY(exclusive_scan_i32_to_i64(tcold.as<int32_t>(), tpre.as<int64_t>(), ls->n_tiles, s));
-            std::vector<int64_t> pre((size_t)ls->n_tiles + 1);
-            CSRK_TRY(stage_d2h(pre.data(), tpre.p, pre.size() * 8, s));
-            CSRK_HIP(hipStreamSynchronize(s));
-            for (; nt_first > NW; nt_first -= NW) {
-                make_rounds(nt_first);
-                int64_t mx = 0;
-                for (int64_t r = 0; r < nround_ls; r++)
-                    mx = std::max(mx, pre[(size_t)h_rt0[(size_t)r + 1]] - pre[(size_t)h_rt0[(size_t)r]]);
-                if (mx <= LS_RND_CAP) break;
-            }
+        *nt_first = LS_RND_MAXTILES / NW * NW;
+        DevBuf tcold, tpre;
+        CSRK_TRY(tcold.alloc((size_t)(ls->n_tiles + 1) * 4));
+        CSRK_TRY(tpre.alloc((size_t)(ls->n_tiles + 2) * 8));
+        ls_tile_cold_kernel<<<(unsigned)ceil_div(ls->n_tiles * WAVE, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), ls->n_tiles,
+                                                                                      tcold.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(exclusive_scan_i32_to_i64(tcold.as<int32_t>(), tpre.as<int64_t>(), ls->n_tiles, s));
+        std::vector<int64_t> pre((size_t)ls->n_tiles + 1);
+        CSRK_TRY(stage_d2h(pre.data(), tpre.p, pre.size() * 8, s));
+        CSRK_HIP(hipStreamSynchronize(s));
+        for (; *nt_first > NW; *nt_first -= NW) {
+            make_rounds(*nt_first);
+            int64_t mx = 0;
+            for (int64_t r = 0; r < nround_ls; r++)
+                mx = std::max(mx, pre[(size_t)h_rt0[(size_t)r + 1]] - pre[(size_t)h_rt0[(size_t)r]]);
+            if (mx <= LS_RND_CAP) break;
         }
+        return CSRK_OK;
+    }
+
+    // the largest rounds whose staged values fit the LDS round buffer (a round of one tile per wavefront always does)
+    int choose_round_size(bool *fits)
+    {
+        *fits = false;
+        int nt_first = 0;
+        CSRK_TRY(first_round_size(&nt_first));
         for (int nt = nt_first; nt >= NW;) {
+            int64_t max_round = 0;
             CSRK_TRY(count_pass(nt, &max_round));
             if (max_round <= LS_RND_CAP) {
-                fits = true;
+                *fits = true;
                 break;
             }
-            // the fullest round scales with the round's size: jump to the size that would just fit, then step down
-            int next = (int)((double)nt * LS_RND_CAP / (double)max_round) / NW * NW;
-            nt = next < nt - NW ? next : nt - NW;
+            nt = spmvlayout::next_round_size(nt, LS_RND_CAP, max_round, NW);
         }
-        if (!fits) return CSRK_OK;
+        return CSRK_OK;
     }
-    tr.lap("  cold: round size (count passes)");
-    if (nround > INT32_MAX) return CSRK_OK;
-    CSRK_HIP(hipMemsetAsync(cnt.as<int32_t>() + nround_ls * nblk, 0, (size_t)(nblk + 1) * 4, s));
-    ls_pack_count_kernel<<<(unsigned)ceil_div(n_hot, 256), 256, 0, s>>>(hot_cols, n_hot, (int32_t)W,
-                                                                       cnt.as<int32_t>() + nround_ls * nblk, offp.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    CSRK_HIP(hipMemsetAsync(cntT.p, 0, (size_t)(nb + 1) * 4, s));
-    ls_cold_transpose_kernel<<<(unsigned)ceil_div(nb, 256), 256, 0, s>>>(cnt.as<int32_t>(), (int32_t)nround, (int32_t)nblk,
-                                                                       cntT.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    const int64_t n_all = n_cold + n_hot;
-    // worth a pass of its own only when the cold columns cannot live in L2 anyway and there are enough of them
-    if (n_cold < 1 || n_all >= (int64_t)LS_PAD || (!(env && env[0] == '1') && n_cold * 16 < n_words)) return CSRK_OK;
-    CSRK_TRY(exclusive_scan_i32(cnt.as<int32_t>(), cnt.as<int32_t>(), nb + 1, s));
-    CSRK_TRY(exclusive_scan_i32(cntT.as<int32_t>(), cntT.as<int32_t>(), nb + 1, s));
-    CSRK_TRY(ls->xg.alloc((size_t)(n_all + WAVE) * 8));      // (+ padding: the stream kernel's last pair of an odd count)
-    CSRK_TRY(ls->a_col.alloc((size_t)n_all * 2));
-    CSRK_TRY(ls->a_dst.alloc((size_t)n_all * 4));
-    CSRK_TRY(ls->round_start.alloc((size_t)(nround_ls + 1) * 4));
-    ls_round_start_kernel<<<(unsigned)ceil_div(nround_ls + 1, 256), 256, 0, s>>>(cnt.as<int32_t>(), (int32_t)nround_ls, (int32_t)nblk,
-                                                                               ls->round_start.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    CSRK_TRY(ls->round_tile0.alloc(h_rt0.size() * 4));
-    CSRK_TRY(ls->wg_round0.alloc(h_wr0.size() * 4));
-    CSRK_TRY(stage_h2d(ls->round_tile0.p, h_rt0.data(), h_rt0.size() * 4, s));
-    CSRK_TRY(stage_h2d(ls->wg_round0.p, h_wr0.data(), h_wr0.size() * 4, s));
-    ls_cold_place_kernel<<<gw, 256, 0, s>>>(ls->idx.as<uint32_t>(), n_words, (int32_t)nround, (int32_t)nblk, (int32_t)W,
-                                           tile_round.as<int32_t>(), 1, cnt.as<int32_t>(), cntT.as<int32_t>(), off.as<int32_t>(),
-                                           ls->a_col.as<uint16_t>(), ls->a_dst.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    ls_pack_place_kernel<<<(unsigned)ceil_div(n_hot, 256), 256, 0, s>>>(hot_cols, n_hot, (int32_t)W, (int32_t)nround,
-                                                                       cntT.as<int32_t>(), offp.as<int32_t>(), (int32_t)n_cold,
-                                                                       ls->a_col.as<uint16_t>(), ls->a_dst.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    CSRK_TRY(ls->blk_start.alloc((size_t)(nblk + 1) * 4));
-    ls_stage_starts_kernel<<<(unsigned)ceil_div(nblk + 1, 256), 256, 0, s>>>(cntT.as<int32_t>(), (int32_t)nround, (int32_t)nblk,
-                                                                            ls->blk_start.as<int32_t>());
-    CSRK_LAUNCH_CHECK();
-    ls->n_stage_blk = (int32_t)nblk;
-    ls->stage_w = (int32_t)W;
-    CSRK_TRY(spmv_kernel_attributes());
+
+    // the packed columns ride along as a virtual last round; then the counts in (block, round) order beside (round, block)
+    int count_pack(const int32_t *hot_cols, int32_t n_hot)
+    {
+        const int64_t nblk = sb.nblk;
+        CSRK_HIP(hipMemsetAsync(cnt.as<int32_t>() + nround_ls * nblk, 0, (size_t)(nblk + 1) * 4, s));
+        ls_pack_count_kernel<<<(unsigned)ceil_div(n_hot, 256), 256, 0, s>>>(hot_cols, n_hot, (int32_t)sb.W,
+                                                                           cnt.as<int32_t>() + nround_ls * nblk, offp.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_HIP(hipMemsetAsync(cntT.p, 0, (size_t)(nb + 1) * 4, s));
+        ls_cold_transpose_kernel<<<(unsigned)ceil_div(nb, 256), 256, 0, s>>>(cnt.as<int32_t>(), (int32_t)nround, (int32_t)nblk,
+                                                                           cntT.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        return CSRK_OK;
+    }
+
+    // the stream's staging arrays: where every cold entry and packed column is copied from and to, the index words rewritten
+    // to round offsets, the rounds' and blocks' starts
+    int place(const int32_t *hot_cols, int32_t n_hot)
+    {
+        const int64_t nblk = sb.nblk, n_all = n_cold + n_hot;
+        CSRK_TRY(exclusive_scan_i32(cnt.as<int32_t>(), cnt.as<int32_t>(), nb + 1, s));
+        CSRK_TRY(exclusive_scan_i32(cntT.as<int32_t>(), cntT.as<int32_t>(), nb + 1, s));
+        CSRK_TRY(ls->xg.alloc((size_t)(n_all + WAVE) * 8));      // (+ padding: the stream kernel's last pair of an odd count)
+        CSRK_TRY(ls->a_col.alloc((size_t)n_all * 2));
+        CSRK_TRY(ls->a_dst.alloc((size_t)n_all * 4));
+        CSRK_TRY(ls->round_start.alloc((size_t)(nround_ls + 1) * 4));
+        ls_round_start_kernel<<<(unsigned)ceil_div(nround_ls + 1, 256), 256, 0, s>>>(cnt.as<int32_t>(), (int32_t)nround_ls, (int32_t)nblk,
+                                                                                   ls->round_start.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(ls->round_tile0.alloc(h_rt0.size() * 4));
+        CSRK_TRY(ls->wg_round0.alloc(h_wr0.size() * 4));
+        CSRK_TRY(stage_h2d(ls->round_tile0.p, h_rt0.data(), h_rt0.size() * 4, s));
+        CSRK_TRY(stage_h2d(ls->wg_round0.p, h_wr0.data(), h_wr0.size() * 4, s));
+        ls_cold_place_kernel<<<(unsigned)ceil_div(n_words, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), n_words, (int32_t)nround, (int32_t)nblk,
+                                                                            (int32_t)sb.W, tile_round.as<int32_t>(), 1, cnt.as<int32_t>(),
+                                                                            cntT.as<int32_t>(), off.as<int32_t>(), ls->a_col.as<uint16_t>(),
+                                                                            ls->a_dst.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        ls_pack_place_kernel<<<(unsigned)ceil_div(n_hot, 256), 256, 0, s>>>(hot_cols, n_hot, (int32_t)sb.W, (int32_t)nround,
+                                                                           cntT.as<int32_t>(), offp.as<int32_t>(), (int32_t)n_cold,
+                                                                           ls->a_col.as<uint16_t>(), ls->a_dst.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(ls->blk_start.alloc((size_t)(nblk + 1) * 4));
+        ls_stage_starts_kernel<<<(unsigned)ceil_div(nblk + 1, 256), 256, 0, s>>>(cntT.as<int32_t>(), (int32_t)nround, (int32_t)nblk,
+                                                                                ls->blk_start.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+        ls->n_stage_blk = (int32_t)nblk;
+        ls->stage_w = (int32_t)sb.W;
+        CSRK_TRY(spmv_kernel_attributes());
+        return CSRK_OK;
+    }
+
     // every column field is now a pack slot (< n_hot) or an offset into a round's staged values (< LS_RND_CAP): 3-byte words
-    DevBuf idx24;
-    const bool narrow = CSRK_LS_IDX24 && (int64_t)n_hot < (int64_t)LS24_COL_MASK && (int64_t)LS_RND_CAP < (int64_t)LS24_COL_MASK;
-    if (narrow) {
-        CSRK_TRY(idx24.alloc((size_t)ls->n_tiles * LS24_TILE_BYTES));
-        ls_idx24_kernel<<<(unsigned)ceil_div(ls->n_tiles * WAVE, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), ls->n_tiles,
-                                                                                   idx24.as<unsigned char>());
+    int narrow_words(int32_t n_hot)
+    {
+        DevBuf idx24;
+        const bool narrow = CSRK_LS_IDX24 && (int64_t)n_hot < (int64_t)LS24_COL_MASK && (int64_t)LS_RND_CAP < (int64_t)LS24_COL_MASK;
+        if (narrow) {
+            CSRK_TRY(idx24.alloc((size_t)ls->n_tiles * LS24_TILE_BYTES));
+            ls_idx24_kernel<<<(unsigned)ceil_div(ls->n_tiles * WAVE, 256), 256, 0, s>>>(ls->idx.as<uint32_t>(), ls->n_tiles,
+                                                                                       idx24.as<unsigned char>());
+            CSRK_LAUNCH_CHECK();
+        }
+        CSRK_HIP(hipStreamSynchronize(s));      // the temporaries are freed on return
+        if (narrow) {
+            ls->idx.release();
+            ls->idx.p = idx24.take();
+            ls->idx.bytes = (size_t)ls->n_tiles * LS24_TILE_BYTES;
+            ls->idx24 = true;
+        }
+        return CSRK_OK;
+    }
+};
+
+static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols, int32_t n_hot, const SpmvKnobs &knobs, hipStream_t s)
+{
+    ls->idx24 = false;
+    ls->n_cold = 0;
+    ls->stage_tiles = 0;
+    ls->n_rounds = 0;
+    ls->max_wg_rounds = 0;
+    if (knobs.ls_stage == 0) return CSRK_OK;
+    ColdStage C;
+    C.ls = ls;
+    C.s = s;
+    C.n_words = ls->n_tiles * ACC_TILE;
+    int cus = 0;
+    CSRK_TRY(device_cus(m, &cus));
+    C.sb = spmvlayout::stage_blocks(m->ncols, cus, LS_STAGE_WMAX, ls->n_tiles,
+                                    LS_STAGE_TILES < ColdStage::NW ? LS_STAGE_TILES : ColdStage::NW, ls->grid);
+    if (C.sb.nb_max < 1 || C.sb.nb_max > (int64_t)1 << 26) return CSRK_OK;
+    size_t mfree = 0, mtotal = 0;
+    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
+    if (!spmvlayout::stage_temps_fit(C.n_words, C.sb.nb_max, mfree)) return CSRK_OK;
+    if (ls->n_tiles >= INT32_MAX) return CSRK_OK;
+    PlanTrace tr(knobs);
+    CSRK_TRY(C.alloc(n_hot));
+    bool fits = false;
+    CSRK_TRY(C.choose_round_size(&fits));
+    if (!fits) return CSRK_OK;
+    tr.lap("  cold: round size (count passes)");
+    if (C.nround > INT32_MAX) return CSRK_OK;
+    CSRK_TRY(C.count_pack(hot_cols, n_hot));
+    // worth a pass of its own only when the cold columns cannot live in L2 anyway and there are enough of them
+    if (C.n_cold < 1 || C.n_cold + n_hot >= (int64_t)LS_PAD || (knobs.ls_stage != 1 && !spmvlayout::cold_stage_pays(C.n_cold, C.n_words)))
+        return CSRK_OK;
+    CSRK_TRY(C.place(hot_cols, n_hot));
+    CSRK_TRY(C.narrow_words(n_hot));
+    ls->n_cold = C.n_cold;
+    ls->stage_tiles = C.stage_tiles;
+    ls->n_rounds = (int32_t)C.nround_ls;
+    for (size_t w = 0; w + 1 < C.h_wr0.size(); w++) ls->max_wg_rounds = std::max(ls->max_wg_rounds, C.h_wr0[w + 1] - C.h_wr0[w]);
+    tr.lap("  cold: place, 3-byte words");
+    return CSRK_OK;
+}
+
+// Dense rows: when few rows of the view are empty (rows without entries, rows cut out for the tiers: 7 % on the
+// headline matrix) each of them gets ONE padding entry, so every row has a run, run k IS row k, and the stream kernel
+// neither loads row ids (4 loads per tile: 12 of its 170 us) nor clears gaps.  rpd = the view's pointers with empty
+// rows widened to one slot (left empty where spmvlayout::dense_rows_pay says no); *n_pad = the view's empty rows.
+template <class P>
+static int dense_row_pointers(Matrix *m, const P *rpv, int64_t n_view, DevBuf &rpd, int64_t *n_pad, hipStream_t s)
+{
+    DevBuf nz;
+    CSRK_TRY(nz.alloc((size_t)(m->nrows + 2) * 4));
+    ls_rowflag_kernel<P><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256, 0, s>>>(rpv, m->nrows, nz.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(exclusive_scan_i32(nz.as<int32_t>(), nz.as<int32_t>(), m->nrows, s));
+    int32_t n_nonempty = 0;
+    CSRK_TRY(stage_d2h(&n_nonempty, nz.as<int32_t>() + m->nrows, 4, s));
+    CSRK_HIP(hipStreamSynchronize(s));
+    *n_pad = (int64_t)m->nrows - n_nonempty;
+    if (spmvlayout::dense_rows_pay(n_view, *n_pad, sizeof(P) == 8)) {
+        CSRK_TRY(rpd.alloc((size_t)(m->nrows + 1) * sizeof(P)));
+        ls_dense_ptr_kernel<P><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256, 0, s>>>(rpv, nz.as<int32_t>(), m->nrows, rpd.as<P>());
         CSRK_LAUNCH_CHECK();
     }
-    CSRK_HIP(hipStreamSynchronize(s));      // the temporaries are freed on return
-    if (narrow) {
-        ls->idx.release();
-        ls->idx.p = idx24.take();
-        ls->idx.bytes = (size_t)ls->n_tiles * LS24_TILE_BYTES;
-        ls->idx24 = true;
-    }
-    ls->n_cold = n_cold;
-    ls->stage_tiles = stage_tiles;
-    ls->n_rounds = (int32_t)nround_ls;
-    for (size_t w = 0; w + 1 < h_wr0.size(); w++) ls->max_wg_rounds = std::max(ls->max_wg_rounds, h_wr0[w + 1] - h_wr0[w]);
-    tr.lap("  cold: place, 3-byte words");
+    CSRK_HIP(hipStreamSynchronize(s));      // nz is released here
     return CSRK_OK;
 }
 
@@ -2058,61 +2117,104 @@ static int build_cold_stage(Matrix *m, LightStream *ls, const int32_t *hot_cols,
 // the light stream.  Built with the lazy plan.  Skipped (the tile kernel stays in charge) when ncols needs
 // the two flag bits, when the copy does not fit in device memory, or with CSRK_SPMV_STREAM=0.
 template <class P, int VT>
-static int build_light_stream(Matrix *m, SpmvPlan *p, hipStream_t s)
+static int build_light_stream(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s)
 {
     p->ls.on = false;
-    const char *env = getenv("CSRK_SPMV_STREAM");
-    if (env && env[0] == '0') return CSRK_OK;
+    if (knobs.stream == 0) return CSRK_OK;
+    const bool force = knobs.stream == 1;
     const int64_t n_view = p->n_heavy ? p->nnz_light : m->nnz;
     if (m->nrows == 0 || n_view < 1 || (int64_t)m->ncols > (int64_t)LS_COL_MASK) return CSRK_OK;
     // Without long rows cut out and without a popularity skew worth packing, the gathers are either local
     // (banded: the tile kernel's entry-per-lane order coalesces them better: 0.526 vs 0.638 ms measured) or
     // all equally cold (uniform random columns: both kernels run at the 128-B-per-gather fabric rate), and
     // the stream's copy of the matrix buys nothing.
-    if (!p->n_heavy && !p->n_hot && !(env && env[0] == '1')) return CSRK_OK;
+    if (!p->n_heavy && !p->n_hot && !force) return CSRK_OK;
     const P *rp = (const P *)m->d_rowptrs;
     const P *rpv = p->n_heavy ? p->rp_light.as<P>() : rp;
     const int32_t *slot_map = p->n_hot ? p->hot_slot.as<int32_t>() : (const int32_t *)nullptr;
-    const int64_t n_tiles = ceil_div(n_view, ACC_TILE);
     size_t mfree = 0, mtotal = 0;
     CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
-    if ((size_t)n_tiles * ACC_TILE * 12 + ((size_t)m->nrows + n_tiles) * 8 + (64u << 20) > mfree && !(env && env[0] == '1'))
-        return CSRK_OK;
-    // Dense rows: when few rows of the view are empty (rows without entries, rows cut out for the tiers: 7 % on the
-    // headline matrix) each of them gets ONE padding entry, so every row has a run, run k IS row k, and the stream kernel
-    // neither loads row ids (4 loads per tile: 12 of its 170 us) nor clears gaps.  rpd = the view's pointers with empty
-    // rows widened to one slot.  Not when the padding would add more than an eighth to the stream, nor past P's range.
+    if (!spmvlayout::stream_copy_fits(ceil_div(n_view, ACC_TILE), ACC_TILE, m->nrows, mfree) && !force) return CSRK_OK;
     DevBuf rpd_buf;
-    const P *rp_dense = nullptr;
-    int64_t n_view_d = n_view, n_tiles_d = n_tiles;
-    {
-        DevBuf nz;
-        CSRK_TRY(nz.alloc((size_t)(m->nrows + 2) * 4));
-        ls_rowflag_kernel<P><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256, 0, s>>>(rpv, m->nrows, nz.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        CSRK_TRY(exclusive_scan_i32(nz.as<int32_t>(), nz.as<int32_t>(), m->nrows, s));
-        int32_t n_nonempty = 0;
-        CSRK_TRY(stage_d2h(&n_nonempty, nz.as<int32_t>() + m->nrows, 4, s));
-        CSRK_HIP(hipStreamSynchronize(s));
-        const int64_t n_pad = (int64_t)m->nrows - n_nonempty;
-        const bool fits = sizeof(P) == 8 || n_view + n_pad <= (int64_t)INT32_MAX;
-        if (fits && n_pad * 8 <= n_view) {
-            CSRK_TRY(rpd_buf.alloc((size_t)(m->nrows + 1) * sizeof(P)));
-            ls_dense_ptr_kernel<P><<<(unsigned)ceil_div((int64_t)m->nrows + 1, 256), 256, 0, s>>>(rpv, nz.as<int32_t>(), m->nrows,
-                                                                                                rpd_buf.as<P>());
-            CSRK_LAUNCH_CHECK();
-            rp_dense = rpd_buf.as<P>();
-            n_view_d = n_view + n_pad;
-            n_tiles_d = ceil_div(n_view_d, ACC_TILE);
-        }
-        CSRK_HIP(hipStreamSynchronize(s));      // nz is released here
-    }
-    CSRK_TRY((build_stream<P, VT>(m, &p->ls, rp, rp_dense ? rp_dense : rpv, m->nrows, m->d_colinds, m->d_values, n_view_d, n_tiles_d,
-                                  m->nrows, slot_map, s, rp_dense ? rpv : (const P *)nullptr)));
+    int64_t n_pad = 0;
+    CSRK_TRY(dense_row_pointers<P>(m, rpv, n_view, rpd_buf, &n_pad, s));
+    const P *rp_dense = rpd_buf.p ? rpd_buf.as<P>() : (const P *)nullptr;
+    const int64_t n_ent = rp_dense ? n_view + n_pad : n_view;
+    CSRK_TRY((build_stream<P, VT>(m, &p->ls, rp, rp_dense ? rp_dense : rpv, m->nrows, m->d_colinds, m->d_values, n_ent,
+                                  ceil_div(n_ent, ACC_TILE), m->nrows, slot_map, knobs, s, rp_dense ? rpv : (const P *)nullptr)));
     if (p->ls.on && p->n_hot) {
-        CSRK_TRY(build_cold_stage(m, &p->ls, p->hot_cols.as<int32_t>(), p->n_hot, s));
+        CSRK_TRY(build_cold_stage(m, &p->ls, p->hot_cols.as<int32_t>(), p->n_hot, knobs, s));
         // (round-in-LDS form: the round's staged values take the place of the hot window's tail)
         if (p->ls.n_cold && p->ls.round_start.p && p->n_hot_lds > LS_RND_HOT) p->n_hot_lds = LS_RND_HOT;
+    }
+    return CSRK_OK;
+}
+
+// ---- the plans: merge (with the lazy plan's split, pack and streams) and vector -------------------
+template <class P>
+static int build_merge_plan(Matrix *m, SpmvPlan *p, const SpmvKnobs &knobs, hipStream_t s, bool allow_split)
+{
+    const P *rp = (const P *)m->d_rowptrs;
+    p->tile_items = MERGE_ITEMS;
+    p->nnz_light = m->nnz;
+    p->split_considered = allow_split;
+    PlanTrace tr(knobs);
+    if (allow_split) CSRK_TRY(build_heavy_split<P>(m, p, knobs, s));
+    tr.lap("heavy split");
+    const P *rp_path = p->n_heavy ? p->rp_light.as<P>() : rp;
+    int64_t total = (int64_t)m->nrows + p->nnz_light;
+    p->n_tiles = ceil_div(total, MERGE_ITEMS);
+    CSRK_TRY(p->tile_row.alloc((size_t)(p->n_tiles + 1) * 4));
+    CSRK_TRY(p->carry_row.alloc((size_t)p->n_tiles * 4));
+    CSRK_TRY(p->carry_val.alloc((size_t)p->n_tiles * 8));
+    int64_t nthr = p->n_tiles + 1;
+    merge_plan_kernel<P><<<(unsigned)ceil_div(nthr, 256), 256, 0, s>>>(rp_path, m->nrows, p->nnz_light, MERGE_ITEMS,
+                                                                      p->n_tiles, p->tile_row.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    if (p->n_heavy) {
+        CSRK_TRY(p->tile_cut.alloc((size_t)(p->n_tiles + 1) * 4));
+        heavy_tilecut_kernel<<<(unsigned)ceil_div(nthr, 256), 256, 0, s>>>(
+            p->tile_row.as<int32_t>(), p->n_tiles, MERGE_ITEMS, total, p->cut_pos.as<int64_t>(), p->n_heavy,
+            p->tile_cut.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
+    }
+    tr.lap("merge-path tables");
+    if (!allow_split) return CSRK_OK;
+    CSRK_TRY(build_hot_cache<P>(m, p, knobs, s));
+    tr.lap("hot-column census + pack");
+    CSRK_TRY(build_tiers<P>(m, p, knobs, s));
+    tr.lap("tiers");
+    CSRK_TRY(with_val_type(m->val_type, [&](auto vt) -> int { return build_light_stream<P, decltype(vt)::value>(m, p, knobs, s); }));
+    tr.lap("light stream + cold staging");
+    if (p->n_hot && !p->ls.on) {        // no stream (no memory for it, CSRK_SPMV_STREAM=0): the tile kernel reads x itself
+        p->n_hot = 0;
+        p->hot_cols.release();
+        p->xh.release();
+    }
+    p->hot_slot.release();
+    return CSRK_OK;
+}
+
+template <class P>
+static int build_vector_plan(Matrix *m, SpmvPlan *p, hipStream_t s)
+{
+    const P *rp = (const P *)m->d_rowptrs;
+    CSRK_TRY(p->seg_off.alloc((size_t)(m->nrows + 1) * 8));
+    if (m->nrows > 0) {
+        vec_count_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(rp, m->nrows, p->seg_off.as<int64_t>());
+        CSRK_LAUNCH_CHECK();
+    }
+    CSRK_TRY(exclusive_scan_i64(p->seg_off.as<int64_t>(), p->seg_off.as<int64_t>(), m->nrows, s));
+    int64_t n_segs = 0;
+    CSRK_TRY(stage_d2h(&n_segs, p->seg_off.as<int64_t>() + m->nrows, 8, s));
+    CSRK_HIP(hipStreamSynchronize(s));
+    p->n_segs = n_segs;
+    CSRK_TRY(p->seg_row.alloc((size_t)n_segs * 4));
+    CSRK_TRY(p->seg_part.alloc((size_t)n_segs * 8));
+    if (m->nrows > 0) {
+        vec_fill_kernel<<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(p->seg_off.as<int64_t>(), m->nrows,
+                                                                         p->seg_row.as<int32_t>());
+        CSRK_LAUNCH_CHECK();
     }
     return CSRK_OK;
 }
@@ -2120,67 +2222,9 @@ static int build_light_stream(Matrix *m, SpmvPlan *p, hipStream_t s)
 template <class P>
 static int build_plan(Matrix *m, SpmvPlan *p, hipStream_t s, bool allow_split)
 {
-    const P *rp = (const P *)m->d_rowptrs;
-    if (p->algo == CSRK_SPMV_MERGE) {
-        p->tile_items = MERGE_ITEMS;
-        p->nnz_light = m->nnz;
-        p->split_considered = allow_split;
-        PlanTrace tr;
-        if (allow_split) CSRK_TRY(build_heavy_split<P>(m, p, s));
-        tr.lap("heavy split");
-        const P *rp_path = p->n_heavy ? p->rp_light.as<P>() : rp;
-        int64_t total = (int64_t)m->nrows + p->nnz_light;
-        p->n_tiles = ceil_div(total, MERGE_ITEMS);
-        CSRK_TRY(p->tile_row.alloc((size_t)(p->n_tiles + 1) * 4));
-        CSRK_TRY(p->carry_row.alloc((size_t)p->n_tiles * 4));
-        CSRK_TRY(p->carry_val.alloc((size_t)p->n_tiles * 8));
-        int64_t nthr = p->n_tiles + 1;
-        merge_plan_kernel<P><<<(unsigned)ceil_div(nthr, 256), 256, 0, s>>>(rp_path, m->nrows, p->nnz_light, MERGE_ITEMS,
-                                                                          p->n_tiles, p->tile_row.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        if (p->n_heavy) {
-            CSRK_TRY(p->tile_cut.alloc((size_t)(p->n_tiles + 1) * 4));
-            heavy_tilecut_kernel<<<(unsigned)ceil_div(nthr, 256), 256, 0, s>>>(
-                p->tile_row.as<int32_t>(), p->n_tiles, MERGE_ITEMS, total, p->cut_pos.as<int64_t>(), p->n_heavy,
-                p->tile_cut.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-        }
-        tr.lap("merge-path tables");
-        if (allow_split) {
-            CSRK_TRY(build_hot_cache<P>(m, p, s));
-            tr.lap("hot-column census + pack");
-            CSRK_TRY(build_tiers<P>(m, p, s));
-            tr.lap("tiers");
-            if (m->val_type == CSRK_VAL_F64) CSRK_TRY((build_light_stream<P, CSRK_VAL_F64>(m, p, s)));
-            else if (m->val_type == CSRK_VAL_F32) CSRK_TRY((build_light_stream<P, CSRK_VAL_F32>(m, p, s)));
-            else CSRK_TRY((build_light_stream<P, CSRK_VAL_NONE>(m, p, s)));
-            tr.lap("light stream + cold staging");
-            if (p->n_hot && !p->ls.on) {        // no stream (no memory for it, CSRK_SPMV_STREAM=0): the tile kernel reads x itself
-                p->n_hot = 0;
-                p->hot_cols.release();
-                p->xh.release();
-            }
-            p->hot_slot.release();
-        }
-    } else if (p->algo == CSRK_SPMV_VECTOR) {
-        CSRK_TRY(p->seg_off.alloc((size_t)(m->nrows + 1) * 8));
-        if (m->nrows > 0) {
-            vec_count_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(rp, m->nrows, p->seg_off.as<int64_t>());
-            CSRK_LAUNCH_CHECK();
-        }
-        CSRK_TRY(exclusive_scan_i64(p->seg_off.as<int64_t>(), p->seg_off.as<int64_t>(), m->nrows, s));
-        int64_t n_segs = 0;
-        CSRK_TRY(stage_d2h(&n_segs, p->seg_off.as<int64_t>() + m->nrows, 8, s));
-        CSRK_HIP(hipStreamSynchronize(s));
-        p->n_segs = n_segs;
-        CSRK_TRY(p->seg_row.alloc((size_t)n_segs * 4));
-        CSRK_TRY(p->seg_part.alloc((size_t)n_segs * 8));
-        if (m->nrows > 0) {
-            vec_fill_kernel<<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(p->seg_off.as<int64_t>(), m->nrows,
-                                                                             p->seg_row.as<int32_t>());
-            CSRK_LAUNCH_CHECK();
-        }
-    }
+    const SpmvKnobs knobs = read_spmv_knobs();      // once per build: the builders read no environment
+    if (p->algo == CSRK_SPMV_MERGE) return build_merge_plan<P>(m, p, knobs, s, allow_split);
+    if (p->algo == CSRK_SPMV_VECTOR) return build_vector_plan<P>(m, p, s);
     return CSRK_OK;
 }
 

@@ -145,7 +145,7 @@ def cut_rows(m, split):
 
 
 def make_rounds(n_tiles, grid, nt):
-    "build_cold_stage's make_rounds: (first tile of every round + [n_tiles], first round of every workgroup + [rounds])"
+    "build_cold_stage's rounds (spmvlayout::stage_rounds in csrc/spmv_layout.h): (first tile of every round + [n_tiles], first round of every workgroup + [rounds])"
     rt0, wr0 = [], []
     for w in range(grid):
         tb, te = n_tiles * w // grid, n_tiles * (w + 1) // grid

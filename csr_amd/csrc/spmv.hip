@@ -33,10 +33,13 @@
 // All kernels accumulate in float64 whatever the storage dtype, like the reference
 // (float32 values are widened on load; structure-only matrices multiply by 1.0,
 // csr/csr.py:254-262).
+//
+// This file: the kernels a product runs; then, from "host side" on, the steps that launch them (what DECIDES a launch is
+// plain arithmetic in spmv_launch.h, as what decides a plan's layout is in spmv_layout.h; the plan is built in
+// spmv_plan.hip); then the C ABI.
 #include "spmv_plan.h"
 
 #include <algorithm>
-#include <ctime>
 
 namespace csrk {
 // R32: float32 values times a float32 vector.  Numba types the reference's loop by its operands (csr/kernels/numba/
@@ -733,26 +736,7 @@ __global__ __launch_bounds__(PT) void spmv_acc_kernel(const AccLaunchArgs L, con
 // carry rows behind the partials and the listed rest loaded a row at a time by the whole wavefront; 5 us is the floor of a
 // launch that only scatters.  Measured and left out (profiles/r06_experiments.json): sixteen partials in flight per lane,
 // row ids and carry ends requested at the top, G = 16 for tier 0 (25 us), 256-thread workgroups (12.5).
-struct EpiJob {
-    int32_t kind, blocks;      // 0 = fix, 1 = reduce
-    // fix
-    const int32_t *carry_row;
-    const double *carry_val;
-    int64_t n;
-    double *fy;
-    // reduce
-    const double *partial;
-    const int32_t *row_list;
-    int32_t H, n_wg, G;
-    int32_t extra;                  // rows of partial[] behind the n_wg: added last, in order (tier 1's carry rows, Panel::ncs)
-    const int32_t *crp, *cidx;      // optional (nullptr: no listed carries to add)
-    const double *cval;
-};
-struct EpiJobs {
-    EpiJob j[6];
-    int32_t n;
-};
-constexpr int EPI_THREADS = 1024;
+// (EpiJob, EpiJobs, EPI_THREADS and the functions that make the jobs: spmv_launch.h)
 
 __global__ __launch_bounds__(EPI_THREADS) void spmv_epilogue_kernel(EpiJobs jobs, double *__restrict__ y)
 {
@@ -841,7 +825,7 @@ __global__ __launch_bounds__(EPI_THREADS) void spmv_epilogue_kernel(EpiJobs jobs
 // LS_RND24 = LS_RND with the index words stored in 3 bytes (LightStream::idx24): per tile a 16-bit plane (a lane's eight
 // low halves: one 16-B load) and an 8-bit plane (its eight high bytes: one 8-B load) -- 11 B per entry instead of 12; the
 // kernel's time follows its bytes (2 B per entry less, ablated: 161 -> 151 us).
-constexpr int LS_PLAIN = 0, LS_RND = 2, LS_RND24 = 3;
+// (LS_PLAIN, LS_RND, LS_RND24: spmv_launch.h, with the function that picks the form a plan runs)
 template <int MODE, bool DENSE = false, bool R32 = false, class SV = double>
 __global__ __launch_bounds__(LS_THREADS) void spmv_lstream_kernel(
     const SV *__restrict__ svals, const uint32_t *__restrict__ sidx, const int32_t *__restrict__ rowids,
@@ -1292,56 +1276,89 @@ __global__ __launch_bounds__(LS_STAGE_THREADS) void ls_stage_kernel(const XT *__
     }
 }
 
+// ---- host side ----------------------------------------------------------------------------------
+// One product = the steps of DESIGN.md section 4, "The launch side", in its order.  What DECIDES a launch -- the split, the
+// algorithm and its parts, the light stream's form, tier 0's launches, the rider, the epilogue's jobs -- is plain arithmetic
+// in spmv_launch.h (checked on the host: tests/spmv_launch_host); here are the launches.  The steps that read the plan's
+// private streams are templates over R32 and the type of x alone; the row-pointer width and the value type reach only the
+// kernels that read the CSR arrays (launch_raw).
+using namespace spmvlaunch;
+
+template <class T> struct TypeTag {
+    using type = T;
+};
+
+// Which instantiation serves a form.  The launches and spmv_kernel_attributes both come here: visit(kernel, ...) is called
+// with the kernel of `form`, or, without a form, with every kernel a launch can reach.
+template <int MODE, bool R32, class Visit> static void ls_kernels_of_mode(const LsForm *form, Visit &visit)
+{
+    auto serves = [form](bool dense, bool f32) { return !form || (form->mode == MODE && form->dense == dense && form->f32 == f32); };
+    if (serves(false, false)) visit(spmv_lstream_kernel<MODE, false, R32, double>, TypeTag<double>());
+    if (serves(true, false)) visit(spmv_lstream_kernel<MODE, true, R32, double>, TypeTag<double>());
+    if (serves(false, true)) visit(spmv_lstream_kernel<MODE, false, R32, float>, TypeTag<float>());
+    if (serves(true, true)) visit(spmv_lstream_kernel<MODE, true, R32, float>, TypeTag<float>());
+}
+template <bool R32, class Visit> static void ls_kernels(const LsForm *form, Visit &&visit)
+{
+    ls_kernels_of_mode<LS_PLAIN, R32>(form, visit);
+    ls_kernels_of_mode<LS_RND, R32>(form, visit);
+    ls_kernels_of_mode<LS_RND24, R32>(form, visit);
+}
+template <bool R32, class XT, class Visit> static void acc_kernels(const AccForm *form, Visit &&visit)
+{
+    if (!form || *form == ACC_F32) visit(spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, float, XT>);
+    if (!form || *form == ACC_NIB) visit(spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, fix56::nib::Bytes, XT>);
+    if (!form || *form == ACC_FIX56) visit(spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, fix56::Packed, XT>);
+    if (!form || *form == ACC_F64) visit(spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, double, XT>);
+}
+
 // the kernels that ask for more dynamic LDS than the default limit allows (per device: the builders call this)
 int spmv_kernel_attributes()
 {
-    for (const void *f : {(const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS>, (const void *)spmv_lstream_kernel<LS_PLAIN>,
-                          (const void *)spmv_lstream_kernel<LS_RND>, (const void *)spmv_lstream_kernel<LS_PLAIN, true>,
-                          (const void *)spmv_lstream_kernel<LS_RND, true>, (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, false, true>, (const void *)spmv_lstream_kernel<LS_RND, false, true>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, true, true>, (const void *)spmv_lstream_kernel<LS_RND, true, true>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, float>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, false, false, float>, (const void *)spmv_lstream_kernel<LS_RND, false, false, float>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, true, false, float>, (const void *)spmv_lstream_kernel<LS_RND, true, false, float>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, false, true, float>, (const void *)spmv_lstream_kernel<LS_RND, false, true, float>,
-                          (const void *)spmv_lstream_kernel<LS_PLAIN, true, true, float>, (const void *)spmv_lstream_kernel<LS_RND, true, true, float>,
-                          (const void *)spmv_lstream_kernel<LS_RND24>, (const void *)spmv_lstream_kernel<LS_RND24, true>,
-                          (const void *)spmv_lstream_kernel<LS_RND24, false, true>, (const void *)spmv_lstream_kernel<LS_RND24, true, true>,
-                          (const void *)spmv_lstream_kernel<LS_RND24, false, false, float>, (const void *)spmv_lstream_kernel<LS_RND24, true, false, float>,
-                          (const void *)spmv_lstream_kernel<LS_RND24, false, true, float>, (const void *)spmv_lstream_kernel<LS_RND24, true, true, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, double, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, double, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, float, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, float, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::Packed, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::Packed, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::nib::Bytes>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::nib::Bytes>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, false, fix56::nib::Bytes, float>,
-                          (const void *)spmv_acc_kernel<ACC_CB, ACC_THREADS, true, fix56::nib::Bytes, float>})
-        CSRK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+    hipError_t set_whole_lds = hipSuccess;      // the first failure
+    auto whole_lds = [&set_whole_lds](auto *kernel, auto...) {
+        if (set_whole_lds != hipSuccess) return;
+        set_whole_lds = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
+    };
+    ls_kernels<false>(nullptr, whole_lds);
+    ls_kernels<true>(nullptr, whole_lds);
+    acc_kernels<false, double>(nullptr, whole_lds);
+    acc_kernels<true, double>(nullptr, whole_lds);
+    acc_kernels<false, float>(nullptr, whole_lds);
+    acc_kernels<true, float>(nullptr, whole_lds);
+    CSRK_HIP(set_whole_lds);
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
     CSRK_HIP(hipFuncSetAttribute((const void *)ls_stage_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LS_STAGE_WMAX * 8)));
     return CSRK_OK;
 }
 
+// the form of the light stream this plan holds: the launch, the float32-x decision and the plan's census all ask here
+static LsForm ls_form_of(const SpmvPlan *p)
+{
+    const LightStream &ls = p->ls;
+    return ls_form(ls.n_cold, ls.round_start.p != nullptr, ls.idx24, ls.dense, ls.f32,
+                   {LS_HOT_LDS, LS_RND_HOT, LS_RND_CAP, LS_THREADS / WAVE, ACC_TILE});
+}
+
 // `launching`: the call is an SpMV launch (counts towards the lazy split), not a query.
 // Caller holds m->mu.
-static int get_plan_locked(Matrix *m, hipStream_t s, SpmvPlan **out, bool launching)
+static int get_plan_locked(Matrix *m, SpmvPlan **out, bool launching)
 {
     if (launching) m->spmv_calls++;
     // The long-row split costs ~25 ms and 2.4 GB on the headline matrix and pays back ~1.4 ms per
     // SpMV, so it is built on the SECOND launch on a handle: the reference's CSR.mult_vec makes a
     // handle per call (csr/csr.py:582) and must not pay for a plan it uses once.  Forcing the split
-    // (CSRK_SPMV_HEAVY_SPLIT=1) or profiling builds it at once.
-    const char *env = getenv("CSRK_SPMV_HEAVY_SPLIT"), *env_hot = getenv("CSRK_SPMV_HOT"), *env_ls = getenv("CSRK_SPMV_STREAM");
-    const bool eager = (env && env[0] == '1') || (env_hot && env_hot[0] == '1') || (env_ls && env_ls[0] == '1') || !launching;
-    const bool want_split = eager || m->spmv_calls >= 2;
-    if (m->spmv_plan && !m->spmv_plan->split_considered && want_split && m->spmv_plan->algo == CSRK_SPMV_MERGE &&
-        !m->spmv_plan->profiling) {
+    // (CSRK_SPMV_HEAVY_SPLIT=1) or profiling builds it at once.  The knobs are read only while that
+    // is undecided: a product on a final plan reads no environment.
+    const SpmvPlan *old = m->spmv_plan;
+    const bool considered = old && old->split_considered, profiling = old && old->profiling;
+    const int old_algo = old ? old->algo : CSRK_SPMV_MERGE;
+    if (!split_open(old != nullptr, considered, old_algo, profiling)) {
+        *out = m->spmv_plan;
+        return CSRK_OK;
+    }
+    const bool want_split = split_wanted(split_forced(read_spmv_knobs()), launching, m->spmv_calls);
+    if (plan_needs_rebuild(old != nullptr, considered, want_split, old_algo, profiling)) {
         if (hipDeviceSynchronize() != hipSuccess) {
             set_error("device synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
             return CSRK_ERR_HIP;
@@ -1353,9 +1370,8 @@ static int get_plan_locked(Matrix *m, hipStream_t s, SpmvPlan **out, bool launch
         SpmvPlan *p = new (std::nothrow) SpmvPlan();
         CSRK_REQUIRE(p, "out of host memory");
         p->algo = m->spmv_algo == CSRK_SPMV_AUTO ? CSRK_SPMV_MERGE : m->spmv_algo;
-        // Plans are built on the default stream and completed before use: their temporaries come from
-        // the caching allocator, whose recycling is safe only in default-stream order.
-        (void)s;
+        // Plans are built on the default stream, whatever stream the product runs on, and completed before use: their
+        // temporaries come from the caching allocator, whose recycling is safe only in default-stream order.
         int rc = build_spmv_plan(m, p, want_split);
         if (rc == CSRK_OK && hipDeviceSynchronize() != hipSuccess) {
             set_error("SpMV plan construction failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1371,287 +1387,271 @@ static int get_plan_locked(Matrix *m, hipStream_t s, SpmvPlan **out, bool launch
     return CSRK_OK;
 }
 
-static int get_plan(Matrix *m, hipStream_t s, SpmvPlan **out)
+static int get_plan(Matrix *m, SpmvPlan **out)
 {
     std::lock_guard<std::mutex> lk(m->mu);
-    return get_plan_locked(m, s, out, false);
+    return get_plan_locked(m, out, false);
 }
 
+// ---- the steps of a product under the merge algorithm, in the order run_merge takes them ---------------------------------
 // XT = float: the caller's x is float32 and the plan serves every row without the raw-array kernels (spmv_dispatch checks)
-template <class P, int VT, bool R32 = false, class XT = double>
-static int launch_spmv(Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipStream_t s, int part)
+
+// Cold staging (ls_stage_kernel) fills xg and the pack.
+template <class XT> static int stage_cold_x(const Matrix *m, SpmvPlan *p, const XT *d_x, hipStream_t s)
 {
-    constexpr bool X64 = sizeof(XT) == 8;
-    const P *rp = (const P *)m->d_rowptrs;
-    if (m->nrows == 0) return CSRK_OK;
-    int algo = p->algo;
-    if (algo == CSRK_SPMV_MERGE && m->nnz < 2) algo = CSRK_SPMV_SCALAR;   // the tile kernel's pair loads need >= 2 entries
-    // part (csrk_spmv_device_part): bit 0 = the rows of the row-major path (every row gets a value: the rows cut out
-    // for the tiers get 0.0), bit 1 = the tiers' rows (their reduces overwrite those zeros).  1 then 2 = 3.
-    const bool do_light = (part & 1) != 0, do_heavy = (part & 2) != 0;
-    if (algo != CSRK_SPMV_MERGE && !do_light) return CSRK_OK;      // no tiers outside the merge algorithm
-    switch (algo) {
-    case CSRK_SPMV_MERGE: {
-        // epilogue jobs, one launch at the end
-        EpiJobs epi;
-        epi.n = 0;
-        auto flush_epi = [&]() -> int {
-            if (epi.n == 0) return CSRK_OK;
-            unsigned g = 0;
-            for (int i = 0; i < epi.n; i++) g += (unsigned)epi.j[i].blocks;
-            spmv_epilogue_kernel<<<g, EPI_THREADS, 0, s>>>(epi, d_y);
-            CSRK_LAUNCH_CHECK();
-            epi.n = 0;
-            return CSRK_OK;
-        };
-        auto add_fix = [&](const int32_t *cr, const double *cv, int64_t n, double *yy) -> int {
-            if (n <= 0) return CSRK_OK;
-            if (epi.n == 6) CSRK_TRY(flush_epi());
-            EpiJob J = {};
-            J.kind = 0;
-            J.blocks = (int32_t)ceil_div(n, EPI_THREADS);
-            J.carry_row = cr;
-            J.carry_val = cv;
-            J.n = n;
-            J.fy = yy;
-            epi.j[epi.n++] = J;
-            return CSRK_OK;
-        };
-        auto add_red = [&](const double *part, const int32_t *rows, int32_t H, int32_t n_wg, int G, const int32_t *crp,
-                           const int32_t *cidx, const double *cval, int32_t extra = 0) -> int {
-            if (H <= 0) return CSRK_OK;
-            if (epi.n == 6) CSRK_TRY(flush_epi());
-            EpiJob J = {};
-            J.kind = 1;
-            J.blocks = (int32_t)ceil_div(H, WAVE * (EPI_THREADS / WAVE / G));
-            J.partial = part;
-            J.row_list = rows;
-            J.H = H;
-            J.n_wg = n_wg;
-            J.G = G;
-            J.extra = extra;
-            J.crp = crp;
-            J.cidx = cidx;
-            J.cval = cval;
-            epi.j[epi.n++] = J;
-            return CSRK_OK;
-        };
-        // cold staging (ls_stage_kernel) fills xg and the pack; it runs first, so that the x it has just read is still in
-        // the Infinity Cache when the accumulator kernel fetches its windows
-        if (do_light && p->ls.on && p->ls.n_cold) {
-            KernelTimer ks(p, s, 3);
-            const unsigned gs = (unsigned)(ceil_div(p->ls.n_stage_blk, 8) * 8);
-            ls_stage_kernel<XT><<<gs, LS_STAGE_THREADS, (size_t)p->ls.stage_w * 8, s>>>(
-                d_x, m->ncols, p->ls.stage_w, p->ls.a_col.as<uint16_t>(), p->ls.a_dst.as<int32_t>(),
-                p->ls.blk_start.as<int32_t>(), p->ls.n_stage_blk, p->ls.xg.as<double>());
-            ks.stop();
-            CSRK_LAUNCH_CHECK();
-        }
-        if (do_light && p->n_hot && !(p->ls.on && p->ls.n_cold)) {      // (with cold staging the pack is filled by ls_stage_kernel)
-            hot_pack_kernel<XT><<<(unsigned)ceil_div(p->n_hot, 256), 256, 0, s>>>(d_x, p->hot_cols.as<int32_t>(), p->n_hot,
-                                                                            p->xh.as<double>());
-            CSRK_LAUNCH_CHECK();
-        }
-        bool t0_rides = false;      // tier 0's reduce ran inside the pair kernel's launch: the epilogue only scatters its sums
-        if (do_heavy && p->n_heavy && !p->acc.empty()) {        // tier 0, accumulator form
-            KernelTimer kh(p, s, 1);
-            for (size_t a0 = 0; a0 < p->acc.size(); a0 += (size_t)p->acc[a0]->launch_groups) {
-                // one launch: the group p->acc[a0] and those that run side by side with it (build_acc_groups)
-                AccPanel *ap = p->acc[a0];
-                const int gb = ap->launch_groups;
-                if (gb < 1 || gb > accgroups::MAX_GROUPS || a0 + (size_t)gb > p->acc.size()) {
-                    set_error("internal: tier 0's groups and launches disagree");
-                    return CSRK_ERR_INVALID;
-                }
-                AccLaunchArgs L = {};
-                size_t lds = 0;
-                for (int g = 0; g < gb; g++) {
-                    const AccPanel *aq = p->acc[a0 + (size_t)g];
-                    L.g[g] = {aq->vals.p, aq->idx.as<uint16_t>(), aq->tile_row0.as<int32_t>(), aq->segs.as<AccSeg>(),
-                              aq->wg_seg.as<int32_t>(), aq->partial.as<double>(), aq->nrow, aq->n_wg, aq->fx_g, 0};
-                    lds = aq->lds > lds ? aq->lds : lds;
-                }
-                L.wg_map = gb > 1 ? ap->wg_map.as<uint32_t>() : nullptr;
-                const unsigned n_blocks = (unsigned)(gb > 1 ? ap->launch_wgs : ap->n_wg);
-#define ACC_LAUNCH(SV) spmv_acc_kernel<ACC_CB, ACC_THREADS, R32, SV, XT><<<n_blocks, ACC_THREADS, lds, s>>>(L, d_x, m->ncols)
-                if (ap->f32) ACC_LAUNCH(float);
-                else if (ap->nib) ACC_LAUNCH(fix56::nib::Bytes);
-                else if (ap->fix56) ACC_LAUNCH(fix56::Packed);
-                else ACC_LAUNCH(double);
-#undef ACC_LAUNCH
-                CSRK_LAUNCH_CHECK();
-            }
-            kh.stop();
-        }
-        if (do_heavy && p->n_heavy && p->tier1.on) {            // tier 1, pair form
-            Panel *pn = &p->tier1;
-            KernelTimer kh(p, s, 2);
-#define PANEL_ARGS(PP)                                                                                              \
-    pn->rp.as<PP>(), pn->ci.as<int32_t>(), pn->vs.as<double>(), d_x, m->ncols, pn->y.as<double>(),                    \
-        pn->tile.as<PanelTile>(), pn->group.as<PanelGroup>(), pn->rows, pn->carry_row.as<int32_t>(),                  \
-        pn->carry_val.as<double>(), pn->nnz, pn->cb, rider
-            PanelRider rider = {};
-            rider.first = pn->groups;
-            for (int q = 0; q < accgroups::MAX_GROUPS; q++) rider.start[q] = INT32_MAX;
-            int64_t rider_wgs = 0;
-            // (tier 0 is one launch: its groups, side by side, ride one behind the other)
-            if (PANEL_T1 / WAVE == 4 && do_heavy && !p->acc.empty() && (size_t)p->acc[0]->launch_groups == p->acc.size() &&
-                p->acc.size() <= (size_t)accgroups::MAX_GROUPS && p->acc[0]->z.p) {
-                for (size_t q = 0; q < p->acc.size(); q++) {
-                    AccPanel *ap = p->acc[q];
-                    rider.partial[q] = ap->partial.as<double>();
-                    rider.z[q] = ap->z.as<double>();
-                    rider.H[q] = ap->nrow;
-                    rider.n_wg[q] = ap->n_wg;
-                    rider.start[q] = (int32_t)rider_wgs;
-                    rider_wgs += ceil_div(ap->nrow, WAVE);
-                }
-                t0_rides = true;
-            }
-            const unsigned grid = (unsigned)(pn->groups + rider_wgs);
-            if (pn->p64) spmv_panel_kernel<int64_t, PANEL_T1, R32, XT><<<grid, PANEL_T1, 0, s>>>(PANEL_ARGS(int64_t));
-            else spmv_panel_kernel<int32_t, PANEL_T1, R32, XT><<<grid, PANEL_T1, 0, s>>>(PANEL_ARGS(int32_t));
-#undef PANEL_ARGS
-            kh.stop();
-            CSRK_LAUNCH_CHECK();
-            // (the pair kernel's carries are added by the tier's reduce: Panel::crp)
-        }
-        if (do_light) {
-#define MERGE_ARGS_LIGHT(CI)                                                                                        \
-    p->rp_light.as<P>(), CI, m->d_values, d_x, d_y, p->tile_row.as<int32_t>(), m->nrows, p->nnz_light,                \
-        p->carry_row.as<int32_t>(), p->carry_val.as<double>(), p->tile_cut.as<int32_t>(), p->cut_pos.as<int64_t>(),  \
-        p->cut_cum.as<int64_t>(), m->nnz
-#define MERGE_ARGS_FULL(CI)                                                                                         \
-    rp, CI, m->d_values, d_x, d_y, p->tile_row.as<int32_t>(), m->nrows, m->nnz, p->carry_row.as<int32_t>(),          \
-        p->carry_val.as<double>(), nullptr, nullptr, nullptr, m->nnz
-            const unsigned grid = (unsigned)p->n_tiles;
-            if (p->ls.on) {
-                KernelTimer kl(p, s);
-                constexpr size_t ls_lds = ((size_t)LS_HOT_LDS + (size_t)(LS_THREADS / WAVE) * (ACC_TILE + 2)) * 8;
-                const double *x_cold = X64 ? (const double *)(const void *)d_x : nullptr, *x_pack = p->xh.as<double>();      // (float x: cold staging is on, spmv_dispatch checks)
-                if (p->ls.n_cold) {      // cold staging: the unpacked columns' x values, in the stream's order
-                    x_cold = p->ls.xg.as<double>();
-                    x_pack = x_cold + p->ls.n_cold;
-                }
-#define LS_ARGS(SV)                                                                                                   \
-    p->ls.vals.as<SV>(), p->ls.idx.as<uint32_t>(), p->ls.rowids.as<int32_t>(), p->ls.tile_base.as<int32_t>(),          \
-        x_cold, x_pack, p->n_hot_lds, p->ls.n_tiles, p->ls.n_runs, p->ls.n_out, d_y,         \
-        p->ls.carry_row.as<int32_t>(), p->ls.carry_val.as<double>()
-                constexpr size_t rnd_lds = ((size_t)LS_RND_HOT + LS_RND_CAP + (size_t)(LS_THREADS / WAVE) * (ACC_TILE + 2)) * 8;
-                const int32_t *nil = nullptr;
-#define LS_GO(D, SV)                                                                                                   \
-    do {                                                                                                               \
-        if (p->ls.n_cold && p->ls.round_start.p && p->ls.idx24)                                                        \
-            spmv_lstream_kernel<LS_RND24, D, R32, SV><<<p->ls.grid, LS_THREADS, rnd_lds, s>>>(                         \
-                LS_ARGS(SV), p->ls.round_start.as<int32_t>(), p->ls.round_tile0.as<int32_t>(),                         \
-                p->ls.wg_round0.as<int32_t>());                                                                        \
-        else if (p->ls.n_cold && p->ls.round_start.p)                                                                  \
-            spmv_lstream_kernel<LS_RND, D, R32, SV><<<p->ls.grid, LS_THREADS, rnd_lds, s>>>(                           \
-                LS_ARGS(SV), p->ls.round_start.as<int32_t>(), p->ls.round_tile0.as<int32_t>(),                         \
-                p->ls.wg_round0.as<int32_t>());                                                                        \
-        else                                                                                                           \
-            spmv_lstream_kernel<LS_PLAIN, D, R32, SV><<<p->ls.grid, LS_THREADS, ls_lds, s>>>(LS_ARGS(SV), nil, nil, nil); \
-    } while (0)
-                if (p->ls.f32) {
-                    if (p->ls.dense) LS_GO(true, float);
-                    else LS_GO(false, float);
-                } else {
-                    if (p->ls.dense) LS_GO(true, double);
-                    else LS_GO(false, double);
-                }
-#undef LS_GO
-#undef LS_ARGS
-                kl.stop();
-                CSRK_LAUNCH_CHECK();
-                if (p->n_heavy) {
-                    CSRK_TRY(add_fix(p->ls.carry_row.as<int32_t>(), p->ls.carry_val.as<double>(), p->ls.n_tiles, d_y));
-                } else {
-                    spmv_merge_fixup_kernel<<<(unsigned)ceil_div(p->ls.n_tiles * WAVE, 256), 256, 0, s>>>(
-                        p->ls.carry_row.as<int32_t>(), p->ls.carry_val.as<double>(), p->ls.n_tiles, d_y);
-                    CSRK_LAUNCH_CHECK();
-                }
-            } else if constexpr (X64) {
-            KernelTimer kt(p, s);
-            if (p->n_heavy)
-                spmv_merge_kernel<P, VT, true, R32><<<grid, MERGE_THREADS, 0, s>>>(MERGE_ARGS_LIGHT(m->d_colinds));
-            else
-                spmv_merge_kernel<P, VT, false, R32><<<grid, MERGE_THREADS, 0, s>>>(MERGE_ARGS_FULL(m->d_colinds));
-            kt.stop();
-            CSRK_LAUNCH_CHECK();
-            if (p->n_heavy)
-                spmv_merge_fixup_short_kernel<<<(unsigned)ceil_div(p->n_tiles, 256), 256, 0, s>>>(
-                    p->carry_row.as<int32_t>(), p->carry_val.as<double>(), p->n_tiles, d_y);
-            else
-                spmv_merge_fixup_kernel<<<(unsigned)ceil_div(p->n_tiles * WAVE, 256), 256, 0, s>>>(
-                    p->carry_row.as<int32_t>(), p->carry_val.as<double>(), p->n_tiles, d_y);
-            CSRK_LAUNCH_CHECK();
-            } else {
-                set_error("internal: a float32 vector reached the raw-array kernels");
-                return CSRK_ERR_INVALID;
-            }
-#undef MERGE_ARGS_LIGHT
-#undef MERGE_ARGS_FULL
-        }
-        if (do_heavy && p->n_heavy && !p->acc.empty() && t0_rides) {
-            for (AccPanel *ap : p->acc) {
-                if (epi.n == 6) CSRK_TRY(flush_epi());
-                EpiJob J = {};
-                J.kind = 2;
-                J.blocks = (int32_t)ceil_div(ap->nrow, EPI_THREADS);
-                J.partial = ap->z.as<double>();
-                J.row_list = ap->row_list.as<int32_t>();
-                J.H = ap->nrow;
-                epi.j[epi.n++] = J;
-            }
-        } else if (do_heavy && p->n_heavy && !p->acc.empty())
-            for (AccPanel *ap : p->acc)
-                CSRK_TRY(add_red(ap->partial.as<double>(), ap->row_list.as<int32_t>(), ap->nrow, ap->n_wg, 4, nullptr, nullptr, nullptr));
-        if (do_heavy && p->n_heavy && p->tier1.on) {
-            // y[row] = sum over column blocks of the (block, row) partials, in block order, then the row's listed carries
-            Panel *pn = &p->tier1;
-            CSRK_TRY(add_red(pn->y.as<double>(), pn->row_list.as<int32_t>(), pn->nrow, pn->nb, pn->nb > 64 ? 4 : 2,
-                             pn->crp.as<int32_t>(), pn->cidx.as<int32_t>(), pn->carry_val.as<double>(), pn->ncs));
-        }
-        CSRK_TRY(flush_epi());      // the light stream's carries and the ordered reduces of the tiers, one launch
-        break;
-    }
-    case CSRK_SPMV_VECTOR: {
-        if constexpr (!X64) {
-            set_error("internal: a float32 vector reached the raw-array kernels");
+    const LightStream &ls = p->ls;
+    KernelTimer ks(p, s, 3);
+    const unsigned gs = (unsigned)(ceil_div(ls.n_stage_blk, 8) * 8);
+    ls_stage_kernel<XT><<<gs, LS_STAGE_THREADS, (size_t)ls.stage_w * 8, s>>>(d_x, m->ncols, ls.stage_w, ls.a_col.as<uint16_t>(),
+                                                                           ls.a_dst.as<int32_t>(), ls.blk_start.as<int32_t>(),
+                                                                           ls.n_stage_blk, ls.xg.as<double>());
+    ks.stop();
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the pack, when no copy pass fills it
+template <class XT> static int pack_hot_x(SpmvPlan *p, const XT *d_x, hipStream_t s)
+{
+    hot_pack_kernel<XT><<<(unsigned)ceil_div(p->n_hot, 256), 256, 0, s>>>(d_x, p->hot_cols.as<int32_t>(), p->n_hot, p->xh.as<double>());
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// tier 0, accumulator form: one launch per group, or per set of groups that run side by side (build_acc_groups)
+template <bool R32, class XT> static int launch_tier0(const Matrix *m, SpmvPlan *p, const XT *d_x, hipStream_t s)
+{
+    KernelTimer kh(p, s, 1);
+    int gb = 0;
+    for (size_t a0 = 0; a0 < p->acc.size(); a0 += (size_t)gb) {
+        const AccPanel *ap = p->acc[a0];
+        if (!acc_launch_count(a0, ap->launch_groups, p->acc.size(), &gb)) {
+            set_error("internal: tier 0's groups and launches disagree");
             return CSRK_ERR_INVALID;
-        } else
-        if (p->n_segs > 0) {
-            KernelTimer kt(p, s);
-            spmv_vector_kernel<P, VT><<<(unsigned)ceil_div(p->n_segs * WAVE, 256), 256, 0, s>>>(
-                rp, m->d_colinds, m->d_values, d_x, d_y, p->seg_off.as<int64_t>(), p->seg_row.as<int32_t>(),
-                p->n_segs, p->seg_part.as<double>());
-            kt.stop();
-            CSRK_LAUNCH_CHECK();
-            spmv_vector_fixup_kernel<<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(
-                p->seg_off.as<int64_t>(), m->nrows, p->seg_part.as<double>(), d_y);
-            CSRK_LAUNCH_CHECK();
         }
-        break;
-    }
-    case CSRK_SPMV_SCALAR: {
-        if constexpr (!X64) {
-            set_error("internal: a float32 vector reached the raw-array kernels");
-            return CSRK_ERR_INVALID;
-        } else {
-        KernelTimer kt(p, s);
-        // (R32: a float32 matrix of fewer than two entries under the merge algorithm lands here with its float32 products)
-        spmv_scalar_kernel<P, VT, R32><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(rp, m->d_colinds, m->d_values, d_x,
-                                                                                  d_y, m->nrows);
-        kt.stop();
+        AccLaunchArgs L = {};
+        size_t lds[MAX_GROUPS];
+        for (int g = 0; g < gb; g++) {
+            const AccPanel *aq = p->acc[a0 + (size_t)g];
+            L.g[g] = {aq->vals.p, aq->idx.as<uint16_t>(), aq->tile_row0.as<int32_t>(), aq->segs.as<AccSeg>(),
+                      aq->wg_seg.as<int32_t>(), aq->partial.as<double>(), aq->nrow, aq->n_wg, aq->fx_g, 0};
+            lds[g] = aq->lds;
+        }
+        const AccLaunch al = acc_launch(gb, ap->launch_wgs, ap->n_wg, lds);
+        L.wg_map = al.mapped ? ap->wg_map.as<uint32_t>() : nullptr;
+        const AccForm form = acc_form(ap->f32, ap->nib, ap->fix56);
+        acc_kernels<R32, XT>(&form, [&](auto *kernel) { kernel<<<al.blocks, ACC_THREADS, al.lds, s>>>(L, d_x, m->ncols); });
         CSRK_LAUNCH_CHECK();
-        }
-        break;
     }
-    default:
-        set_error("unknown spmv algo %d", p->algo);
-        return CSRK_ERR_INVALID;
+    kh.stop();
+    return CSRK_OK;
+}
+
+// whether tier 0's reduce rides in the pair kernel's launch: the epilogue then only scatters its sums
+static bool tier0_rides(const SpmvPlan *p)
+{
+    return !p->acc.empty() && t0_rides(PANEL_T1 / WAVE, p->acc.size(), p->acc[0]->launch_groups, p->acc[0]->z.p != nullptr);
+}
+
+// tier 1, pair form (the pair kernel's carries are added by the tier's reduce: Panel::crp)
+template <bool R32, class XT> static int launch_tier1(const Matrix *m, SpmvPlan *p, const XT *d_x, hipStream_t s, bool rides)
+{
+    const Panel *pn = &p->tier1;
+    KernelTimer kh(p, s, 2);
+    PanelRider rider = {};
+    rider.first = pn->groups;
+    // (tier 0 is one launch: its groups, side by side, ride one behind the other)
+    const int n_ride = rides ? (int)p->acc.size() : 0;
+    int32_t rows[MAX_GROUPS] = {};
+    for (int q = 0; q < n_ride; q++) {
+        const AccPanel *ap = p->acc[(size_t)q];
+        rider.partial[q] = ap->partial.as<double>();
+        rider.z[q] = ap->z.as<double>();
+        rider.H[q] = rows[q] = ap->nrow;
+        rider.n_wg[q] = ap->n_wg;
+    }
+    const RiderBlocks rb = rider_blocks(rows, n_ride);
+    for (int q = 0; q < MAX_GROUPS; q++) rider.start[q] = rb.start[q];
+    const unsigned grid = pair_grid(pn->groups, rb.total);
+    auto go = [&](auto row_pointer) {
+        using PP = typename decltype(row_pointer)::type;
+        spmv_panel_kernel<PP, PANEL_T1, R32, XT><<<grid, PANEL_T1, 0, s>>>(
+            pn->rp.as<PP>(), pn->ci.as<int32_t>(), pn->vs.as<double>(), d_x, m->ncols, pn->y.as<double>(), pn->tile.as<PanelTile>(),
+            pn->group.as<PanelGroup>(), pn->rows, pn->carry_row.as<int32_t>(), pn->carry_val.as<double>(), pn->nnz, pn->cb, rider);
+    };
+    if (pn->p64) go(TypeTag<int64_t>());
+    else go(TypeTag<int32_t>());
+    kh.stop();
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// The light stream in the plan's form.  x: the caller's float64 x, for the form that gathers from it (nullptr with a float32
+// x: cold staging is then on, spmv_dispatch checks).  With rows cut out its carries are added by the epilogue.
+template <bool R32> static int launch_light_stream(SpmvPlan *p, const double *x, double *d_y, hipStream_t s)
+{
+    const LightStream &ls = p->ls;
+    const LsForm form = ls_form_of(p);
+    const LsBases at = ls_bases(form, ls.n_cold, x, ls.xg.as<double>(), p->xh.as<double>());
+    const bool rounds = form.mode != LS_PLAIN;
+    const int32_t *round_start = rounds ? ls.round_start.as<int32_t>() : nullptr;
+    const int32_t *round_tile0 = rounds ? ls.round_tile0.as<int32_t>() : nullptr;
+    const int32_t *wg_round0 = rounds ? ls.wg_round0.as<int32_t>() : nullptr;
+    KernelTimer kl(p, s);
+    ls_kernels<R32>(&form, [&](auto *kernel, auto value) {
+        using SV = typename decltype(value)::type;
+        kernel<<<ls.grid, LS_THREADS, form.lds, s>>>(ls.vals.as<SV>(), ls.idx.as<uint32_t>(), ls.rowids.as<int32_t>(),
+                                                     ls.tile_base.as<int32_t>(), at.cold, at.pack, p->n_hot_lds, ls.n_tiles, ls.n_runs,
+                                                     ls.n_out, d_y, ls.carry_row.as<int32_t>(), ls.carry_val.as<double>(),
+                                                     round_start, round_tile0, wg_round0);
+    });
+    kl.stop();
+    CSRK_LAUNCH_CHECK();
+    if (!p->n_heavy) {
+        spmv_merge_fixup_kernel<<<(unsigned)ceil_div(ls.n_tiles * WAVE, 256), 256, 0, s>>>(ls.carry_row.as<int32_t>(),
+                                                                                         ls.carry_val.as<double>(), ls.n_tiles, d_y);
+        CSRK_LAUNCH_CHECK();
     }
     return CSRK_OK;
+}
+
+// The light stream's carries and the ordered reduces of the tiers, one launch (per six jobs).
+// y[row] of tier 1 = sum over column blocks of the (block, row) partials, in block order, then the row's listed carries.
+static int launch_epilogue(SpmvPlan *p, double *d_y, hipStream_t s, bool fix_light, bool tiers, bool rides)
+{
+    const LightStream &ls = p->ls;
+    const Panel &t1 = p->tier1;
+    const EpiJob fix = epi_fix(ls.carry_row.as<int32_t>(), ls.carry_val.as<double>(), ls.n_tiles, d_y);
+    const EpiJob reduce1 = epi_tier1(t1.y.as<double>(), t1.row_list.as<int32_t>(), t1.nrow, t1.nb, t1.crp.as<int32_t>(),
+                                     t1.cidx.as<int32_t>(), t1.carry_val.as<double>(), t1.ncs);
+    auto tier0_job = [p, rides](size_t g) {
+        const AccPanel *ap = p->acc[g];
+        return epi_tier0(rides, ap->partial.as<double>(), ap->z.as<double>(), ap->row_list.as<int32_t>(), ap->nrow, ap->n_wg);
+    };
+    auto launch = [d_y, s](const EpiQueue &q) -> int {
+        spmv_epilogue_kernel<<<q.grid(), EPI_THREADS, 0, s>>>(q.jobs, d_y);
+        CSRK_LAUNCH_CHECK();
+        return CSRK_OK;
+    };
+    return epi_run(fix_light ? &fix : nullptr, tiers ? p->acc.size() : 0, tier0_job, tiers && t1.on ? &reduce1 : nullptr, launch);
+}
+
+// ---- the kernels that read the CSR arrays: the merge-path tiles of a plan without a light stream, vector, scalar ------------
+template <class P, int VT, bool R32> static int launch_raw_tiles(const Matrix *m, SpmvPlan *p, const double *d_x, double *d_y, hipStream_t s)
+{
+    const unsigned grid = (unsigned)p->n_tiles;
+    int32_t *carry_row = p->carry_row.as<int32_t>();
+    double *carry_val = p->carry_val.as<double>();
+    KernelTimer kt(p, s);
+    if (p->n_heavy)      // the light view: the cut rows collapsed to length 0
+        spmv_merge_kernel<P, VT, true, R32><<<grid, MERGE_THREADS, 0, s>>>(
+            p->rp_light.as<P>(), m->d_colinds, m->d_values, d_x, d_y, p->tile_row.as<int32_t>(), m->nrows, p->nnz_light, carry_row,
+            carry_val, p->tile_cut.as<int32_t>(), p->cut_pos.as<int64_t>(), p->cut_cum.as<int64_t>(), m->nnz);
+    else
+        spmv_merge_kernel<P, VT, false, R32><<<grid, MERGE_THREADS, 0, s>>>(
+            (const P *)m->d_rowptrs, m->d_colinds, m->d_values, d_x, d_y, p->tile_row.as<int32_t>(), m->nrows, m->nnz, carry_row,
+            carry_val, nullptr, nullptr, nullptr, m->nnz);
+    kt.stop();
+    CSRK_LAUNCH_CHECK();
+    if (p->n_heavy)
+        spmv_merge_fixup_short_kernel<<<(unsigned)ceil_div(p->n_tiles, 256), 256, 0, s>>>(carry_row, carry_val, p->n_tiles, d_y);
+    else
+        spmv_merge_fixup_kernel<<<(unsigned)ceil_div(p->n_tiles * WAVE, 256), 256, 0, s>>>(carry_row, carry_val, p->n_tiles, d_y);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+template <class P, int VT> static int launch_vector(const Matrix *m, SpmvPlan *p, const double *d_x, double *d_y, hipStream_t s)
+{
+    if (p->n_segs <= 0) return CSRK_OK;
+    KernelTimer kt(p, s);
+    spmv_vector_kernel<P, VT><<<(unsigned)ceil_div(p->n_segs * WAVE, 256), 256, 0, s>>>(
+        (const P *)m->d_rowptrs, m->d_colinds, m->d_values, d_x, d_y, p->seg_off.as<int64_t>(), p->seg_row.as<int32_t>(), p->n_segs,
+        p->seg_part.as<double>());
+    kt.stop();
+    CSRK_LAUNCH_CHECK();
+    spmv_vector_fixup_kernel<<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(p->seg_off.as<int64_t>(), m->nrows,
+                                                                               p->seg_part.as<double>(), d_y);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// (R32: a float32 matrix of fewer than two entries under the merge algorithm lands here with its float32 products)
+template <class P, int VT, bool R32> static int launch_scalar(const Matrix *m, SpmvPlan *p, const double *d_x, double *d_y, hipStream_t s)
+{
+    KernelTimer kt(p, s);
+    spmv_scalar_kernel<P, VT, R32><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>((const P *)m->d_rowptrs, m->d_colinds,
+                                                                                     m->d_values, d_x, d_y, m->nrows);
+    kt.stop();
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// The file's one ladder over the CSR arrays' types: f(row-pointer tag, value type).  R32 (float32 products) names float32
+// values only, so it adds no kernel the other arm does not have in float64 products.
+template <bool R32, class F> static int with_csr_types(const Matrix *m, F &&f)
+{
+    using F64 = std::integral_constant<int, CSRK_VAL_F64>;
+    using F32 = std::integral_constant<int, CSRK_VAL_F32>;
+    using NONE = std::integral_constant<int, CSRK_VAL_NONE>;
+    if constexpr (R32) {
+        return m->ptr64 ? f(TypeTag<int64_t>(), F32()) : f(TypeTag<int32_t>(), F32());
+    } else {
+        if (m->val_type == CSRK_VAL_F64) return m->ptr64 ? f(TypeTag<int64_t>(), F64()) : f(TypeTag<int32_t>(), F64());
+        if (m->val_type == CSRK_VAL_F32) return m->ptr64 ? f(TypeTag<int64_t>(), F32()) : f(TypeTag<int32_t>(), F32());
+        return m->ptr64 ? f(TypeTag<int64_t>(), NONE()) : f(TypeTag<int32_t>(), NONE());
+    }
+}
+
+// `algo` on the CSR arrays.  These kernels take a float64 x only: spmv_dispatch widens a float32 one before it comes here.
+template <bool R32, class XT>
+static int launch_raw(const Matrix *m, SpmvPlan *p, int algo, const XT *d_x, double *d_y, hipStream_t s)
+{
+    if constexpr (!std::is_same<XT, double>::value) {
+        set_error("internal: a float32 vector reached the raw-array kernels");
+        return CSRK_ERR_INVALID;
+    } else {
+        return with_csr_types<R32>(m, [&](auto row_pointer, auto value_type) -> int {
+            using P = typename decltype(row_pointer)::type;
+            constexpr int VT = decltype(value_type)::value;
+            switch (algo) {
+            case CSRK_SPMV_MERGE: return launch_raw_tiles<P, VT, R32>(m, p, d_x, d_y, s);
+            case CSRK_SPMV_VECTOR: return launch_vector<P, VT>(m, p, d_x, d_y, s);
+            case CSRK_SPMV_SCALAR: return launch_scalar<P, VT, R32>(m, p, d_x, d_y, s);
+            default: set_error("unknown spmv algo %d", p->algo); return CSRK_ERR_INVALID;
+            }
+        });
+    }
+}
+
+template <bool R32, class XT> static int run_merge(const Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipStream_t s, int part)
+{
+    const Parts run = parts_of(part);
+    const bool tiers = run.heavy && p->n_heavy, tier0 = tiers && !p->acc.empty(), tier1 = tiers && p->tier1.on;
+    const bool staged = p->ls.on && p->ls.n_cold;
+    // the copy pass runs first, so that the x it has just read is still in the Infinity Cache when the accumulator kernel
+    // fetches its windows
+    if (run.light && staged) CSRK_TRY(stage_cold_x(m, p, d_x, s));
+    if (run.light && p->n_hot && !staged) CSRK_TRY(pack_hot_x(p, d_x, s));      // (with cold staging the pack is filled by the copy pass)
+    if (tier0) CSRK_TRY((launch_tier0<R32>(m, p, d_x, s)));
+    const bool rides = tier1 && tier0_rides(p);
+    if (tier1) CSRK_TRY((launch_tier1<R32>(m, p, d_x, s, rides)));
+    if (run.light && p->ls.on) {
+        const double *x64 = nullptr;
+        if constexpr (std::is_same<XT, double>::value) x64 = d_x;
+        CSRK_TRY(launch_light_stream<R32>(p, x64, d_y, s));
+    } else if (run.light)
+        CSRK_TRY((launch_raw<R32>(m, p, CSRK_SPMV_MERGE, d_x, d_y, s)));
+    return launch_epilogue(p, d_y, s, run.light && p->ls.on && p->n_heavy, tiers, rides);
+}
+
+template <bool R32, class XT> static int launch_spmv(const Matrix *m, SpmvPlan *p, const XT *d_x, double *d_y, hipStream_t s, int part)
+{
+    if (m->nrows == 0) return CSRK_OK;
+    const int algo = effective_algo(p->algo, m->nnz);
+    if (launches_nothing(algo, part)) return CSRK_OK;
+    if (algo == CSRK_SPMV_MERGE) return run_merge<R32>(m, p, d_x, d_y, s, part);
+    return launch_raw<R32>(m, p, algo, d_x, d_y, s);
 }
 
 __global__ void widen_f32_kernel(const float *__restrict__ in, double *__restrict__ out, int64_t n)
@@ -1673,30 +1673,15 @@ static int spmv_dispatch(Matrix *m, const double *d_x, double *d_y, hipStream_t 
     // not overlap in time (same contract as any plan-owning library).
     std::lock_guard<std::mutex> lk(m->mu);
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan_locked(m, s, &p, true));
+    CSRK_TRY(get_plan_locked(m, &p, true));
     if (s) m->used_user_stream = true;
     // every n-th PRODUCT is timed: a product issued in two parts (part 1, then part 2) is one step, so part 2 keeps
     // the decision taken for its part 1 instead of counting as a call of its own
     if (part != 2) p->prof_this = p->profiling && (p->prof_calls++ % (p->prof_every > 0 ? p->prof_every : 1)) == 0;
+    CSRK_REQUIRE(!r32 || (m->val_type == CSRK_VAL_F32 && p->algo == CSRK_SPMV_MERGE), "float32 products need float32 values and the merge algorithm");
+    if (d_x32 && f32x_direct(p->algo, m->nnz, p->ls.on, ls_form_of(p)))
+        return r32 ? launch_spmv<true>(m, p, d_x32, d_y, s, part) : launch_spmv<false>(m, p, d_x32, d_y, s, part);
     if (d_x32) {
-        const bool streams_only = p->algo == CSRK_SPMV_MERGE && m->nnz >= 2 && p->ls.on && p->ls.n_cold > 0 && p->ls.round_start.p;
-        if (streams_only) {
-#define GOF(P, VT, R) return launch_spmv<P, VT, R, float>(m, p, d_x32, d_y, s, part)
-            if (r32) {
-                if (m->ptr64) GOF(int64_t, CSRK_VAL_F32, true);
-                GOF(int32_t, CSRK_VAL_F32, true);
-            }
-            if (m->ptr64) {
-                if (m->val_type == CSRK_VAL_F64) GOF(int64_t, CSRK_VAL_F64, false);
-                if (m->val_type == CSRK_VAL_F32) GOF(int64_t, CSRK_VAL_F32, false);
-                GOF(int64_t, CSRK_VAL_NONE, false);
-            } else {
-                if (m->val_type == CSRK_VAL_F64) GOF(int32_t, CSRK_VAL_F64, false);
-                if (m->val_type == CSRK_VAL_F32) GOF(int32_t, CSRK_VAL_F32, false);
-                GOF(int32_t, CSRK_VAL_NONE, false);
-            }
-#undef GOF
-        }
         CSRK_TRY(p->xwide.ensure((size_t)m->ncols * 8 + 8));
         if (m->ncols) {
             widen_f32_kernel<<<(unsigned)ceil_div(m->ncols, 256), 256, 0, s>>>(d_x32, p->xwide.as<double>(), m->ncols);
@@ -1704,23 +1689,7 @@ static int spmv_dispatch(Matrix *m, const double *d_x, double *d_y, hipStream_t 
         }
         d_x = p->xwide.as<double>();
     }
-#define GO(P, VT) return launch_spmv<P, VT>(m, p, d_x, d_y, s, part)
-    if (r32) {
-        CSRK_REQUIRE(m->val_type == CSRK_VAL_F32 && p->algo == CSRK_SPMV_MERGE, "float32 products need float32 values and the merge algorithm");
-        if (m->ptr64) return launch_spmv<int64_t, CSRK_VAL_F32, true>(m, p, d_x, d_y, s, part);
-        return launch_spmv<int32_t, CSRK_VAL_F32, true>(m, p, d_x, d_y, s, part);
-    }
-    if (m->ptr64) {
-        if (m->val_type == CSRK_VAL_F64) GO(int64_t, CSRK_VAL_F64);
-        if (m->val_type == CSRK_VAL_F32) GO(int64_t, CSRK_VAL_F32);
-        GO(int64_t, CSRK_VAL_NONE);
-    } else {
-        if (m->val_type == CSRK_VAL_F64) GO(int32_t, CSRK_VAL_F64);
-        if (m->val_type == CSRK_VAL_F32) GO(int32_t, CSRK_VAL_F32);
-        GO(int32_t, CSRK_VAL_NONE);
-    }
-#undef GO
-    return CSRK_ERR_INVALID;   // not reached
+    return r32 ? launch_spmv<true>(m, p, d_x, d_y, s, part) : launch_spmv<false>(m, p, d_x, d_y, s, part);
 }
 
 }  // namespace csrk
@@ -1775,7 +1744,7 @@ int csrk_spmv_cut_rows(csrk_handle_t h, int32_t *d_rows, int64_t capacity, int64
     if (!m) return CSRK_ERR_INVALID;
     CSRK_REQUIRE(n_rows, "n_rows is NULL");
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));              // a query: builds the split eagerly
+    CSRK_TRY(get_plan(m, &p));              // a query: builds the split eagerly
     std::lock_guard<std::mutex> lk(m->mu);
     const int64_t n = p->algo == CSRK_SPMV_MERGE ? p->n_heavy : 0;
     *n_rows = n;
@@ -1886,7 +1855,7 @@ int csrk_spmv_profile_begin(csrk_handle_t h, int max_records)
     if (!m) return CSRK_ERR_INVALID;
     CSRK_REQUIRE(max_records > 0 && max_records <= 100000, "max_records out of range");
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));
+    CSRK_TRY(get_plan(m, &p));
     std::lock_guard<std::mutex> lk(m->mu);
     while ((int)p->ev.size() < 8 * max_records) {      // up to four timed kernels per launch
         hipEvent_t e;
@@ -1906,7 +1875,7 @@ int csrk_spmv_profile_every(csrk_handle_t h, int every_n)
     if (!m) return CSRK_ERR_INVALID;
     CSRK_REQUIRE(every_n >= 1, "every_n must be >= 1");
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));
+    CSRK_TRY(get_plan(m, &p));
     std::lock_guard<std::mutex> lk(m->mu);
     p->prof_every = every_n;
     return CSRK_OK;
@@ -1918,7 +1887,7 @@ int csrk_spmv_profile_channels(csrk_handle_t h, int mask)
     if (!m) return CSRK_ERR_INVALID;
     CSRK_REQUIRE(mask > 0 && mask <= 0xf, "mask must name at least one of the four channels");
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));
+    CSRK_TRY(get_plan(m, &p));
     std::lock_guard<std::mutex> lk(m->mu);
     p->prof_mask = mask;
     return CSRK_OK;
@@ -1965,7 +1934,7 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
     if (!m) return CSRK_ERR_INVALID;
     CSRK_REQUIRE(out && n >= 0, "out is NULL");
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));
+    CSRK_TRY(get_plan(m, &p));
     const Panel &t1 = p->tier1;
     // tier 0: [4] tiles, [5] column blocks, [7] block width, [9] rows, [10] entries, [18] 1 (accumulator form)
     // (sums over the tier's groups; every group has the same column blocks)
@@ -1993,11 +1962,11 @@ int csrk_spmv_plan_stats(csrk_handle_t h, int64_t *out, int n)
                            p->ls.round_start.p ? p->ls.stage_tiles : 0,
                            a_wgs, 0, part[0], part[1], part[2], part[3], part[4]};
     for (int i = 0; i < n && i < 34; i++) out[i] = v[i];
-    // the light stream's form (launch_spmv picks the kernel by these): [34] dense layout, [35] 3-byte index words, [36] pack
+    // the light stream's form (spmvlaunch::ls_form picks the kernel by these): [34] dense layout, [35] 3-byte index words, [36] pack
     // slots read from LDS (n_lds as launched), [37] rounds in all and [38] the most one workgroup walks -- staged rounds, or the
     // plain kernel's one tile per wavefront --, [39] column blocks of the copy pass, [40] their width, [41] float32 values
     const LightStream &ls = p->ls;
-    const bool rnd = ls.on && ls.n_cold && ls.round_start.p;
+    const bool rnd = ls.on && ls_form_of(p).mode != LS_PLAIN;
     const int64_t plain_rounds = ls.on ? ceil_div(ls.n_tiles, LS_THREADS / WAVE) : 0;
     const int64_t w[8] = {ls.on && ls.dense ? 1 : 0,
                           ls.on && ls.idx24 ? 1 : 0,
@@ -2030,7 +1999,7 @@ int csrk_spmv_plan_info(csrk_handle_t h, int64_t *n_tiles, int32_t *tile_items)
     Matrix *m = from_handle(h);
     if (!m) return CSRK_ERR_INVALID;
     SpmvPlan *p = nullptr;
-    CSRK_TRY(get_plan(m, nullptr, &p));
+    CSRK_TRY(get_plan(m, &p));
     if (n_tiles) *n_tiles = p->algo == CSRK_SPMV_MERGE ? p->n_tiles : p->n_segs;
     if (tile_items) *tile_items = p->algo == CSRK_SPMV_MERGE ? p->tile_items : VEC_SEG;
     return CSRK_OK;

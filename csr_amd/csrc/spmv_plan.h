@@ -1,7 +1,8 @@
 // Shared between spmv.hip (the kernels a product runs, their launches, the C ABI) and spmv_plan.hip (what is built
 // once per handle: the tiers, the hot-column pack, the light stream and its cold staging): the plan's structures, the
 // tile / stream layout constants and the slot arithmetic both sides must agree on.  (The plain structures the plan kernels
-// read and the host arithmetic that lays a plan out are in spmv_layout.h.)
+// read and the host arithmetic that lays a plan out are in spmv_layout.h; the epilogue's job structures and the host
+// arithmetic that decides a product's launches are in spmv_launch.h.)
 #pragma once
 #include "common.h"
 #include "device_loads.h"
@@ -9,6 +10,7 @@
 #include "fix56.h"
 #include "acc_groups.h"
 #include "spmv_layout.h"
+#include "spmv_launch.h"
 
 #include <type_traits>
 #include <vector>
@@ -519,6 +521,13 @@ constexpr int LS_STAGE_THREADS = 1024, LS_STAGE_IPT = 8;
 
 __device__ __forceinline__ bool ls_is_cold(uint32_t ix) { return !(ix & LS_HOT_BIT) && (ix & LS_COL_MASK) != LS_PAD; }
 
+// what spmv_launch.h (plain host arithmetic: it sees no device header) assumes of the kernels' constants
+static_assert(spmvlaunch::LANES == WAVE && spmvlaunch::MAX_GROUPS == accgroups::MAX_GROUPS, "spmv_launch.h counts wavefronts and groups");
+static_assert(spmvlaunch::ALGO_MERGE == CSRK_SPMV_MERGE && spmvlaunch::ALGO_SCALAR == CSRK_SPMV_SCALAR, "spmv_launch.h names the algorithms");
+static_assert(EPI_THREADS % (4 * WAVE) == 0, "a reduce's G wavefronts per set divide the epilogue's workgroup");
+
+// spmv_plan.hip: every environment variable a plan build looks at, read now (spmv_layout.h: parse_spmv_knobs)
+SpmvKnobs read_spmv_knobs();
 // spmv_plan.hip: build the plan of `m` for p->algo (allow_split: with the long-row split, the pack and the streams --
 // the lazy plan of the second product; else the tile coordinates only).  Default stream; the caller synchronises.
 int build_spmv_plan(Matrix *m, SpmvPlan *p, bool allow_split);

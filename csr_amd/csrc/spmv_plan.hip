@@ -910,8 +910,9 @@ __global__ void vec_fill_kernel(const int64_t *__restrict__ seg_off, int32_t nro
 constexpr int HEAVY_STREAMS = 8;   // XCDs: blockIdx % 8 labels the XCD group (speed assumption only)
 
 // The knobs of one plan build (spmv_layout.h: SpmvKnobs, with their parsing rules): read here, once, at the top of
-// build_plan, and handed down.  No builder reads the environment.
-static SpmvKnobs read_spmv_knobs()
+// build_plan, and handed down.  No builder reads the environment.  (spmv.hip's get_plan_locked reads them the same way
+// while it decides whether a plan is built with the split.)
+SpmvKnobs read_spmv_knobs()
 {
     SpmvKnobStrings e;
     e.heavy_split = getenv("CSRK_SPMV_HEAVY_SPLIT");

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../include/csrk.h"
 
@@ -175,6 +176,15 @@ int exclusive_scan_i32_to_i64(const int32_t *in, int64_t *out, int64_t n, hipStr
 // See radix.hip.
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The value-type ladder of the host side: a builder or a launch templated on the matrix's value type, called with it as a
+// constant: f(std::integral_constant<int, VT>).
+template <class F> inline int with_val_type(int val_type, F &&f)
+{
+    if (val_type == CSRK_VAL_F64) return f(std::integral_constant<int, CSRK_VAL_F64>());
+    if (val_type == CSRK_VAL_F32) return f(std::integral_constant<int, CSRK_VAL_F32>());
+    return f(std::integral_constant<int, CSRK_VAL_NONE>());
+}
 
 // Row-pointer load that works for both widths.
 __device__ __forceinline__ int64_t load_ptr(const void *rp, int is64, int64_t i)

@@ -20,17 +20,17 @@
 #include "common.h"
 #include "device_loads.h"
 #include "panel.h"
+#include "spmm_plan.h"
 
-#include <algorithm>
 #include <cstdio>
 #include <mutex>
 #include <vector>
 
 namespace csrk {
 
-constexpr int MM_SEG = 64;       // entries per segment (light rows)
-constexpr int MM_G = 16;         // lanes per unit (segment or row slice): 16 lanes x 4 columns = a 64-column chunk of the panel
-constexpr int MM_CHUNK = 64;     // panel columns per pass over a unit's entries
+// (MM_SEG, MM_G, MM_CHUNK and the HR_ constants: spmm_plan.h, with every host decision of this file)
+static_assert(HR_LANES == WAVE, "spmm_plan.h counts wavefronts of WAVE lanes");
+static_assert(spmmplan::DB_VAL_NONE == CSRK_VAL_NONE && spmmplan::DB_VAL_F32 == CSRK_VAL_F32, "spmm_plan.h's value types are csrk.h's");
 
 // one segment of a light row: entries [start, start + n) of the CSR arrays; the result goes to row `row` of C
 // (part < 0) or to partial panel `part` (split rows)
@@ -61,16 +61,6 @@ struct SegDesc {
 // its second) instead of one: G x 1 GB of coalesced tile loads instead of 512 B of 128-B line fills per entry.  Each workgroup writes the partial panel of its
 // rows over its column range; the reduce kernel adds a row's R partials in range order (fixed order: bitwise
 // reproducible; inside a tile a row's entries keep their storage order).
-constexpr int HR_THREADS = 1024;
-constexpr int HR_WAVES = HR_THREADS / WAVE;      // 16
-constexpr int HR_RPW = 32;                       // rows per wavefront
-constexpr int HR_ROWS = HR_WAVES * HR_RPW;       // 512 rows per workgroup
-constexpr int HR_TILE = 128;                     // rows of B per tile
-constexpr int HR_KC = 64;                        // panel columns per launch (wider panels: one launch per 64 columns)
-constexpr int HR_PAD = 2 * WAVE;                 // the entry arrays' padding: a wavefront loads 64 entries from a bucket's start whatever its length
-constexpr int HR_MAXG = 8;                       // at most 8 row groups (4096 heavy rows)
-constexpr size_t HR_LDS = (size_t)2 * HR_TILE * HR_KC * 8;
-
 struct SpmmPlan {
     // heavy rows (spmm_hrows_kernel)
     bool hr_on = false;
@@ -222,6 +212,7 @@ __global__ void mm_count_kernel(const P *__restrict__ rp, int32_t nrows, int64_t
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrows) return;
     int64_t len = (int64_t)rp[r + 1] - (int64_t)rp[r];
+    // (spmmplan::light_segments is this expression for the host test: calling it here changed the kernel's instructions)
     const int64_t n = (heavy_min > 0 && len >= heavy_min) ? 0 : (len <= MM_SEG ? 1 : (len + MM_SEG - 1) / MM_SEG);
     cnt[r] = n;
     pcnt[r] = n > 1 ? n : 0;         // only split rows need partial panels
@@ -380,7 +371,7 @@ __global__ __launch_bounds__(HR_THREADS) void spmm_hrows_kernel(const int64_t *_
         nn = (int32_t)(bp[bk + bstep + 1] - e0n);
     }
     // (thread's offset inside a tile of B: row tid / 32, column pair tid % 32; fits 32 bits when a tile's rows do)
-    // (EVEN also says B and ldb keep the 16-B pieces aligned: spmm_device)
+    // (EVEN also says B and ldb keep the 16-B pieces aligned: spmmplan::hrows_even)
     const bool can_whole = EVEN && kc == HR_KC && (int64_t)HR_TILE * ldb * 8 < (1ll << 31);
     const uint32_t voff = (uint32_t)(((int64_t)(tid >> 5) * ldb + (tid & 31) * 2) * 8);
     {
@@ -574,37 +565,30 @@ static int build_mm_plan(Matrix *m, SpmmPlan *p, hipStream_t s)
 {
     CSRK_TRY(p->seg_off.alloc((size_t)(m->nrows + 1) * 8));
     CSRK_TRY(p->part_off.alloc((size_t)(m->nrows + 1) * 8));
+    const unsigned grid = (unsigned)ceil_div(m->nrows, 256);      // a thread per row
     if (m->nrows > 0) {
-        mm_count_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>((const P *)m->d_rowptrs, m->nrows,
-                                                                            p->seg_off.as<int64_t>(),
-                                                                            p->part_off.as<int64_t>(),
-                                                                            p->hr_on ? p->hr_min : 0);
+        mm_count_kernel<P><<<grid, 256, 0, s>>>((const P *)m->d_rowptrs, m->nrows, p->seg_off.as<int64_t>(), p->part_off.as<int64_t>(),
+                                                p->hr_on ? p->hr_min : 0);
         CSRK_LAUNCH_CHECK();
     }
     CSRK_TRY(exclusive_scan_i64(p->seg_off.as<int64_t>(), p->seg_off.as<int64_t>(), m->nrows, s));
     CSRK_TRY(exclusive_scan_i64(p->part_off.as<int64_t>(), p->part_off.as<int64_t>(), m->nrows, s));
-    int64_t n = 0, nm = 0;
-    CSRK_TRY(stage_d2h(&n, p->seg_off.as<int64_t>() + m->nrows, 8, s));
-    CSRK_TRY(stage_d2h(&nm, p->part_off.as<int64_t>() + m->nrows, 8, s));
+    CSRK_TRY(stage_d2h(&p->n_segs, p->seg_off.as<int64_t>() + m->nrows, 8, s));
+    CSRK_TRY(stage_d2h(&p->n_multi, p->part_off.as<int64_t>() + m->nrows, 8, s));
     CSRK_HIP(hipStreamSynchronize(s));
-    p->n_segs = n;
-    p->n_multi = nm;
-    if (nm > 0) {
+    if (p->n_multi > 0) {
         DevBuf cnt;
         CSRK_TRY(cnt.alloc(4));
         CSRK_HIP(hipMemsetAsync(cnt.p, 0, 4, s));
-        CSRK_TRY(p->split_rows.alloc((size_t)(nm / 2 + 1) * 4));      // every split row has >= 2 segments
-        mm_list_split_kernel<<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>(p->seg_off.as<int64_t>(), m->nrows,
-                                                                              p->split_rows.as<int32_t>(), cnt.as<int32_t>());
+        CSRK_TRY(p->split_rows.alloc((size_t)(p->n_multi / 2 + 1) * 4));      // every split row has >= 2 segments
+        mm_list_split_kernel<<<grid, 256, 0, s>>>(p->seg_off.as<int64_t>(), m->nrows, p->split_rows.as<int32_t>(), cnt.as<int32_t>());
         CSRK_LAUNCH_CHECK();
         CSRK_TRY(stage_d2h(&p->n_split, cnt.p, 4, s));
         CSRK_HIP(hipStreamSynchronize(s));
     }
-    CSRK_TRY(p->seg.alloc((size_t)n * sizeof(SegDesc)));
+    CSRK_TRY(p->seg.alloc((size_t)p->n_segs * sizeof(SegDesc)));
     if (m->nrows > 0) {
-        mm_fill_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>((const P *)m->d_rowptrs, p->seg_off.as<int64_t>(),
-                                                                           p->part_off.as<int64_t>(), m->nrows,
-                                                                           p->seg.as<SegDesc>());
+        mm_fill_kernel<P><<<grid, 256, 0, s>>>((const P *)m->d_rowptrs, p->seg_off.as<int64_t>(), p->part_off.as<int64_t>(), m->nrows, p->seg.as<SegDesc>());
         CSRK_LAUNCH_CHECK();
     }
     return CSRK_OK;
@@ -613,181 +597,167 @@ static int build_mm_plan(Matrix *m, SpmmPlan *p, hipStream_t s)
 int stable_sort_records_f64(const int32_t *keys, const int32_t *payload, const double *vals, int64_t n, int32_t key_range,
                             int64_t payload_range, int64_t *out_ptr, int32_t *out_payload, double *out_vals, hipStream_t s);   // transpose.hip
 
-// Choose the heavy rows and build their bucketed stream (plan time).  `force`: CSRK_SPMM_HEAVY=1 (small test matrices).
-template <class P>
-static int build_hrows(Matrix *m, SpmmPlan *p, int32_t k, bool force, hipStream_t s)
+// the file's knobs (spmm_plan.h), read where a plan is about to be built and at the top of spgemm_dense_b: the tests
+// change them between two handles, so nothing is kept across builds
+static SpmmKnobs read_spmm_knobs()
 {
-    p->hr_on = false;
-    if (m->nrows < 1 || m->ncols < 1 || m->nnz < 1) return CSRK_OK;
-    int cus = 0;
-    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    // row lengths -> the threshold that leaves at most HR_MAXG * 512 rows (and, unless forced, pays for its sweeps of B)
-    std::vector<int64_t> len((size_t)m->nrows);
-    {
-        DevBuf dlen;
-        CSRK_TRY(dlen.alloc((size_t)m->nrows * 8));
-        hr_len_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>((const P *)m->d_rowptrs, m->nrows, dlen.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        CSRK_TRY(stage_d2h(len.data(), dlen.p, (size_t)m->nrows * 8, s));
-        CSRK_HIP(hipStreamSynchronize(s));
-    }
-    std::vector<int32_t> cand;
-    const int64_t floor_len = force ? 256 : 512;                            // shorter rows never pay for a register slot
-    for (int32_t r = 0; r < m->nrows; r++)
-        if (len[(size_t)r] >= floor_len) cand.push_back(r);
-    if (cand.empty()) return CSRK_OK;
-    std::sort(cand.begin(), cand.end(), [&](int32_t a, int32_t b) { return len[(size_t)a] != len[(size_t)b] ? len[(size_t)a] > len[(size_t)b] : a < b; });
-    // Every row group sweeps all of B once (G n_cols rows of B staged in all), tile by tile, whatever it finds there: a
-    // group costs its tiles (staging, a barrier, a partial batch per wavefront) plus ~21 ps per entry, and saves the ~63 ps
-    // per entry of the light-row kernel.  Measured on the BASELINE matrix (2M columns; groups of 23.0 / 3.2 / 1.8 / 1.2 M
-    // entries): one group 2.22 ms for the product, two 2.12, four 2.13, eight 2.55.  Take row groups, longest rows first,
-    // while the group's entries are at least 1.25 x the rows of B it stages.
-    int G = 0;
-    int64_t nnz_h = 0;
-    size_t taken = 0;
-    const char *genv = getenv("CSRK_SPMM_HEAVY_GROUPS");
-    const int g_forced = genv ? atoi(genv) : 0;
-    while (G < HR_MAXG && taken < cand.size()) {
-        const size_t end = std::min(cand.size(), taken + (size_t)HR_ROWS);
-        int64_t gn = 0;
-        for (size_t c = taken; c < end; c++) gn += len[(size_t)cand[c]];
-        const bool pays = gn * 4 >= 5 * (int64_t)m->ncols;
-        if (getenv("CSRK_PLAN_TRACE"))
-            fprintf(stderr, "[csrk spmm plan] heavy row group %d: rows %zu..%zu (lengths %lld..%lld), %lld entries, %s\n", G, taken, end,
-                    (long long)len[(size_t)cand[taken]], (long long)len[(size_t)cand[end - 1]], (long long)gn, pays ? "pays" : "does not pay");
-        if (g_forced > 0 ? G >= g_forced : (!pays && !(force && G == 0))) break;
-        nnz_h += gn;
-        taken = end;
-        G++;
-    }
-    if (G == 0) return CSRK_OK;
-    // the threshold is a row LENGTH (the light path skips rows by length): rows as long as the last one taken come along
-    // when they fit, else the threshold moves up to the next length
-    int64_t hmin = len[(size_t)cand[taken - 1]];
-    size_t n = taken;
-    while (n < cand.size() && len[(size_t)cand[n]] >= hmin) n++;
-    if (n > (size_t)G * HR_ROWS) {
-        hmin++;
-        n = taken;
-        while (n > 0 && len[(size_t)cand[n - 1]] < hmin) n--;
-    }
-    if (n == 0 || hmin > INT32_MAX) return CSRK_OK;
-    cand.resize(n);
-    nnz_h = 0;
-    for (int32_t r : cand) nnz_h += len[(size_t)r];
-    while (G > 1 && (size_t)(G - 1) * HR_ROWS >= n) G--;
-    // G R workgroups, one per CU; a range needs a tile; with R a multiple of 8 the G workgroups of a column range sit
-    // side by side on one XCD (spmm_hrows_kernel)
-    const int64_t n_tiles = ceil_div((int64_t)m->ncols, HR_TILE);
-    int R = (int)std::min<int64_t>(std::max(cus, G) / G, n_tiles);
-    if (R >= 8) R = R / 8 * 8;
-    const int64_t n_buckets = n_tiles * G * HR_WAVES;
-    if (n_buckets >= (1ll << 30)) return CSRK_OK;                           // (keys are 32-bit)
-    if (!force && n_buckets * 8 > nnz_h * 12) return CSRK_OK;               // the bucket table would outweigh the stream
-    size_t mfree = 0, mtotal = 0;
-    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
-    if ((size_t)nnz_h * 40 + (size_t)n_buckets * 8 + (64u << 20) > mfree) return CSRK_OK;
-    // places: rank i (longest first) -> group i % G, then wavefront and slot round robin, so every wavefront of every
-    // group holds the same mix of lengths
-    std::vector<int32_t> code(n);
-    std::vector<int64_t> off(n + 1);
-    for (size_t i = 0; i < n; i++) {
-        const int32_t g = (int32_t)(i % (size_t)G), j = (int32_t)(i / (size_t)G);
-        code[i] = (g << 9) | ((j % HR_WAVES) << 5) | (j / HR_WAVES);
-        off[i] = i ? off[i - 1] + len[(size_t)cand[i - 1]] : 0;
-    }
-    off[n] = off[n - 1] + len[(size_t)cand[n - 1]];
+    return parse_spmm_knobs({getenv("CSRK_SPMM_HEAVY"), getenv("CSRK_SPMM_HEAVY_GROUPS"), getenv("CSRK_PLAN_TRACE"), getenv("CSRK_SPGEMM_DENSE")});
+}
+
+// ---- the heavy rows' plan: build_hrows and its steps ---------------------------------------------------------------------
+// what one build holds besides the plan: the host tables of its asynchronous copies, then the temporaries in the order they
+// are requested from the pool (and go back to it in reverse, on return)
+struct HrowsBuild {
+    std::vector<int32_t> code, range;
+    std::vector<int64_t> off;
     DevBuf doff, key, pay, val;
-    CSRK_TRY(p->hr_rows.alloc(n * 4));
-    CSRK_TRY(p->hr_code.alloc(n * 4));
-    CSRK_TRY(doff.alloc((n + 1) * 8));
-    CSRK_TRY(key.alloc((size_t)nnz_h * 4));
-    CSRK_TRY(pay.alloc((size_t)nnz_h * 4));
-    CSRK_TRY(val.alloc((size_t)nnz_h * 8));
-    CSRK_TRY(p->hr_bp.alloc((size_t)(n_buckets + 1) * 8));
-    CSRK_TRY(p->hr_idx.alloc((size_t)(nnz_h + HR_PAD) * 4));
-    CSRK_TRY(p->hr_vals.alloc((size_t)(nnz_h + HR_PAD) * 8));
-    CSRK_HIP(hipMemsetAsync(p->hr_idx.as<uint32_t>() + nnz_h, 0, HR_PAD * 4, s));      // (the batches of four read a little past a bucket)
-    CSRK_HIP(hipMemsetAsync(p->hr_vals.as<double>() + nnz_h, 0, HR_PAD * 8, s));
-    CSRK_TRY(stage_h2d(p->hr_rows.p, cand.data(), n * 4, s));
-    CSRK_TRY(stage_h2d(p->hr_code.p, code.data(), n * 4, s));
-    CSRK_TRY(stage_h2d(doff.p, off.data(), (n + 1) * 8, s));
-#define EMIT(VT)                                                                                                       \
-    hr_emit_kernel<P, VT><<<(unsigned)n, 256, 0, s>>>((const P *)m->d_rowptrs, m->d_colinds, m->d_values, p->hr_rows.as<int32_t>(), \
-                                                      p->hr_code.as<int32_t>(), doff.as<int64_t>(), G, key.as<int32_t>(),  \
-                                                      pay.as<int32_t>(), val.as<double>())
-    if (m->val_type == CSRK_VAL_F64) EMIT(CSRK_VAL_F64);
-    else if (m->val_type == CSRK_VAL_F32) EMIT(CSRK_VAL_F32);
-    else EMIT(CSRK_VAL_NONE);
-#undef EMIT
+};
+
+template <class P>
+static int hrows_row_lengths(Matrix *m, std::vector<int64_t> &len, hipStream_t s)
+{
+    len.resize((size_t)m->nrows);
+    DevBuf dlen;
+    CSRK_TRY(dlen.alloc((size_t)m->nrows * 8));
+    hr_len_kernel<P><<<(unsigned)ceil_div(m->nrows, 256), 256, 0, s>>>((const P *)m->d_rowptrs, m->nrows, dlen.as<int64_t>());
     CSRK_LAUNCH_CHECK();
-    CSRK_TRY(stable_sort_records_f64(key.as<int32_t>(), pay.as<int32_t>(), val.as<double>(), nnz_h, (int32_t)n_buckets, 1 << 16,
-                                     p->hr_bp.as<int64_t>(), (int32_t *)p->hr_idx.p, p->hr_vals.as<double>(), s));
-    // column ranges: whole tiles, balanced by entries plus a fixed cost per tile (staging + barrier ~ 200 entries' worth)
-    std::vector<int64_t> tot((size_t)n_tiles + 1);
-    {
-        DevBuf dt;
-        CSRK_TRY(dt.alloc((size_t)(n_tiles + 1) * 8));
-        hr_tile_totals_kernel<<<(unsigned)ceil_div(n_tiles + 1, 256), 256, 0, s>>>(p->hr_bp.as<int64_t>(), (int32_t)n_tiles, G * HR_WAVES,
-                                                                                 dt.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        CSRK_TRY(stage_d2h(tot.data(), dt.p, (size_t)(n_tiles + 1) * 8, s));
-        CSRK_HIP(hipStreamSynchronize(s));
-    }
-    const int64_t tile_cost = 200 * (int64_t)G;
-    const double total_cost = (double)nnz_h + (double)tile_cost * (double)n_tiles;
-    std::vector<int32_t> range((size_t)R + 1);
-    range[0] = 0;
-    {
-        int64_t t = 0;
-        for (int q = 1; q < R; q++) {
-            const double goal = total_cost * q / R;
-            while (t < n_tiles && (double)tot[(size_t)t + 1] + (double)tile_cost * (double)(t + 1) <= goal) t++;
-            // every range keeps at least one tile, and leaves one for each range after it
-            t = std::max<int64_t>(t, (int64_t)range[(size_t)q - 1] + 1);
-            t = std::min<int64_t>(t, n_tiles - (R - q));
-            range[(size_t)q] = (int32_t)t;
-        }
-    }
-    range[(size_t)R] = (int32_t)n_tiles;
-    CSRK_TRY(p->hr_range.alloc(((size_t)R + 1) * 4));
-    CSRK_TRY(stage_h2d(p->hr_range.p, range.data(), ((size_t)R + 1) * 4, s));
-    CSRK_TRY(p->hr_part.alloc((size_t)R * G * HR_ROWS * HR_KC * 8));
-    CSRK_HIP(hipFuncSetAttribute((const void *)spmm_hrows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HR_LDS));
-    CSRK_HIP(hipFuncSetAttribute((const void *)spmm_hrows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HR_LDS));
-    CSRK_HIP(hipStreamSynchronize(s));      // host vectors of the async copies; the temporaries are freed on return
-    p->hr_on = true;
-    p->hr_min = (int32_t)hmin;
-    p->hr_n = (int32_t)n;
-    p->hr_G = G;
-    p->hr_R = R;
-    p->hr_tiles = (int32_t)n_tiles;
-    p->hr_nnz = nnz_h;
-    (void)k;
+    CSRK_TRY(stage_d2h(len.data(), dlen.p, (size_t)m->nrows * 8, s));
+    CSRK_HIP(hipStreamSynchronize(s));
     return CSRK_OK;
 }
 
-static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, double *dC, int64_t ldc, hipStream_t s,
-                       SpmmOut om = {nullptr, 0})
+// spmmplan::choose_heavy, its trace (CSRK_PLAN_TRACE) and the one question it leaves to the device: is there memory for the build
+static int hrows_choose(const std::vector<int64_t> &len, int32_t ncols, int cus, const SpmmKnobs &knobs, spmmplan::HeavyChoice &h)
 {
-    CSRK_REQUIRE(k >= 0 && ldb >= k && ldc >= k, "bad panel geometry k=%d ldb=%lld ldc=%lld", k, (long long)ldb, (long long)ldc);
-    if (m->nrows == 0 || k == 0) return CSRK_OK;
-    SpmmPlan *p;
-    // The launch group below shares the plan's partial-panel buffers (hr_part, part): the per-handle lock is held
-    // across it, as spmv_dispatch does, so that concurrent callers are ordered by the stream instead of interleaving
-    // (csrk.h: calls on the same handle serialise).
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (s) m->used_user_stream = true;
+    h = spmmplan::choose_heavy(len, ncols, cus, knobs);
+    if (knobs.trace)
+        for (size_t g = 0; g < h.tried.size(); g++) {
+            const spmmplan::GroupTry &t = h.tried[g];
+            fprintf(stderr, "[csrk spmm plan] heavy row group %d: rows %zu..%zu (lengths %lld..%lld), %lld entries, %s\n", (int)g, t.first, t.end,
+                    (long long)t.longest, (long long)t.shortest, (long long)t.entries, t.pays ? "pays" : "does not pay");
+        }
+    if (!h.on) return CSRK_OK;
+    size_t mfree = 0, mtotal = 0;
+    CSRK_HIP(hipMemGetInfo(&mfree, &mtotal));
+    h.on = spmmplan::build_fits_memory(h.nnz_h, h.n_buckets, mfree);
+    return CSRK_OK;
+}
+
+// the plan's stream arrays and the build's temporaries; the rows, their places and their entry offsets go up
+static int hrows_stream_buffers(SpmmPlan *p, const std::vector<int64_t> &len, const spmmplan::HeavyChoice &h, HrowsBuild &b, hipStream_t s)
+{
+    const size_t n = h.rows.size();
+    const int64_t nnz_h = h.nnz_h;
+    b.code = spmmplan::place_codes(n, h.G);
+    b.off = spmmplan::entry_offsets(len, h.rows);
+    CSRK_TRY(p->hr_rows.alloc(n * 4));
+    CSRK_TRY(p->hr_code.alloc(n * 4));
+    CSRK_TRY(b.doff.alloc((n + 1) * 8));
+    CSRK_TRY(b.key.alloc((size_t)nnz_h * 4));
+    CSRK_TRY(b.pay.alloc((size_t)nnz_h * 4));
+    CSRK_TRY(b.val.alloc((size_t)nnz_h * 8));
+    CSRK_TRY(p->hr_bp.alloc((size_t)(h.n_buckets + 1) * 8));
+    CSRK_TRY(p->hr_idx.alloc((size_t)(nnz_h + HR_PAD) * 4));
+    CSRK_TRY(p->hr_vals.alloc((size_t)(nnz_h + HR_PAD) * 8));
+    CSRK_HIP(hipMemsetAsync(p->hr_idx.as<uint32_t>() + nnz_h, 0, HR_PAD * 4, s));      // (the batches of eight read a little past a bucket)
+    CSRK_HIP(hipMemsetAsync(p->hr_vals.as<double>() + nnz_h, 0, HR_PAD * 8, s));
+    CSRK_TRY(stage_h2d(p->hr_rows.p, h.rows.data(), n * 4, s));
+    CSRK_TRY(stage_h2d(p->hr_code.p, b.code.data(), n * 4, s));
+    CSRK_TRY(stage_h2d(b.doff.p, b.off.data(), (n + 1) * 8, s));
+    return CSRK_OK;
+}
+
+// the heavy rows' entries as records in (rank, storage) order, then stably by bucket into the plan's stream
+template <class P>
+static int hrows_emit_and_sort(Matrix *m, SpmmPlan *p, const spmmplan::HeavyChoice &h, HrowsBuild &b, hipStream_t s)
+{
+    with_val_type(m->val_type, [&](auto vt) -> int {
+        hr_emit_kernel<P, decltype(vt)::value><<<(unsigned)h.rows.size(), 256, 0, s>>>(
+            (const P *)m->d_rowptrs, m->d_colinds, m->d_values, p->hr_rows.as<int32_t>(), p->hr_code.as<int32_t>(), b.doff.as<int64_t>(), h.G,
+            b.key.as<int32_t>(), b.pay.as<int32_t>(), b.val.as<double>());
+        return CSRK_OK;
+    });
+    CSRK_LAUNCH_CHECK();
+    return stable_sort_records_f64(b.key.as<int32_t>(), b.pay.as<int32_t>(), b.val.as<double>(), h.nnz_h, (int32_t)h.n_buckets, 1 << 16,
+                                   p->hr_bp.as<int64_t>(), (int32_t *)p->hr_idx.p, p->hr_vals.as<double>(), s);
+}
+
+// the entries before each tile -> the host -> spmmplan::balance_ranges -> the plan's range table
+static int hrows_ranges(SpmmPlan *p, const spmmplan::HeavyChoice &h, HrowsBuild &b, hipStream_t s)
+{
+    std::vector<int64_t> tot((size_t)h.n_tiles + 1);
+    {
+        DevBuf dt;
+        CSRK_TRY(dt.alloc((size_t)(h.n_tiles + 1) * 8));
+        hr_tile_totals_kernel<<<(unsigned)ceil_div(h.n_tiles + 1, 256), 256, 0, s>>>(p->hr_bp.as<int64_t>(), (int32_t)h.n_tiles, h.G * HR_WAVES, dt.as<int64_t>());
+        CSRK_LAUNCH_CHECK();
+        CSRK_TRY(stage_d2h(tot.data(), dt.p, (size_t)(h.n_tiles + 1) * 8, s));
+        CSRK_HIP(hipStreamSynchronize(s));
+    }
+    b.range = spmmplan::balance_ranges(tot, h.n_tiles, h.G, h.R, h.nnz_h);
+    CSRK_TRY(p->hr_range.alloc(((size_t)h.R + 1) * 4));
+    CSRK_TRY(stage_h2d(p->hr_range.p, b.range.data(), ((size_t)h.R + 1) * 4, s));
+    return CSRK_OK;
+}
+
+// the workgroups' partial panels, the kernels' LDS, and the plan says "on"
+static int hrows_commit(SpmmPlan *p, const spmmplan::HeavyChoice &h, hipStream_t s)
+{
+    CSRK_TRY(p->hr_part.alloc((size_t)h.R * h.G * HR_ROWS * HR_KC * 8));
+    CSRK_HIP(hipFuncSetAttribute((const void *)spmm_hrows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HR_LDS));
+    CSRK_HIP(hipFuncSetAttribute((const void *)spmm_hrows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HR_LDS));
+    CSRK_HIP(hipStreamSynchronize(s));      // host tables of the async copies; the temporaries are freed on the builder's return
+    p->hr_on = true;
+    p->hr_min = (int32_t)h.hmin;
+    p->hr_n = (int32_t)h.rows.size();
+    p->hr_G = h.G;
+    p->hr_R = h.R;
+    p->hr_tiles = (int32_t)h.n_tiles;
+    p->hr_nnz = h.nnz_h;
+    return CSRK_OK;
+}
+
+// Choose the heavy rows and build their bucketed stream (plan time).
+template <class P>
+static int build_hrows(Matrix *m, SpmmPlan *p, const SpmmKnobs &knobs, hipStream_t s)
+{
+    p->hr_on = false;
+    if (!spmmplan::has_entries(m->nrows, m->ncols, m->nnz)) return CSRK_OK;
+    int cus = 0;
+    CSRK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    std::vector<int64_t> len;
+    CSRK_TRY(hrows_row_lengths<P>(m, len, s));
+    spmmplan::HeavyChoice h;
+    CSRK_TRY(hrows_choose(len, m->ncols, cus, knobs, h));
+    if (!h.on) return CSRK_OK;
+    HrowsBuild b;
+    CSRK_TRY(hrows_stream_buffers(p, len, h, b, s));
+    CSRK_TRY(hrows_emit_and_sort<P>(m, p, h, b, s));
+    CSRK_TRY(hrows_ranges(p, h, b, s));
+    return hrows_commit(p, h, s);
+}
+
+// ---- a product: spmm_device and its steps ----------------------------------------------------------------------------------
+struct SpmmPanels {      // the operands of one product
+    const double *B;
+    double *C;
+    int64_t ldb, ldc;
+    int32_t k;
+    hipStream_t s;
+    SpmmOut om;
+};
+
+// the handle's plan, built at its first product for that product's width (caller holds m->mu)
+static int spmm_plan_locked(Matrix *m, int32_t k, SpmmPlan **out)
+{
     if (!m->spmm_plan) {
         SpmmPlan *np = new (std::nothrow) SpmmPlan();
         CSRK_REQUIRE(np, "out of host memory");
         // default stream + completion before use: see the caching allocator's contract (common.h)
         int rc = CSRK_OK;
-        // the heavy-row form pays when B as a whole does not fit the caches (CSRK_SPMM_HEAVY=0 / 1: never / always)
-        const char *env = getenv("CSRK_SPMM_HEAVY");
-        const bool force = env && env[0] == '1';
-        if (!(env && env[0] == '0') && ((int64_t)m->ncols * k * 8 > (64ll << 20) || force))
-            rc = m->ptr64 ? build_hrows<int64_t>(m, np, k, force, nullptr) : build_hrows<int32_t>(m, np, k, force, nullptr);
+        const SpmmKnobs knobs = read_spmm_knobs();
+        if (spmmplan::heavy_engaged(m->ncols, k, knobs))      // (B as a whole does not fit the caches; CSRK_SPMM_HEAVY=0 / 1: never / always)
+            rc = m->ptr64 ? build_hrows<int64_t>(m, np, knobs, nullptr) : build_hrows<int32_t>(m, np, knobs, nullptr);
         if (rc == CSRK_OK) rc = m->ptr64 ? build_mm_plan<int64_t>(m, np, nullptr) : build_mm_plan<int32_t>(m, np, nullptr);
         if (rc == CSRK_OK && hipDeviceSynchronize() != hipSuccess) rc = CSRK_ERR_HIP;
         if (rc != CSRK_OK) {
@@ -796,63 +766,75 @@ static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, doub
         }
         m->spmm_plan = np;
     }
-    p = m->spmm_plan;
-    // a wider panel than any before needs a larger partial buffer: earlier launches (any stream) may still be using the
-    // old block, which DevBuf::alloc returns to the pool at once -- wait for the device first
-    const bool grow_p = p->n_multi > 0 && p->part_k < k;
-    if (grow_p && p->part.p) CSRK_HIP(hipDeviceSynchronize());
-    if (grow_p) {           // some row is split: partial panels needed
-        CSRK_TRY(p->part.alloc((size_t)p->n_multi * k * 8));
-        p->part_k = k;
-    }
-    // The 16-B loads and stores (FULL4, EVEN) need 16-B aligned B / C rows: a column block of a wider panel that starts
-    // at an odd column, or an odd ldb / ldc, takes the 8-B forms instead (same products, same order of the sums: the
-    // bits do not depend on the form)
-    const bool b_al = ((uintptr_t)dB & 15) == 0 && (ldb & 1) == 0;
-    const bool c_al = ((uintptr_t)dC & 15) == 0 && (ldc & 1) == 0;
-    const bool full4 = (k % 4) == 0 && b_al && c_al;
-    if (p->hr_on) {
-        const unsigned wgs = (unsigned)(p->hr_G * p->hr_R);
-        const unsigned rgrid = (unsigned)ceil_div((int64_t)p->hr_n * WAVE, 256);
-        for (int32_t c0 = 0; c0 < k; c0 += HR_KC) {        // 64 panel columns per launch (stream order: hr_part is reused)
-            const int32_t kc = k - c0 < HR_KC ? k - c0 : HR_KC;
-#define HROWS(EVEN)                                                                                                    \
-    spmm_hrows_kernel<EVEN><<<wgs, HR_THREADS, HR_LDS, s>>>(p->hr_bp.as<int64_t>(), p->hr_idx.as<uint32_t>(),             \
-                                                           p->hr_vals.as<double>(), dB + c0, kc, ldb, m->ncols,          \
-                                                           p->hr_range.as<int32_t>(), p->hr_G, p->hr_part.as<double>())
-            if (kc % 2 == 0 && b_al) HROWS(true);
-            else HROWS(false);
-#undef HROWS
-            CSRK_LAUNCH_CHECK();
-            spmm_hrows_reduce_kernel<<<rgrid, 256, 0, s>>>(p->hr_rows.as<int32_t>(), p->hr_code.as<int32_t>(), p->hr_n, p->hr_G, p->hr_R,
-                                                          kc, p->hr_part.as<double>(), dC, ldc, c0, om);
-            CSRK_LAUNCH_CHECK();
-        }
-    }
-    if (p->n_segs == 0) return CSRK_OK;
-    const unsigned grid = (unsigned)ceil_div(p->n_segs * MM_G, 256);
-#define GO(VT, F4)                                                                                                     \
-    spmm_seg_kernel<VT, F4><<<grid, 256, 0, s>>>(m->d_colinds, m->d_values, dB, k, ldb, dC, ldc, p->seg.as<SegDesc>(),   \
-                                                 p->n_segs, p->part.as<double>(), om)
-    if (m->val_type == CSRK_VAL_F64) {
-        if (full4) GO(CSRK_VAL_F64, true);
-        else GO(CSRK_VAL_F64, false);
-    } else if (m->val_type == CSRK_VAL_F32) {
-        if (full4) GO(CSRK_VAL_F32, true);
-        else GO(CSRK_VAL_F32, false);
-    } else {
-        if (full4) GO(CSRK_VAL_NONE, true);
-        else GO(CSRK_VAL_NONE, false);
-    }
-#undef GO
-    CSRK_LAUNCH_CHECK();
-    if (p->n_multi > 0) {
-        spmm_fixup_kernel<<<(unsigned)ceil_div((int64_t)p->n_split * WAVE, 256), 256, 0, s>>>(
-            p->seg_off.as<int64_t>(), p->part_off.as<int64_t>(), p->split_rows.as<int32_t>(), p->n_split, k,
-            p->part.as<double>(), dC, ldc, om);
+    *out = m->spmm_plan;
+    return CSRK_OK;
+}
+
+// a wider panel than any before needs a larger partial buffer: earlier launches (any stream) may still be using the old
+// block, which DevBuf::alloc returns to the pool at once -- wait for the device first
+static int spmm_grow_partials(SpmmPlan *p, int32_t k)
+{
+    if (!spmmplan::grow_partials(p->n_multi, p->part_k, k)) return CSRK_OK;
+    if (p->part.p) CSRK_HIP(hipDeviceSynchronize());
+    CSRK_TRY(p->part.alloc((size_t)p->n_multi * k * 8));
+    p->part_k = k;
+    return CSRK_OK;
+}
+
+// the heavy rows: 64 panel columns per launch pair (stream order: hr_part is reused)
+static int spmm_launch_heavy(const Matrix *m, const SpmmPlan *p, const SpmmPanels &a, bool b_al)
+{
+    const unsigned wgs = spmmplan::hrows_grid(p->hr_G, p->hr_R), rgrid = spmmplan::reduce_grid(p->hr_n);
+    for (int32_t b = 0; b < spmmplan::col_blocks(a.k); b++) {
+        const spmmplan::ColBlock cb = spmmplan::col_block(a.k, b);
+        const auto hrows = spmmplan::hrows_even(cb.kc, b_al) ? spmm_hrows_kernel<true> : spmm_hrows_kernel<false>;
+        hrows<<<wgs, HR_THREADS, HR_LDS, a.s>>>(p->hr_bp.as<int64_t>(), p->hr_idx.as<uint32_t>(), p->hr_vals.as<double>(), a.B + cb.c0, cb.kc,
+                                                a.ldb, m->ncols, p->hr_range.as<int32_t>(), p->hr_G, p->hr_part.as<double>());
+        CSRK_LAUNCH_CHECK();
+        spmm_hrows_reduce_kernel<<<rgrid, 256, 0, a.s>>>(p->hr_rows.as<int32_t>(), p->hr_code.as<int32_t>(), p->hr_n, p->hr_G, p->hr_R, cb.kc,
+                                                        p->hr_part.as<double>(), a.C, a.ldc, cb.c0, a.om);
         CSRK_LAUNCH_CHECK();
     }
     return CSRK_OK;
+}
+
+// the other rows' segments, then the split rows' partials in segment order
+static int spmm_launch_light(const Matrix *m, const SpmmPlan *p, const SpmmPanels &a, bool full4)
+{
+    if (p->n_segs == 0) return CSRK_OK;
+    with_val_type(m->val_type, [&](auto vt) -> int {
+        constexpr int VT = decltype(vt)::value;
+        const auto seg = full4 ? spmm_seg_kernel<VT, true> : spmm_seg_kernel<VT, false>;
+        seg<<<spmmplan::seg_grid(p->n_segs), 256, 0, a.s>>>(m->d_colinds, m->d_values, a.B, a.k, a.ldb, a.C, a.ldc, p->seg.as<SegDesc>(),
+                                                           p->n_segs, p->part.as<double>(), a.om);
+        return CSRK_OK;
+    });
+    CSRK_LAUNCH_CHECK();
+    if (p->n_multi > 0) {
+        spmm_fixup_kernel<<<spmmplan::fixup_grid(p->n_split), 256, 0, a.s>>>(p->seg_off.as<int64_t>(), p->part_off.as<int64_t>(), p->split_rows.as<int32_t>(),
+                                                                             p->n_split, a.k, p->part.as<double>(), a.C, a.ldc, a.om);
+        CSRK_LAUNCH_CHECK();
+    }
+    return CSRK_OK;
+}
+
+static int spmm_device(Matrix *m, const double *dB, int32_t k, int64_t ldb, double *dC, int64_t ldc, hipStream_t s,
+                       SpmmOut om = {nullptr, 0})
+{
+    CSRK_REQUIRE(k >= 0 && ldb >= k && ldc >= k, "bad panel geometry k=%d ldb=%lld ldc=%lld", k, (long long)ldb, (long long)ldc);
+    if (m->nrows == 0 || k == 0) return CSRK_OK;
+    // The launch groups share the plan's partial-panel buffers (hr_part, part): the per-handle lock is held across them,
+    // as spmv_dispatch does, so that concurrent callers are ordered by the stream instead of interleaving (csrk.h: calls
+    // on the same handle serialise).
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (s) m->used_user_stream = true;
+    SpmmPlan *p = nullptr;
+    CSRK_TRY(spmm_plan_locked(m, k, &p));
+    CSRK_TRY(spmm_grow_partials(p, k));
+    const SpmmPanels a = {dB, dC, ldb, ldc, k, s, om};
+    const bool b_al = spmmplan::aligned16(dB, ldb), c_al = spmmplan::aligned16(dC, ldc);
+    if (p->hr_on) CSRK_TRY(spmm_launch_heavy(m, p, a, b_al));
+    return spmm_launch_light(m, p, a, spmmplan::full4(k, b_al, c_al));
 }
 
 // ---- mult_ab(A, B) with B a fully populated CSR: the reference's own route to BASELINE configs[2] ---------------------
@@ -911,87 +893,103 @@ __global__ void dense_widen_kernel(const float *__restrict__ in, double *__restr
 
 bool spgemm_reference_order_wanted();      // spgemm_order.hip
 
+// the route's temporaries in the order they are requested from the pool (they go back in reverse, in default-stream order:
+// every launch of the route is on it)
+struct DenseBTemps {
+    DevBuf bad, rank, row_base;
+    DevBuf wide;      // a float32 panel under float64 values of A: widened (exactly) once
+};
+
+// The look at B -- 4 bytes per entry: 0.08 ms for configs[2] -- is remembered by the handle (Matrix::dense_panel; `known` is
+// what it remembers: -1 = not looked at yet); the flag is read with C's rows, below.
+static int dense_b_look(const Matrix *b, int32_t k, int known, DenseBTemps &t)
+{
+    CSRK_TRY(t.bad.alloc(4));
+    CSRK_HIP(hipMemsetAsync(t.bad.p, 0, 4, nullptr));
+    if (known >= 0) return CSRK_OK;
+    const unsigned gb = (unsigned)ceil_div(b->nnz + 1, 256);
+    if (b->ptr64) dense_b_check_kernel<int64_t><<<gb, 256>>>((const int64_t *)b->d_rowptrs, b->d_colinds, b->nrows, k, t.bad.as<int32_t>());
+    else dense_b_check_kernel<int32_t><<<gb, 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows, k, t.bad.as<int32_t>());
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// C's rows meanwhile: which rows of A hold an entry (rank[i] = such rows before row i); then the look's answer and their number
+static int dense_c_live_rows(const Matrix *a, DenseBTemps &t, int32_t *is_bad, int64_t *live)
+{
+    const int32_t nr = a->nrows;
+    CSRK_TRY(t.rank.alloc((size_t)(nr + 1) * 8));
+    CSRK_TRY(t.row_base.alloc((size_t)(nr + 1) * 8));
+    const unsigned ga = (unsigned)ceil_div(nr + 1, 256);
+    if (a->ptr64) dense_c_live_kernel<int64_t><<<ga, 256>>>((const int64_t *)a->d_rowptrs, nr, t.rank.as<int64_t>());
+    else dense_c_live_kernel<int32_t><<<ga, 256>>>((const int32_t *)a->d_rowptrs, nr, t.rank.as<int64_t>());
+    CSRK_LAUNCH_CHECK();
+    CSRK_TRY(exclusive_scan_i64(t.rank.as<int64_t>(), t.rank.as<int64_t>(), nr, nullptr));
+    CSRK_TRY(stage_d2h(is_bad, t.bad.p, 4, nullptr));
+    CSRK_TRY(stage_d2h(live, t.rank.as<int64_t>() + nr, 8, nullptr));
+    return CSRK_OK;
+}
+
+// C's row pointers and columns, then its values: the dense-panel product of A and B's values, stored through SpmmOut
+static int dense_c_fill(Matrix *a, const Matrix *b, Matrix *c, bool ref_order, DenseBTemps &t)
+{
+    const int32_t nr = a->nrows, k = b->ncols;
+    dense_c_rows_kernel<<<(unsigned)ceil_div(nr + 1, 256), 256>>>(t.rank.as<int64_t>(), nr, k, (int32_t *)c->d_rowptrs, t.row_base.as<int64_t>());
+    CSRK_LAUNCH_CHECK();
+    if (c->nnz > 0) {
+        dense_c_cols_kernel<<<(unsigned)ceil_div(c->nnz, 256), 256>>>(c->d_colinds, c->nnz, k, ref_order);
+        CSRK_LAUNCH_CHECK();
+    }
+    const double *panel = (const double *)b->d_values;
+    if (b->val_type == CSRK_VAL_F32) {
+        CSRK_TRY(t.wide.alloc((size_t)b->nnz * 8));
+        dense_widen_kernel<<<(unsigned)ceil_div(b->nnz, 256), 256>>>((const float *)b->d_values, t.wide.as<double>(), b->nnz);
+        CSRK_LAUNCH_CHECK();
+        panel = t.wide.as<double>();
+    }
+    if (c->nnz > 0) CSRK_TRY(spmm_device(a, panel, k, k, (double *)c->d_values, k, nullptr, SpmmOut{t.row_base.as<int64_t>(), ref_order ? k : 0}));
+    // (row_base, the widened panel and C's arrays are recycled in default-stream order: the launches above are on it)
+    CSRK_HIP(hipDeviceSynchronize());
+    return CSRK_OK;
+}
+
 // *taken = false: B is not a row-major panel (or the route is switched off): the caller runs the general product
 int spgemm_dense_b(Matrix *a, Matrix *b, Matrix **out, bool *taken)
 {
     *taken = false;
-    const char *env = getenv("CSRK_SPGEMM_DENSE");
-    if (env && env[0] == '0') return CSRK_OK;
+    const SpmmKnobs knobs = read_spmm_knobs();
+    if (!spmmplan::dense_b_gate(knobs, a->ncols, a->nnz, a->val_type, b->nrows, b->ncols, b->nnz, b->val_type)) return CSRK_OK;
     const int32_t k = b->ncols;
-    if (a->ncols != b->nrows || k < 1 || b->nrows < 1 || a->nnz == 0 || b->nnz != (int64_t)b->nrows * k) return CSRK_OK;
-    if (a->val_type == CSRK_VAL_NONE || b->val_type == CSRK_VAL_NONE) return CSRK_OK;      // (the general product reports it)
-    if (a->val_type == CSRK_VAL_F32 && b->val_type == CSRK_VAL_F32) return CSRK_OK;         // float32 products: multiply.py:120
-    // (the look at B -- 4 bytes per entry: 0.08 ms for configs[2] -- is remembered by the handle: Matrix::dense_panel)
     int known;
     {
         std::lock_guard<std::mutex> lk(b->mu);
         known = b->dense_panel;
     }
     if (known == 0) return CSRK_OK;
-    DevBuf bad;
-    CSRK_TRY(bad.alloc(4));
-    CSRK_HIP(hipMemsetAsync(bad.p, 0, 4, nullptr));
-    if (known < 0) {
-        const unsigned gb = (unsigned)ceil_div(b->nnz + 1, 256);
-        if (b->ptr64) dense_b_check_kernel<int64_t><<<gb, 256>>>((const int64_t *)b->d_rowptrs, b->d_colinds, b->nrows, k, bad.as<int32_t>());
-        else dense_b_check_kernel<int32_t><<<gb, 256>>>((const int32_t *)b->d_rowptrs, b->d_colinds, b->nrows, k, bad.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-    }
-    // C's rows meanwhile: which rows of A hold an entry
-    const int32_t nr = a->nrows;
-    DevBuf rank, row_base;
-    CSRK_TRY(rank.alloc((size_t)(nr + 1) * 8));
-    CSRK_TRY(row_base.alloc((size_t)(nr + 1) * 8));
-    const unsigned ga = (unsigned)ceil_div(nr + 1, 256);
-    if (a->ptr64) dense_c_live_kernel<int64_t><<<ga, 256>>>((const int64_t *)a->d_rowptrs, nr, rank.as<int64_t>());
-    else dense_c_live_kernel<int32_t><<<ga, 256>>>((const int32_t *)a->d_rowptrs, nr, rank.as<int64_t>());
-    CSRK_LAUNCH_CHECK();
-    CSRK_TRY(exclusive_scan_i64(rank.as<int64_t>(), rank.as<int64_t>(), nr, nullptr));
+    DenseBTemps t;
     int32_t is_bad = 0;
     int64_t live = 0;
-    CSRK_TRY(stage_d2h(&is_bad, bad.p, 4, nullptr));
-    CSRK_TRY(stage_d2h(&live, rank.as<int64_t>() + nr, 8, nullptr));
+    CSRK_TRY(dense_b_look(b, k, known, t));
+    CSRK_TRY(dense_c_live_rows(a, t, &is_bad, &live));
     if (known < 0) {
         std::lock_guard<std::mutex> lk(b->mu);
         b->dense_panel = is_bad ? 0 : 1;
     }
     if (is_bad) return CSRK_OK;
-    const int64_t c_nnz = live * k;
-    if (c_nnz > INT32_MAX) {
+    const int64_t c_nnz = spmmplan::dense_c_nnz(live, k);
+    if (spmmplan::dense_c_overflows(c_nnz)) {
         set_error("product has %lld entries; the reference's int32 row pointers (multiply.py:28) cannot hold it: "
                   "multiply row blocks of A instead", (long long)c_nnz);
         return CSRK_ERR_OVERFLOW;
     }
     const bool ref_order = spgemm_reference_order_wanted();      // (read once: C's columns and the stores of its values agree)
     Matrix *c = nullptr;
-    CSRK_TRY(new_matrix(nr, k, c_nnz, 0, CSRK_VAL_F64, &c));
-    dense_c_rows_kernel<<<ga, 256>>>(rank.as<int64_t>(), nr, k, (int32_t *)c->d_rowptrs, row_base.as<int64_t>());
-    int rc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
-    if (rc == CSRK_OK && c_nnz > 0) {
-        dense_c_cols_kernel<<<(unsigned)ceil_div(c_nnz, 256), 256>>>(c->d_colinds, c_nnz, k, ref_order);
-        rc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
-    }
-    DevBuf wide;      // a float32 panel under float64 values of A: widened (exactly) once
-    const double *panel = (const double *)b->d_values;
-    if (rc == CSRK_OK && b->val_type == CSRK_VAL_F32) {
-        rc = wide.alloc((size_t)b->nnz * 8);
-        if (rc == CSRK_OK) {
-            dense_widen_kernel<<<(unsigned)ceil_div(b->nnz, 256), 256>>>((const float *)b->d_values, wide.as<double>(), b->nnz);
-            rc = hipGetLastError() == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
-            panel = wide.as<double>();
-        }
-    }
-    if (rc == CSRK_OK && c_nnz > 0) rc = spmm_device(a, panel, k, k, (double *)c->d_values, k, nullptr, SpmmOut{row_base.as<int64_t>(), ref_order ? k : 0});
-    // (row_base, the widened panel and C's arrays are recycled in default-stream order: the launches above are on it)
-    if (rc == CSRK_OK && hipDeviceSynchronize() != hipSuccess) rc = CSRK_ERR_HIP;
-    if (rc != CSRK_OK) {
-        if (rc == CSRK_ERR_HIP) set_error("mult_ab (dense B): %s", hipGetErrorString(hipGetLastError()));
-        delete c;
-        return rc;
-    }
-    *out = c;
-    *taken = true;
-    return CSRK_OK;
+    CSRK_TRY(new_matrix(a->nrows, k, c_nnz, 0, CSRK_VAL_F64, &c));
+    const int rc = dense_c_fill(a, b, c, ref_order, t);
+    *taken = rc == CSRK_OK;
+    if (*taken) *out = c;
+    else delete c;
+    return rc;
 }
 
 }  // namespace csrk
@@ -1016,9 +1014,10 @@ int csrk_spmm_plan_stats(csrk_handle_t h, int64_t *out, int n)
     CSRK_REQUIRE(out && n >= 0, "out is NULL");
     std::lock_guard<std::mutex> lk(m->mu);
     const SpmmPlan *p = m->spmm_plan;
-    const int64_t v[9] = {p && p->hr_on ? 1 : 0, p ? p->hr_min : 0, p ? p->hr_n : 0, p ? p->hr_G : 0, p ? p->hr_R : 0,
-                          p ? p->hr_nnz : 0, p ? p->hr_tiles : 0, p ? p->n_segs : 0, p ? p->n_multi : 0};
-    for (int i = 0; i < n && i < 9; i++) out[i] = p && !p->hr_on && i >= 1 && i <= 6 ? 0 : v[i];
+    int64_t v[9];      // (no plan yet: every field reads 0)
+    spmmplan::plan_stats(p ? spmmplan::PlanCounts{p->hr_on, p->hr_min, p->hr_n, p->hr_G, p->hr_R, p->hr_nnz, p->hr_tiles, p->n_segs, p->n_multi}
+                           : spmmplan::PlanCounts{}, v);
+    for (int i = 0; i < n && i < 9; i++) out[i] = v[i];
     return CSRK_OK;
 }
 

@@ -939,14 +939,6 @@ static int device_cus(const Matrix *m, int *cus)
     return CSRK_OK;
 }
 
-// A builder templated on the matrix's value type, called with it as a constant: f(std::integral_constant<int, VT>).
-template <class F> static int with_val_type(int val_type, F &&f)
-{
-    if (val_type == CSRK_VAL_F64) return f(std::integral_constant<int, CSRK_VAL_F64>());
-    if (val_type == CSRK_VAL_F32) return f(std::integral_constant<int, CSRK_VAL_F32>());
-    return f(std::integral_constant<int, CSRK_VAL_NONE>());
-}
-
 // Both panels: `off` holds the scanned (block, row) pair counts.  Entries before each block's end -> the host -> tiles before
 // each block (spmvlayout::tile_starts: `items` per tile, `extra` items per block), in t0 and, for the kernels, in `bends`.
 static int block_tile_starts(const DevBuf &off, int32_t n, int32_t nb, int64_t items, int64_t extra, DevBuf &bends,

@@ -3,8 +3,10 @@ Inputs that put the dense-panel SpMM (csrc/spmm_dense.hip: spmm_seg_kernel and s
 build_hrows, spmm_hrows_kernel and spmm_hrows_reduce_kernel for the heavy ones) on the edges of its segments, buckets, tiles
 and column ranges, and the NumPy restatement of its plan (`Plan`) and of the order of its sums (`product`).  No GPU imports
 and nothing from the library: tests/test_spmm_cases_host.py checks that every case reaches the edges it claims and that the
-bit comparison is not vacuous; tests/test_gpu_spmm_edges.py runs the library on the same cases and compares
-csrk_spmm_plan_stats and the range table with the model before any value is compared.
+bit comparison is not vacuous; tests/test_spmm_plan_host.py compares `Plan` on every case with the library's own plan
+arithmetic (csrc/spmm_plan.h, which build_hrows and spmm_device call) in a host program; tests/test_gpu_spmm_edges.py runs
+the library on the same cases and compares csrk_spmm_plan_stats and the range table with the model before any value is
+compared.
 
 The plan, restated.  Inputs: row pointers, columns, ncols, the panel width k of the handle's first product, the switch
 CSRK_SPMM_HEAVY ('0', '1' or None), CSRK_SPMM_HEAVY_GROUPS, the device's CU count and the constants SEG = 64 entries per
@@ -54,7 +56,7 @@ def cdiv(a, b):
 
 
 def engage(ncols, k, mode):
-    "spmm_device: is the heavy form tried at all (mode: CSRK_SPMM_HEAVY)"
+    "spmmplan::heavy_engaged: is the heavy form tried at all (mode: CSRK_SPMM_HEAVY)"
     return mode != '0' and (mode == '1' or int(ncols) * int(k) * 8 > ENGAGE_BYTES)
 
 
@@ -66,7 +68,7 @@ def wg_place(b, G, R, by_xcd=None):
 
 
 class Plan:
-    "the dense-panel plan of a matrix as build_hrows and build_mm_plan make it"
+    "the dense-panel plan of a matrix as build_hrows (spmmplan::choose_heavy, balance_ranges) and build_mm_plan make it"
 
     def __init__(self, rowptrs, colinds, ncols, k, mode, groups=0, cus=CUS, hr_rows=HR_ROWS, waves=WAVES, tile=TILE, seg=SEG,
                  maxg=MAXG, floor=None, tile_cost=TILE_COST):
@@ -140,7 +142,7 @@ class Plan:
         key = (self.h_tile * G + self.group[self.h_rank]) * waves + self.wave[self.h_rank]
         self.bucket_len = np.bincount(key, minlength=n_buckets).reshape(n_tiles, G, waves)
         tot = np.concatenate([[0], np.cumsum(np.bincount(self.h_tile, minlength=n_tiles))])
-        # column ranges: the host loop of build_hrows, literally (float arithmetic)
+        # column ranges: the loop of spmmplan::balance_ranges, literally (float arithmetic)
         tile_cost = tile_cost * G
         total_cost = float(nnz_h) + float(tile_cost) * float(n_tiles)
         rng_ = [0] * (R + 1)

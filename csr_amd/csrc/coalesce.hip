@@ -21,10 +21,9 @@
 // Every slot is counted, nothing is appended in arrival order and no atomic touches a value: the result is a function of
 // (h, dup).  Column indices are compared and copied, never used as addresses.
 #include "result.h"
+#include "sort.h"
 
 namespace csrk {
-
-int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 
 static thread_local int g_coalesce_route = 0;
 
@@ -222,15 +221,12 @@ static int coalesce_impl(Matrix *m, int dup, int *route, Matrix **out)
         return m->ptr64 ? merge_any<int64_t>(m, m->d_colinds, m->d_values, m->val_type, dup, out)
                         : merge_any<int32_t>(m, m->d_colinds, m->d_values, m->val_type, dup, out);
     }
-    // Sorting every row by column, stably, is what two stable transposes do (csrk_order_columns): t2 has h's row pointers,
-    // the columns ascending and, among equal columns, h's storage order; its values are float64 (float32 widened exactly).
+    // Every row sorted by column, stably (sorted_rows_copy, as csrk_order_columns): t2 has h's row pointers, the columns
+    // ascending and, among equal columns, h's storage order; its values are float64 (float32 widened exactly).
     *route = 2;
-    Matrix *t1 = nullptr, *t2 = nullptr;
-    CSRK_TRY(transpose_matrix(m, 1, &t1, nullptr));
-    int rc = transpose_matrix(t1, 1, &t2, nullptr);
-    delete t1;
-    if (rc != CSRK_OK) return rc;
-    rc = m->ptr64 ? merge_any<int64_t>(m, t2->d_colinds, t2->d_values, t2->val_type, dup, out)
+    Matrix *t2 = nullptr;
+    CSRK_TRY(sorted_rows_copy(m, &t2));
+    const int rc = m->ptr64 ? merge_any<int64_t>(m, t2->d_colinds, t2->d_values, t2->val_type, dup, out)
                   : merge_any<int32_t>(m, t2->d_colinds, t2->d_values, t2->val_type, dup, out);
     delete t2;                                        // (merge_impl drained the device)
     return rc;

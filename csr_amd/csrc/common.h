@@ -172,8 +172,8 @@ int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t n, hipStream_t s
 // Widen int32 counts while scanning (used when the output pointer type is int64).
 int exclusive_scan_i32_to_i64(const int32_t *in, int64_t *out, int64_t n, hipStream_t s);
 
-// Stable LSD radix sort of (key, payload...) records, used by transpose / order_columns.
-// See radix.hip.
+// Stable LSD radix sort of (key, payload...) records, used by transpose / from_coo / order_columns: transpose.hip, its
+// host decisions in radix_plan.h, what it offers the other translation units in sort.h.
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

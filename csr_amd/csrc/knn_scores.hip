@@ -34,12 +34,11 @@
 // Column indices are compared, never used as addresses; every wavefront stays whole inside the loops that ballot and shuffle.
 #include "device_loads.h"
 #include "result.h"
+#include "sort.h"
 
 #include <functional>
 
 namespace csrk {
-
-int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 
 constexpr int KS_LANES = 16;                    // lanes that share one target's walk = model entries per step
 constexpr int KS_THREADS = 256;

@@ -20,12 +20,11 @@
 //                                former 4.0 ms of kernels on the headline matrix, bound by its longest row on one CU).
 // HBM traffic: values 1 read + 1 write (A, B), 2 reads + 1 write (C); row pointers once; norms once.
 #include "result.h"
+#include "sort.h"
 
 #include <atomic>
 
 namespace csrk {
-
-int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 
 __device__ __forceinline__ double wsum(double v)
 {
@@ -879,19 +878,15 @@ int csrk_filter_zeros(csrk_handle_t h, csrk_handle_t *out)
     return CSRK_OK;
 }
 
-// Sorting every row by column, stably, is what two stable transposes do: the first orders
-// entries by (col, source position), the second by (row, col, source position).
+// Every row sorted by column, stably (sorted_rows_copy: two stable transposes), copied back over the columns and values.
 int csrk_order_columns(csrk_handle_t h)
 {
     Matrix *m = from_handle(h);
     if (!m) return CSRK_ERR_INVALID;
     if (m->nnz == 0) return CSRK_OK;
     std::lock_guard<std::mutex> lk(m->mu);
-    Matrix *t1 = nullptr, *t2 = nullptr;
-    CSRK_TRY(transpose_matrix(m, 1, &t1, nullptr));
-    int rc = transpose_matrix(t1, 1, &t2, nullptr);
-    delete t1;
-    if (rc != CSRK_OK) return rc;
+    Matrix *t2 = nullptr;
+    CSRK_TRY(sorted_rows_copy(m, &t2));
     hipError_t e = hipMemcpy(m->d_colinds, t2->d_colinds, (size_t)m->nnz * 4, hipMemcpyDeviceToDevice);
     if (e == hipSuccess && m->val_type == CSRK_VAL_F64)
         e = hipMemcpy(m->d_values, t2->d_values, (size_t)m->nnz * 8, hipMemcpyDeviceToDevice);

@@ -37,12 +37,12 @@
 #include <memory>
 
 #include "common.h"
+#include "sort.h"
 #include "spgemm_plan.h"
 #include "wave.h"
 
 namespace csrk {
 
-int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s);   // transpose.hip
 bool spgemm_reference_order_wanted();                                            // spgemm_order.hip
 int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products);
 void spgemm_order_limits(int64_t out[5]);

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "device_loads.h"
 #include "panel.h"
+#include "sort.h"
 #include "spmm_plan.h"
 
 #include <cstdio>
@@ -593,9 +594,6 @@ static int build_mm_plan(Matrix *m, SpmmPlan *p, hipStream_t s)
     }
     return CSRK_OK;
 }
-
-int stable_sort_records_f64(const int32_t *keys, const int32_t *payload, const double *vals, int64_t n, int32_t key_range,
-                            int64_t payload_range, int64_t *out_ptr, int32_t *out_payload, double *out_vals, hipStream_t s);   // transpose.hip
 
 // the file's knobs (spmm_plan.h), read where a plan is about to be built and at the top of spgemm_dense_b: the tests
 // change them between two handles, so nothing is kept across builds

@@ -28,16 +28,18 @@
 // (a chunk never spans two low digits), so the exclusive scan of the pass-2 digit table IS the output row pointers:
 // rowptr[hi * 256 + lo] = (records of smaller high digits) + (records of high digit hi in the chunks before low digit
 // lo's run).  No sorted-key array is written or read.
+//
+// The host side (below the kernels) takes every decision -- route, sizes, grids, pass schedule -- from radix_plan.h.
+#include <initializer_list>
+#include <memory>
+#include <utility>
+
 #include "common.h"
+#include "radix_plan.h"      // RX_THREADS, RX_ROUNDS, RX_CHUNK, RX_HC, RXS_THREADS, RXS_IPT
+#include "sort.h"
 
 namespace csrk {
 
-#ifndef CSRK_RX_THREADS
-#define CSRK_RX_THREADS 512
-#endif
-constexpr int RX_THREADS = CSRK_RX_THREADS;
-constexpr int RX_ROUNDS = 8;
-constexpr int RX_CHUNK = RX_THREADS * RX_ROUNDS;     // 4096 records per workgroup (8192: 0.67 vs 0.65 ms)
 constexpr int RX_WAVES = RX_THREADS / WAVE;
 constexpr int RX_WSPAN = WAVE * RX_ROUNDS;            // 512 consecutive records per wavefront
 
@@ -91,7 +93,6 @@ __device__ __forceinline__ int64_t rx_chunk_of(int64_t b, int64_t n_chunks)
 // are aligned to the previous pass's runs; without them chunk c is records [c * RX_CHUNK, (c + 1) * RX_CHUNK))
 // One workgroup counts RX_HC consecutive chunks: all their keys are requested before the first LDS atomic (a workgroup
 // per chunk was a load -> wait -> 4096 LDS atomics -> store chain per 16 KB of keys: 2.5 TB/s).
-constexpr int RX_HC = 4;
 __global__ __launch_bounds__(RX_THREADS) void rx_hist_kernel(const int32_t *__restrict__ keys, int64_t n, int shift,
                                                             int64_t n_chunks, int64_t *__restrict__ table,
                                                             const int64_t *__restrict__ cstart, const int32_t *__restrict__ ccnt)
@@ -130,8 +131,6 @@ __global__ __launch_bounds__(RX_THREADS) void rx_hist_kernel(const int32_t *__re
 // table[d][c] (digit-major) -> exclusive prefix inside digit d's row (in place) and total[d]; the scatter
 // kernel adds the exclusive scan of the 256 totals itself.  One workgroup per digit, one launch -- instead
 // of a generic three-launch device scan of the 256 * n_chunks counts.
-constexpr int RXS_THREADS = 1024;
-constexpr int RXS_IPT = 8;
 __global__ __launch_bounds__(RXS_THREADS) void rx_scan_kernel(int64_t *__restrict__ table, int64_t n_chunks,
                                                              int64_t *__restrict__ total)
 {
@@ -456,177 +455,189 @@ __global__ __launch_bounds__(256) void rx_rowptr_from_table_kernel(const int64_t
     out_ptr[c] = (P)(s_before[hi] + in_row);
 }
 
-// Stable sort of n records by a key in [0, key_range): payload (int32) -> out_payload, values (widened
-// to float64) -> out_vals, and the run starts of every key -> out_ptr[0..key_range].  FROM_CSR: the records
-// are the entries of a CSR matrix (keys = its colinds, payload = the entry's row, from `rp`); otherwise
-// keys / payload / values are the given device arrays (COO ingest).
-template <class P, int VT, bool FROM_CSR>
-static int sort_records(const int32_t *keys, const int32_t *payload, const void *vals, const P *rp, int32_t rp_rows,
-                        int64_t n, int32_t key_range, int64_t payload_range, P *out_ptr, int32_t *out_payload,
-                        double *out_vals, hipStream_t s)
+// ---- host side: sort_records and its steps ------------------------------------------------------------------------------
+// Stable sort of n records by a key in [0, key_range): payload (int32) -> out_payload, values (widened to float64) ->
+// out_vals, and the run starts of every key -> out_ptr[0 .. key_range]; out_ptr is required.  sort_records<.., FROM_CSR =
+// true>: the records are the entries of a CSR matrix (keys = its colinds, payload = the entry's row, from the rp_rows + 1
+// pointers `rp`); otherwise keys / payload / values are the given device arrays (COO ingest).  rp and out_ptr are of the
+// width P that sort_records is instantiated for, vals of the type VT.
+struct SortCall {
+    const int32_t *keys, *payload;
+    const void *vals, *rp;
+    int32_t rp_rows, key_range;
+    int64_t n, payload_range;
+    void *out_ptr;
+    int32_t *out_payload;
+    double *out_vals;
+    hipStream_t s;
+};
+// a sort under way: the call, its plan (radix_plan.h: every decision), and the temporaries all routes use
+struct SortRun {
+    const SortCall &c;
+    const radixplan::Plan pl;
+    DevBuf table, total, rlo, rhi;
+};
+// one pass: its digit, its chunks (plain ones, or the aligned pass's descriptors), its tables, grids and records
+struct RxPass {
+    int shift;
+    int64_t chunks, *table, *total;
+    const int64_t *cstart;
+    const int32_t *ccnt;
+    unsigned hist_grid, scatter_grid;
+    const int32_t *keys_in, *rows_in;
+    const void *vals_in;
+    int32_t *keys_out, *rows_out;
+    double *vals_out;
+};
+
+// the pool requests of a step, in this order: each buffer the plan wants
+static int take(std::initializer_list<std::pair<DevBuf *, const radixplan::Buf *>> wants)
 {
-    constexpr bool HAS_V = VT != CSRK_VAL_NONE;
-    if (n == 0) {
-        if (out_ptr) CSRK_HIP(hipMemsetAsync(out_ptr, 0, (size_t)(key_range + 1) * sizeof(P), s));
-        CSRK_HIP(hipStreamSynchronize(s));
-        return CSRK_OK;
-    }
-    int bits = 0;
-    while (bits < 31 && (1ll << bits) < (int64_t)key_range) bits++;
-    int passes = bits <= 8 ? 1 : (bits + 7) / 8;
-    const int64_t n_chunks = ceil_div(n, RX_CHUNK);
-
-    DevBuf table, total, rlo, rhi, keyA, keyB, rowA, rowB, valA, valB, keyL;
-    const bool packed = passes == 2 && payload_range <= (1ll << 24);
-    const int64_t n_chunks2 = packed ? n_chunks + 256 : n_chunks;      // aligned chunks: at most one partial chunk per run more
-    CSRK_TRY(table.alloc((size_t)(256 * n_chunks2 + 1) * 8));
-    CSRK_TRY(total.alloc(256 * 8));
-    if (FROM_CSR) {
-        CSRK_TRY(rlo.alloc((size_t)n_chunks * 4));
-        CSRK_TRY(rhi.alloc((size_t)n_chunks * 4));
-        rx_rowbounds_kernel<P><<<(unsigned)ceil_div(n_chunks, 256), 256, 0, s>>>(rp, rp_rows, n, n_chunks, RX_CHUNK,
-                                                                              rlo.as<int32_t>(), rhi.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-    }
-    if (packed) {
-        // pass 1 (low digit): {high digit, payload} words + values; pass 2 (high digit) on chunks aligned to pass 1's runs
-        DevBuf cstart, ccnt, run0, total2;
-        CSRK_TRY(rowA.alloc((size_t)n * 4));
-        if (HAS_V) CSRK_TRY(valA.alloc((size_t)n * 8));
-        CSRK_TRY(cstart.alloc((size_t)n_chunks2 * 8));
-        CSRK_TRY(ccnt.alloc((size_t)n_chunks2 * 4));
-        CSRK_TRY(run0.alloc(257 * 8));
-        CSRK_TRY(total2.alloc(256 * 8));
-        double *v_mid = HAS_V ? valA.as<double>() : nullptr;
-        rx_hist_kernel<<<(unsigned)ceil_div(n_chunks, RX_HC), RX_THREADS, 0, s>>>(keys, n, 0, n_chunks, table.as<int64_t>(), nullptr, nullptr);
-        CSRK_LAUNCH_CHECK();
-        rx_scan_kernel<<<256, RXS_THREADS, 0, s>>>(table.as<int64_t>(), n_chunks, total.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        rx_scatter_kernel<P, VT, FROM_CSR ? 1 : 2, 1><<<(unsigned)(8 * ceil_div(n_chunks, 8)), RX_THREADS, 0, s>>>(
-            keys, payload, vals, rp, rp_rows, n, 0, n_chunks, table.as<int64_t>(), total.as<int64_t>(), rlo.as<int32_t>(),
-            rhi.as<int32_t>(), nullptr, rowA.as<int32_t>(), v_mid);
-        CSRK_LAUNCH_CHECK();
-        rx_align_kernel<<<1, 256, 0, s>>>(total.as<int64_t>(), n_chunks2, cstart.as<int64_t>(), ccnt.as<int32_t>(), run0.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        rx_hist_kernel<<<(unsigned)ceil_div(n_chunks2, RX_HC), RX_THREADS, 0, s>>>(rowA.as<int32_t>(), n, 24, n_chunks2, table.as<int64_t>(),
-                                                                 cstart.as<int64_t>(), ccnt.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        rx_scan_kernel<<<256, RXS_THREADS, 0, s>>>(table.as<int64_t>(), n_chunks2, total2.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        constexpr int VMID2 = HAS_V ? CSRK_VAL_F64 : CSRK_VAL_NONE;
-        rx_scatter_kernel<P, VMID2, 0, 2><<<(unsigned)(8 * ceil_div(n_chunks2, 8)), RX_THREADS, 0, s>>>(
-            rowA.as<int32_t>(), nullptr, v_mid, rp, rp_rows, n, 24, n_chunks2, table.as<int64_t>(), total2.as<int64_t>(), nullptr,
-            nullptr, nullptr, out_payload, out_vals, cstart.as<int64_t>(), ccnt.as<int32_t>());
-        CSRK_LAUNCH_CHECK();
-        rx_rowptr_from_table_kernel<P><<<(unsigned)ceil_div((int64_t)key_range + 1, 256), 256, 0, s>>>(
-            table.as<int64_t>(), total2.as<int64_t>(), run0.as<int64_t>(), n_chunks2, key_range, n, out_ptr);
-        CSRK_LAUNCH_CHECK();
-        CSRK_HIP(hipStreamSynchronize(s));   // temporaries go back to the pool on return
-        return CSRK_OK;
-    }
-    CSRK_TRY(keyL.alloc((size_t)n * 4));          // sorted keys of the last pass -> run starts
-    if (passes > 1) {
-        CSRK_TRY(keyA.alloc((size_t)n * 4));
-        CSRK_TRY(rowA.alloc((size_t)n * 4));
-        if (HAS_V) CSRK_TRY(valA.alloc((size_t)n * 8));
-    }
-    if (passes > 2) {
-        CSRK_TRY(keyB.alloc((size_t)n * 4));
-        CSRK_TRY(rowB.alloc((size_t)n * 4));
-        if (HAS_V) CSRK_TRY(valB.alloc((size_t)n * 8));
-    }
-
-    const int32_t *k_in = keys;
-    const int32_t *r_in = payload;
-    const void *v_in = vals;
-    for (int p = 0; p < passes; p++) {
-        const bool first = p == 0, last = p == passes - 1;
-        const int shift = 8 * p;
-        int32_t *k_out = last ? keyL.as<int32_t>() : ((p & 1) ? keyB.as<int32_t>() : keyA.as<int32_t>());
-        int32_t *r_out = last ? out_payload : ((p & 1) ? rowB.as<int32_t>() : rowA.as<int32_t>());
-        double *v_out = !HAS_V ? nullptr : (last ? out_vals : ((p & 1) ? valB.as<double>() : valA.as<double>()));
-        rx_hist_kernel<<<(unsigned)ceil_div(n_chunks, RX_HC), RX_THREADS, 0, s>>>(k_in, n, shift, n_chunks, table.as<int64_t>(), nullptr, nullptr);
-        CSRK_LAUNCH_CHECK();
-        rx_scan_kernel<<<256, RXS_THREADS, 0, s>>>(table.as<int64_t>(), n_chunks, total.as<int64_t>());
-        CSRK_LAUNCH_CHECK();
-        const unsigned grid = (unsigned)(8 * ceil_div(n_chunks, 8));
-        constexpr int VMID = HAS_V ? CSRK_VAL_F64 : CSRK_VAL_NONE;   // intermediates are float64
-#define RX_ARGS                                                                                                     \
-    k_in, r_in, v_in, rp, rp_rows, n, shift, n_chunks, table.as<int64_t>(), total.as<int64_t>(), rlo.as<int32_t>(),    \
-        rhi.as<int32_t>(), k_out, r_out, v_out
-        if (first)
-            rx_scatter_kernel<P, VT, FROM_CSR ? 1 : 2><<<grid, RX_THREADS, 0, s>>>(RX_ARGS);
-        else
-            rx_scatter_kernel<P, VMID, 0><<<grid, RX_THREADS, 0, s>>>(RX_ARGS);
-#undef RX_ARGS
-        CSRK_LAUNCH_CHECK();
-        k_in = k_out;
-        r_in = r_out;
-        v_in = v_out;
-    }
-    if (out_ptr) {
-        rowptr_from_sorted_keys<P><<<(unsigned)ceil_div(ceil_div(n + 1, 4), 256), 256, 0, s>>>(keyL.as<int32_t>(), n, key_range, out_ptr);
-        CSRK_LAUNCH_CHECK();
-    }
-    CSRK_HIP(hipStreamSynchronize(s));   // temporaries go back to the pool on return
+    for (const auto &w : wants)
+        if (w.second->used) CSRK_TRY(w.first->alloc(w.second->bytes));
     return CSRK_OK;
 }
+static int launched() { CSRK_LAUNCH_CHECK(); return CSRK_OK; }      // how every step ends: the launch just issued, checked
+// a route's temporaries go back to the pool when it returns: wait for the launches that use them first
+static int drain(hipStream_t s) { CSRK_HIP(hipStreamSynchronize(s)); return CSRK_OK; }
 
-template <class P, int VT>
-static int transpose_impl(Matrix *a, Matrix *t, hipStream_t s)
+// first / last source row of every chunk, for the first pass over a CSR
+template <class P> static int row_bounds(const SortRun &r)
 {
-    return sort_records<P, VT, true>(a->d_colinds, nullptr, a->d_values, (const P *)a->d_rowptrs, a->nrows, a->nnz,
-                                     a->ncols, a->nrows, (P *)t->d_rowptrs, t->d_colinds, (double *)t->d_values, s);
+    rx_rowbounds_kernel<P><<<r.pl.grid.bounds, 256, 0, r.c.s>>>((const P *)r.c.rp, r.c.rp_rows, r.c.n, r.pl.chunks, RX_CHUNK, r.rlo.as<int32_t>(),
+                                                                r.rhi.as<int32_t>());
+    return launched();
+}
+// a pass's tables: the digit counts of every chunk, then their scan (in place) and the digits' totals
+static int pass_tables(const SortRun &r, const RxPass &ps)
+{
+    rx_hist_kernel<<<ps.hist_grid, RX_THREADS, 0, r.c.s>>>(ps.keys_in, r.c.n, ps.shift, ps.chunks, ps.table, ps.cstart, ps.ccnt);
+    CSRK_LAUNCH_CHECK();
+    rx_scan_kernel<<<radixplan::SCAN_GRID, RXS_THREADS, 0, r.c.s>>>(ps.table, ps.chunks, ps.total);
+    return launched();
+}
+// a pass's stable scatter (MODE, PK: see rx_scatter_kernel); VT of a later pass: the intermediate values are float64
+template <int VT> constexpr int RX_VMID = VT != CSRK_VAL_NONE ? CSRK_VAL_F64 : CSRK_VAL_NONE;
+template <class P, int VT, int MODE, int PK = 0> static int pass_scatter(const SortRun &r, const RxPass &ps)
+{
+    rx_scatter_kernel<P, VT, MODE, PK><<<ps.scatter_grid, RX_THREADS, 0, r.c.s>>>(
+        ps.keys_in, ps.rows_in, ps.vals_in, (const P *)r.c.rp, r.c.rp_rows, r.c.n, ps.shift, ps.chunks, ps.table, ps.total, r.rlo.as<int32_t>(),
+        r.rhi.as<int32_t>(), ps.keys_out, ps.rows_out, ps.vals_out, ps.cstart, ps.ccnt);
+    return launched();
+}
+// the packed route between its passes: pass 2's chunk descriptors from pass 1's digit totals (the runs' lengths)
+static int align_chunks(const SortRun &r, const int64_t *total1, const DevBuf &cstart, const DevBuf &ccnt, const DevBuf &run0)
+{
+    rx_align_kernel<<<radixplan::ALIGN_GRID, 256, 0, r.c.s>>>(total1, r.pl.chunks2, cstart.as<int64_t>(), ccnt.as<int32_t>(), run0.as<int64_t>());
+    return launched();
+}
+// the run starts: off the aligned pass's scanned table, or off the sorted keys
+template <class P> static int rowptrs_from_table(const SortRun &r, const RxPass &p2, const DevBuf &run0)
+{
+    rx_rowptr_from_table_kernel<P><<<r.pl.grid.ptr_table, 256, 0, r.c.s>>>(p2.table, p2.total, run0.as<int64_t>(), p2.chunks, r.c.key_range, r.c.n,
+                                                                          (P *)r.c.out_ptr);
+    return launched();
+}
+template <class P> static int rowptrs_from_keys(const SortRun &r, const DevBuf &sorted_keys)
+{
+    rowptr_from_sorted_keys<P><<<r.pl.grid.ptr_keys, 256, 0, r.c.s>>>(sorted_keys.as<int32_t>(), r.c.n, r.c.key_range, (P *)r.c.out_ptr);
+    return launched();
 }
 
-// Stable sort of the int32 payloads by int32 keys in [0, key_range) -- the same radix passes, structure only.  Exposed to
-// spgemm_order.hip (the reference's output order of mult_ab).
-int stable_sort_payload_by_key(const int32_t *keys, const int32_t *payload, int64_t n, int32_t key_range,
-                               int64_t payload_range, int32_t *out_payload, hipStream_t s)
+// The packed two-pass route (see the file header).  Pass 1 (low digit) writes {high digit, payload} words + values; pass 2
+// (high digit) runs on chunks aligned to pass 1's runs, and its scanned table is the run starts.
+template <class P, int VT, bool FROM_CSR> static int sort_packed(const SortRun &r)
 {
-    // (the run starts are not wanted: with a key range of 2^30 they would be 8 GB)
-    DevBuf ptrs;
-    const bool packed_route = key_range > 256 && key_range <= 65536 && payload_range <= (1ll << 24);      // (that route derives them anyway)
-    if (packed_route) CSRK_TRY(ptrs.alloc((size_t)((int64_t)key_range + 1) * 8));
-    return sort_records<int64_t, CSRK_VAL_NONE, false>(keys, payload, nullptr, (const int64_t *)nullptr, 0, n, key_range,
-                                                       payload_range, packed_route ? ptrs.as<int64_t>() : (int64_t *)nullptr,
-                                                       out_payload, nullptr, s);
+    const SortCall &c = r.c;
+    DevBuf word, valA, cstart, ccnt, run0, total2;
+    CSRK_TRY(take({{&word, &r.pl.rowA}, {&valA, &r.pl.valA}, {&cstart, &r.pl.cstart}, {&ccnt, &r.pl.ccnt}, {&run0, &r.pl.run0}, {&total2, &r.pl.total2}}));
+    const RxPass p1{0, r.pl.chunks, r.table.as<int64_t>(), r.total.as<int64_t>(), nullptr, nullptr, r.pl.grid.hist, r.pl.grid.scatter,
+                    c.keys, c.payload, c.vals, nullptr, word.as<int32_t>(), valA.as<double>()};
+    const RxPass p2{RX_PACKED_SHIFT, r.pl.chunks2, r.table.as<int64_t>(), total2.as<int64_t>(), cstart.as<int64_t>(), ccnt.as<int32_t>(),
+                    r.pl.grid.hist2, r.pl.grid.scatter2, p1.rows_out, nullptr, p1.vals_out, nullptr, c.out_payload, c.out_vals};
+    CSRK_TRY(pass_tables(r, p1));
+    CSRK_TRY((pass_scatter<P, VT, FROM_CSR ? 1 : 2, 1>(r, p1)));
+    CSRK_TRY(align_chunks(r, p1.total, cstart, ccnt, run0));
+    CSRK_TRY(pass_tables(r, p2));
+    CSRK_TRY((pass_scatter<P, RX_VMID<VT>, 0, 2>(r, p2)));
+    CSRK_TRY(rowptrs_from_table<P>(r, p2, run0));
+    return drain(c.s);
 }
 
-// Stable sort of (key, int32 payload, float64 value) records by key in [0, key_range): the sorted payloads and values,
-// and the run start of every key in out_ptr[0 .. key_range] (the COO-ingest form of the radix passes).  Exposed to
-// spmm_dense.hip (the heavy rows' entries bucketed by (column tile, row group, wavefront)).
+// The plain routes: one to four passes in the plan's schedule -- the first from the caller's arrays, the last into the sorted
+// keys (keyL) and the caller's outputs, A and B in turn between them --, then the run starts from the sorted keys.
+template <class P, int VT, bool FROM_CSR> static int sort_plain(const SortRun &r)
+{
+    const SortCall &c = r.c;
+    DevBuf keyA, keyB, rowA, rowB, valA, valB, keyL;
+    CSRK_TRY(take({{&keyL, &r.pl.keyL}, {&keyA, &r.pl.keyA}, {&rowA, &r.pl.rowA}, {&valA, &r.pl.valA}, {&keyB, &r.pl.keyB}, {&rowB, &r.pl.rowB},
+                   {&valB, &r.pl.valB}}));
+    // the record sets by radixplan::Where: Source (never written), A, B, Last
+    int32_t *const keys[4] = {nullptr, keyA.as<int32_t>(), keyB.as<int32_t>(), keyL.as<int32_t>()};
+    int32_t *const rows[4] = {nullptr, rowA.as<int32_t>(), rowB.as<int32_t>(), c.out_payload};
+    double *const vals[4] = {nullptr, valA.as<double>(), valB.as<double>(), VT != CSRK_VAL_NONE ? c.out_vals : nullptr};
+    for (int p = 0; p < r.pl.passes; p++) {
+        const radixplan::Pass &s = r.pl.pass[p];
+        const RxPass ps{s.shift, r.pl.chunks, r.table.as<int64_t>(), r.total.as<int64_t>(), nullptr, nullptr, r.pl.grid.hist, r.pl.grid.scatter,
+                        s.first ? c.keys : keys[s.src], s.first ? c.payload : rows[s.src], s.first ? c.vals : vals[s.src],
+                        keys[s.dst], rows[s.dst], vals[s.dst]};
+        CSRK_TRY(pass_tables(r, ps));
+        if (s.first)
+            CSRK_TRY((pass_scatter<P, VT, FROM_CSR ? 1 : 2>(r, ps)));
+        else
+            CSRK_TRY((pass_scatter<P, RX_VMID<VT>, 0>(r, ps)));
+    }
+    CSRK_TRY(rowptrs_from_keys<P>(r, keyL));
+    return drain(c.s);
+}
+
+template <class P, int VT, bool FROM_CSR> static int sort_records(const SortCall &c)
+{
+    SortRun r{c, radixplan::radix_plan(c.n, c.key_range, c.payload_range, FROM_CSR, VT != CSRK_VAL_NONE)};
+    if (r.pl.route == radixplan::Route::Empty) {
+        CSRK_HIP(hipMemsetAsync(c.out_ptr, 0, r.pl.ptr_slots * sizeof(P), c.s));
+        return drain(c.s);
+    }
+    CSRK_TRY(take({{&r.table, &r.pl.table}, {&r.total, &r.pl.total}, {&r.rlo, &r.pl.rlo}, {&r.rhi, &r.pl.rhi}}));
+    if (r.pl.rlo.used) CSRK_TRY(row_bounds<P>(r));
+    return r.pl.packed ? sort_packed<P, VT, FROM_CSR>(r) : sort_plain<P, VT, FROM_CSR>(r);      // (each ends with drain())
+}
+
+// The ladder: row-pointer width x value type -> sort_records<P, VT, FROM_CSR>
+template <bool FROM_CSR> static int sort_records_as(int ptr64, int val_type, const SortCall &c)
+{
+    return with_val_type(val_type, [&](auto vt) -> int {
+        return ptr64 ? sort_records<int64_t, decltype(vt)::value, FROM_CSR>(c) : sort_records<int32_t, decltype(vt)::value, FROM_CSR>(c);
+    });
+}
+
 int stable_sort_records_f64(const int32_t *keys, const int32_t *payload, const double *vals, int64_t n, int32_t key_range,
                             int64_t payload_range, int64_t *out_ptr, int32_t *out_payload, double *out_vals, hipStream_t s)
 {
-    return sort_records<int64_t, CSRK_VAL_F64, false>(keys, payload, vals, (const int64_t *)nullptr, 0, n, key_range,
-                                                      payload_range, out_ptr, out_payload, out_vals, s);
+    return sort_records<int64_t, CSRK_VAL_F64, false>({keys, payload, vals, nullptr, 0, key_range, n, payload_range, out_ptr, out_payload, out_vals, s});
 }
 
-// Transpose `a` into a new matrix.  Exposed to the other translation units (spgemm_abt,
-// order_columns).
 int transpose_matrix(Matrix *a, int with_values, Matrix **out, hipStream_t s)
 {
-    int vt = (with_values && a->val_type != CSRK_VAL_NONE) ? CSRK_VAL_F64 : CSRK_VAL_NONE;
-    Matrix *t = nullptr;
-    CSRK_TRY(new_matrix(a->ncols, a->nrows, a->nnz, a->ptr64, vt, &t));
-    int rc;
-    int in_vt = vt == CSRK_VAL_NONE ? CSRK_VAL_NONE : a->val_type;
-    if (a->ptr64) {
-        if (in_vt == CSRK_VAL_F64) rc = transpose_impl<int64_t, CSRK_VAL_F64>(a, t, s);
-        else if (in_vt == CSRK_VAL_F32) rc = transpose_impl<int64_t, CSRK_VAL_F32>(a, t, s);
-        else rc = transpose_impl<int64_t, CSRK_VAL_NONE>(a, t, s);
-    } else {
-        if (in_vt == CSRK_VAL_F64) rc = transpose_impl<int32_t, CSRK_VAL_F64>(a, t, s);
-        else if (in_vt == CSRK_VAL_F32) rc = transpose_impl<int32_t, CSRK_VAL_F32>(a, t, s);
-        else rc = transpose_impl<int32_t, CSRK_VAL_NONE>(a, t, s);
-    }
-    if (rc != CSRK_OK) {
-        delete t;
-        return rc;
-    }
-    *out = t;
+    const int vt = (with_values && a->val_type != CSRK_VAL_NONE) ? CSRK_VAL_F64 : CSRK_VAL_NONE;
+    const int in_vt = vt == CSRK_VAL_NONE ? CSRK_VAL_NONE : a->val_type;
+    Matrix *made = nullptr;
+    CSRK_TRY(new_matrix(a->ncols, a->nrows, a->nnz, a->ptr64, vt, &made));
+    std::unique_ptr<Matrix> t(made);
+    // keys = the columns (key range ncols), payload = the source row, recovered from the row pointers (payload range nrows)
+    CSRK_TRY(sort_records_as<true>(a->ptr64, in_vt, {a->d_colinds, nullptr, a->d_values, a->d_rowptrs, a->nrows, a->ncols, a->nnz, a->nrows,
+                                                     t->d_rowptrs, t->d_colinds, (double *)t->d_values, s}));
+    *out = t.release();
     return CSRK_OK;
+}
+
+int sorted_rows_copy(Matrix *m, Matrix **out)
+{
+    Matrix *t1 = nullptr;
+    CSRK_TRY(transpose_matrix(m, 1, &t1, nullptr));
+    const int rc = transpose_matrix(t1, 1, out, nullptr);      // (sets *out on success only)
+    delete t1;
+    return rc;
 }
 
 }  // namespace csrk
@@ -637,6 +648,21 @@ __global__ void coo_cast_f64_to_f32(const double *__restrict__ in, float *__rest
 {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (float)in[i];       // exact: the doubles are widened floats
+}
+
+static int coo_upload(void *dev, const void *host, size_t bytes)
+{
+    const hipError_t e = bytes ? hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) set_error("host-to-device copy failed: %s", hipGetErrorString(e));
+    return e == hipSuccess ? CSRK_OK : CSRK_ERR_HIP;
+}
+// float32 values were sorted as float64 (the sort's only output type): back to the matrix's own type
+static int coo_values_to_f32(const double *v64, float *out, int64_t nnz)
+{
+    coo_cast_f64_to_f32<<<(unsigned)ceil_div(nnz, 256), 256>>>(v64, out, nnz);
+    if (hipDeviceSynchronize() == hipSuccess) return CSRK_OK;
+    set_error("from_coo value cast failed");
+    return CSRK_ERR_HIP;
 }
 
 // COO -> CSR: a stable sort of the entries by row is exactly the reference's counting sort
@@ -651,57 +677,29 @@ extern "C" int csrk_from_coo(int32_t nrows, int32_t ncols, int64_t nnz, const in
     CSRK_REQUIRE(val_type == CSRK_VAL_NONE || val_type == CSRK_VAL_F32 || val_type == CSRK_VAL_F64, "unknown val_type %d", val_type);
     CSRK_REQUIRE(val_type == CSRK_VAL_NONE || nnz == 0 || values, "values is NULL but val_type=%d", val_type);
     const int ptr64 = nnz > INT32_MAX;
-    Matrix *m = nullptr;
-    CSRK_TRY(new_matrix(nrows, ncols, nnz, ptr64, val_type, &m));
-    DevBuf d_rows, d_cols, d_vals, d_v64;
-    int rc = CSRK_OK;
     const size_t vb = val_type == CSRK_VAL_F64 ? 8 : 4;
-    do {
-        if ((rc = d_rows.alloc((size_t)nnz * 4)) != CSRK_OK) break;
-        if ((rc = d_cols.alloc((size_t)nnz * 4)) != CSRK_OK) break;
-        hipError_t e = hipSuccess;
-        if (nnz) e = hipMemcpy(d_rows.p, rows, (size_t)nnz * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && nnz) e = hipMemcpy(d_cols.p, cols, (size_t)nnz * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && val_type != CSRK_VAL_NONE) {
-            if ((rc = d_vals.alloc((size_t)nnz * vb)) != CSRK_OK) break;
-            if (nnz) e = hipMemcpy(d_vals.p, values, (size_t)nnz * vb, hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) {
-            set_error("host-to-device copy failed: %s", hipGetErrorString(e));
-            rc = CSRK_ERR_HIP;
-            break;
-        }
-        double *v_out = (double *)m->d_values;
-        if (val_type == CSRK_VAL_F32) {
-            if ((rc = d_v64.alloc((size_t)nnz * 8)) != CSRK_OK) break;
-            v_out = d_v64.as<double>();
-        }
-#define GO(P, VT)                                                                                                    \
-    rc = sort_records<P, VT, false>(d_rows.as<int32_t>(), d_cols.as<int32_t>(), d_vals.p, (const P *)nullptr, 0, nnz,   \
-                                    nrows, ncols, (P *)m->d_rowptrs, m->d_colinds, v_out, nullptr)
-        if (ptr64) {
-            if (val_type == CSRK_VAL_F64) GO(int64_t, CSRK_VAL_F64);
-            else if (val_type == CSRK_VAL_F32) GO(int64_t, CSRK_VAL_F32);
-            else GO(int64_t, CSRK_VAL_NONE);
-        } else {
-            if (val_type == CSRK_VAL_F64) GO(int32_t, CSRK_VAL_F64);
-            else if (val_type == CSRK_VAL_F32) GO(int32_t, CSRK_VAL_F32);
-            else GO(int32_t, CSRK_VAL_NONE);
-        }
-#undef GO
-        if (rc == CSRK_OK && val_type == CSRK_VAL_F32 && nnz) {
-            coo_cast_f64_to_f32<<<(unsigned)ceil_div(nnz, 256), 256>>>(d_v64.as<double>(), (float *)m->d_values, nnz);
-            if (hipDeviceSynchronize() != hipSuccess) {
-                set_error("from_coo value cast failed");
-                rc = CSRK_ERR_HIP;
-            }
-        }
-    } while (0);
-    if (rc != CSRK_OK) {
-        delete m;
-        return rc;
+    DevBuf d_rows, d_cols, d_vals, d_v64;      // (declared before the result: released after it, as ever)
+    Matrix *made = nullptr;
+    CSRK_TRY(new_matrix(nrows, ncols, nnz, ptr64, val_type, &made));
+    std::unique_ptr<Matrix> m(made);
+    CSRK_TRY(d_rows.alloc((size_t)nnz * 4));
+    CSRK_TRY(d_cols.alloc((size_t)nnz * 4));
+    CSRK_TRY(coo_upload(d_rows.p, rows, (size_t)nnz * 4));
+    CSRK_TRY(coo_upload(d_cols.p, cols, (size_t)nnz * 4));
+    if (val_type != CSRK_VAL_NONE) {
+        CSRK_TRY(d_vals.alloc((size_t)nnz * vb));
+        CSRK_TRY(coo_upload(d_vals.p, values, (size_t)nnz * vb));
     }
-    *out = to_handle(m);
+    double *v_out = (double *)m->d_values;
+    if (val_type == CSRK_VAL_F32) {
+        CSRK_TRY(d_v64.alloc((size_t)nnz * 8));
+        v_out = d_v64.as<double>();
+    }
+    // keys = the rows, payload = the columns
+    CSRK_TRY(sort_records_as<false>(ptr64, val_type, {d_rows.as<int32_t>(), d_cols.as<int32_t>(), d_vals.p, nullptr, 0, nrows, nnz, ncols,
+                                                      m->d_rowptrs, m->d_colinds, v_out, nullptr}));
+    if (val_type == CSRK_VAL_F32 && nnz) CSRK_TRY(coo_values_to_f32(d_v64.as<double>(), (float *)m->d_values, nnz));
+    *out = to_handle(m.release());
     return CSRK_OK;
 }
 

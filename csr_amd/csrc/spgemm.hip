@@ -38,14 +38,11 @@
 
 #include "common.h"
 #include "sort.h"
+#include "spgemm_order.h"
 #include "spgemm_plan.h"
 #include "wave.h"
 
 namespace csrk {
-
-bool spgemm_reference_order_wanted();                                            // spgemm_order.hip
-int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products);
-void spgemm_order_limits(int64_t out[5]);
 
 // csrk_spgemm_last_stats: what the calling thread's last general product did with its rows (include/csrk.h has the layout);
 // zeroed by every csrk_spgemm_ab / _abt, filled at the end of spgemm_run from what the driver holds on the host anyway

@@ -18,25 +18,32 @@
 //
 // Values are not touched: each keeps the bits the product kernels gave it.  tests/test_gpu_ops.py compares the result
 // with the reference's own raw arrays (tests/golden/spgemm.npz, c*_raw_*) bit for bit.
+//
+// The host side (below the kernels; DESIGN.md section 6, "The ordering pass's driver"): spgemm_apply_reference_order is a
+// list of named steps, each a launch or a copy, and decides nothing -- the LDS plan of the walks, the split of the listed
+// rows into tiers, every grid and every byte size are pure functions of spgemm_order_plan.h, which also holds the constants
+// the kernels share with them (tests/test_spgemm_order_plan_host.py).  spgemm_order.h declares what spgemm.hip and
+// spmm_dense.hip call.
 #include "common.h"
 #include "device_loads.h"
+#include "spgemm_order.h"
+#include "spgemm_order_plan.h"
 
-#include <algorithm>
 #include <atomic>
 #include <type_traits>
 
 namespace csrk {
 
+static_assert(soplan::LANES == WAVE, "spgemm_order_plan.h counts wavefronts of WAVE lanes");
+
 static std::atomic<int> g_spgemm_order{-1};      // -1: follow CSRK_SPGEMM_ORDER; 0 ascending; 1 reference
 
 // the reference's order unless the caller (csrk_spgemm_set_order(0)) or the environment (CSRK_SPGEMM_ORDER=ascending) asks
-// for ascending columns
+// for ascending columns (the environment is read on every call: tests/test_gpu_type_matrix.py changes it between products)
 bool spgemm_reference_order_wanted()
 {
     const int o = g_spgemm_order.load();
-    if (o >= 0) return o == 1;
-    const char *e = getenv("CSRK_SPGEMM_ORDER");
-    return !(e && (e[0] == 'a' || e[0] == 'A' || e[0] == '0'));
+    return (o >= 0 ? o : soplan::order_from_knob(getenv("CSRK_SPGEMM_ORDER"))) == 1;
 }
 
 // products of every row of A B: tp[i] = sum over the entries (i, j) of A of |B_j| (SUB lanes per row: sixteen when A's rows
@@ -62,15 +69,11 @@ __global__ __launch_bounds__(256) void so_row_products_kernel(const PA *__restri
     if (lane == 0) tp[i] = n;
 }
 
-constexpr int SO_LEAST = 64;                 // (2^6) rows of fewer products: SO_SUB lanes each, straight from the row number
-constexpr int SO_TINY = 256;                 // (2^8) rows of fewer products: SO_SUB lanes each, from the list
-constexpr int SO_WAVE = 1024;                // (2^10) rows of fewer products: a wavefront each, from the list
-constexpr int SO_MID = 4096;                 // (2^12) rows of fewer products: a 256-thread workgroup each; the others 1024 threads
-constexpr int SO_SUB = 16;
+// (SO_LEAST, SO_TINY, SO_WAVE, SO_MID, SO_SUB, SO_OCTAVES, SO_LDS_BYTES and the placing window: spgemm_order_plan.h, with every
+// host decision of this file)
 constexpr int SO_UNROLL = 8;                 // products a thread has in flight
 constexpr int SO_CHUNK = WAVE * SO_UNROLL;     // consecutive products a wavefront takes at a time
 constexpr int SO_PLACE_UNROLL = 8;           // entries a thread has in flight when they are placed
-constexpr int SO_LDS_BYTES = 150 * 1024;
 constexpr unsigned int SO_NONE = 0xffffffffu;
 
 // Diagnostic build only (-DCSRK_SO_STAMPS): clocks of thread 0 of every so_walk_kernel workgroup, summed per phase
@@ -87,7 +90,6 @@ __device__ unsigned long long g_so_stamps[8];
 // true places the rows behind the cursors the host made of the counts; inside an octave any order).  The count also
 // raises cursor[SO_OCTAVES] if some row will need its keys in memory (more than `cap` entries, or 2^32 products: only then
 // does the host allocate the key array).
-constexpr int SO_OCTAVES = 64;
 __global__ __launch_bounds__(256) void so_list_rows_kernel(const int64_t *__restrict__ tp, int32_t nrows, bool fill,
                                                           const int32_t *__restrict__ c_rp, int32_t cap,
                                                           int32_t *__restrict__ cursor, int32_t *__restrict__ list)
@@ -572,9 +574,6 @@ __global__ __launch_bounds__(THREADS) void so_walk_kernel(const PA *__restrict__
 // The rows so_walk_kernel left in key[] (more entries than its LDS holds, or 2^32 products): every entry's place from its
 // key as there, the bitmap a window of 2^19 product indices.  *bad is raised by a key outside the row's products (an entry
 // never discovered) or two equal keys.
-constexpr int SO_WIN_WORDS = 16384;          // 64 KB of bits + 64 KB of counts
-constexpr int SO_WIN = SO_WIN_WORDS * 32;
-constexpr int SO_PLACE_THREADS = 1024;
 constexpr int SO_OWN = SO_WIN_WORDS / SO_PLACE_THREADS;      // words a thread counts
 __global__ __launch_bounds__(SO_PLACE_THREADS) void so_place_kernel(const int32_t *__restrict__ c_rp, const int32_t *__restrict__ c_ci,
                                                              const double *__restrict__ c_vs, const int64_t *__restrict__ tp,
@@ -649,151 +648,201 @@ __global__ __launch_bounds__(SO_PLACE_THREADS) void so_place_kernel(const int32_
     if (tid == 0 && base != nc) atomicMax(bad, 1u);
 }
 
-// c = a b as the product kernels left it (ascending columns, int32 row pointers, float64 values): re-ordered in place
-int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products)
-{
-    const int64_t n = c->nnz;
-    if (n <= 1 || c->nrows == 0 || a->nnz == 0) return CSRK_OK;
-    CSRK_REQUIRE(!c->ptr64 && c->val_type == CSRK_VAL_F64, "product has an unexpected layout");
+// ---- host side: the steps of one pass, in the order they run (every decision: spgemm_order_plan.h) ---------------------------
+static_assert(soplan::walk_static_lds(soplan::LONG_THREADS, WAVE) <= SO_TABLES_BYTES,
+              "so_walk_kernel<.., 1024, ..>: s_bs, s_off, s_wave64, s_wave, s_take and s_found fit what the LDS plan keeps back");
+
+// the pass's temporaries in the order they are declared: they go back to the pool in the reverse one
+struct SoBuffers {
     DevBuf key, tp_own, flag, oci, ovs, rows, cursor;
+};
+
+// what every launch of one pass repeats, and the two plans the steps read
+struct SoPass {
+    const void *a_rp, *b_rp;             // PA and PB: int32 or int64 row pointers
+    const int32_t *a_ci, *b_ci, *c_rp, *c_ci;
+    const double *c_vs;
+    int32_t a_nrows, c_ncols;
+    int64_t a_nnz, c_nnz;
+    bool counted;                        // tp is the product kernels' own count
+    int64_t *tp;                         // products of every row
+    int32_t *rows, *cursor;              // the listed rows, longest first; the octave counters, then cursors
+    unsigned long long *key;             // keys of the rows LDS does not hold (nullptr: there is none)
+    int32_t *oci;
+    double *ovs;
+    unsigned int *bad;
+    soplan::LdsPlan lds;
+    soplan::Tiers tiers;                 // (the list step copies its cursors to the device from here)
+};
+
+// the temporaries, but for the keys, and the pass's view of the operands
+static int so_take_buffers(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products, SoBuffers &buf, SoPass &x)
+{
     // products of every row: the product kernels' own count when they made one (so_row_products_kernel: 33-60 us)
-    const bool counted = products && products->p && products->bytes >= (size_t)(a->nrows + 1) * 8;
-    if (!counted) CSRK_TRY(tp_own.alloc((size_t)(a->nrows + 1) * 8));
-    int64_t *const tp_p = counted ? products->as<int64_t>() : tp_own.as<int64_t>();
-    CSRK_TRY(flag.alloc(4));
-    CSRK_TRY(rows.alloc((size_t)a->nrows * 4 + 4));
-    CSRK_TRY(cursor.alloc((SO_OCTAVES + 1) * 4));
-    CSRK_TRY(oci.alloc((size_t)n * 4));
-    CSRK_TRY(ovs.alloc((size_t)n * 8));
-    CSRK_HIP(hipMemsetAsync(cursor.p, 0, (SO_OCTAVES + 1) * 4, nullptr));
-    CSRK_HIP(hipMemsetAsync(flag.p, 0, 4, nullptr));
-    // LDS of the 1024-thread walk (the device's own limit decides; 18 KB of it are the kernel's batch tables).  By column --
-    // 4 B per column of C and a bit -- when that leaves a window of 2^15 product indices at least and no row of B can hold
-    // 2^32 entries (32-bit indices inside a batch); else by entry, 8 B each, with a window of 2^16.  The 256-thread walk:
-    // rows of fewer than SO_MID products (and entries), by entry.
+    x.counted = products && soplan::products_counted(products->p, products->bytes, a->nrows);
+    if (!x.counted) CSRK_TRY(buf.tp_own.alloc(soplan::tp_bytes(a->nrows)));
+    CSRK_TRY(buf.flag.alloc(soplan::flag_bytes()));
+    CSRK_TRY(buf.rows.alloc(soplan::rows_bytes(a->nrows)));
+    CSRK_TRY(buf.cursor.alloc(soplan::cursor_bytes()));
+    CSRK_TRY(buf.oci.alloc(soplan::oci_bytes(c->nnz)));
+    CSRK_TRY(buf.ovs.alloc(soplan::ovs_bytes(c->nnz)));
+    CSRK_HIP(hipMemsetAsync(buf.cursor.p, 0, soplan::cursor_bytes(), nullptr));
+    CSRK_HIP(hipMemsetAsync(buf.flag.p, 0, soplan::flag_bytes(), nullptr));
+    x.a_rp = a->d_rowptrs, x.a_ci = a->d_colinds, x.a_nrows = a->nrows, x.a_nnz = a->nnz;
+    x.b_rp = b->d_rowptrs, x.b_ci = b->d_colinds;
+    x.c_rp = (const int32_t *)c->d_rowptrs, x.c_ci = c->d_colinds, x.c_vs = (const double *)c->d_values;
+    x.c_ncols = c->ncols, x.c_nnz = c->nnz;
+    x.tp = x.counted ? products->as<int64_t>() : buf.tp_own.as<int64_t>();
+    x.rows = buf.rows.as<int32_t>(), x.cursor = buf.cursor.as<int32_t>(), x.key = nullptr;
+    x.oci = buf.oci.as<int32_t>(), x.ovs = buf.ovs.as<double>(), x.bad = buf.flag.as<unsigned int>();
+    return CSRK_OK;
+}
+
+// the LDS of the two walks and the placing pass, from the device's own limit
+static int so_read_lds_plan(int64_t b_nnz, SoPass &x)
+{
     int lds_max = 0, dev = 0;
     CSRK_HIP(hipGetDevice(&dev));
     CSRK_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-    const int64_t budget = std::min<int64_t>(SO_LDS_BYTES, (int64_t)lds_max - 18 * 1024);
-    const int64_t by_col = (((int64_t)c->ncols + 31) / 32 * 2 + c->ncols) * 4;
-    int32_t win_cols = 0;
-    for (int32_t w = 16384; w >= 1024; w >>= 1)
-        if (by_col + (int64_t)w * 8 <= budget) {
-            win_cols = w;
-            break;
-        }
-    const bool cols_mode = win_cols > 0 && b->nnz < 0xffffffffll;
-    const int32_t win_long = cols_mode ? win_cols : 2048;
-    const int32_t cap_long = cols_mode ? INT32_MAX : (int32_t)std::max<int64_t>(0, (budget - (int64_t)win_long * 8) / 8);
-    const size_t lds_long = cols_mode ? (size_t)(by_col + (int64_t)win_long * 8) : (size_t)cap_long * 8 + (size_t)win_long * 8;
-    const int32_t win_mid = SO_MID / 32, cap_mid = SO_MID;
-    const size_t lds_mid = (size_t)cap_mid * 8 + (size_t)win_mid * 8;
-    const size_t lds_place = (size_t)SO_WIN_WORDS * 8;
-    CSRK_REQUIRE((int64_t)lds_place + 2048 <= lds_max && cap_long >= SO_MID, "device has too little LDS for the ordering pass");
-    const unsigned gr = (unsigned)ceil_div(a->nrows, 256);
-    const unsigned gs = (unsigned)ceil_div((int64_t)a->nrows * SO_SUB, 256);
-    int32_t n_long = 0, n_mid = 0, n_wave = 0, n_small = 0;      // listed rows of at least SO_MID products (first in the list), SO_WAVE, SO_TINY, SO_LEAST
-    int32_t octaves[SO_OCTAVES + 1];                 // ([SO_OCTAVES]: some row needs its keys in memory)
-    unsigned long long *key_p = nullptr;
-    int32_t *const oci_p = oci.as<int32_t>();
-    double *const ovs_p = ovs.as<double>();
-    unsigned int *const bad_p = flag.as<unsigned int>();
-    const int32_t *const c_rp = (const int32_t *)c->d_rowptrs;
-    const double *const c_vs = (const double *)c->d_values;
-#define WALK_GO(PA, PB, THREADS, COLS, GRID, LDS, CAP, WIN, LIST)                                                      \
-    do {                                                                                                               \
-        CSRK_HIP(hipFuncSetAttribute((const void *)so_walk_kernel<PA, PB, THREADS, COLS>,                              \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS)));                         \
-        so_walk_kernel<PA, PB, THREADS, COLS><<<(unsigned)(GRID), THREADS, LDS>>>(                                     \
-            (const PA *)a->d_rowptrs, a->d_colinds, (const PB *)b->d_rowptrs, b->d_colinds, c_rp, c->d_colinds, c_vs,  \
-            tp_p, c->ncols, CAP, WIN, LIST, key_p, oci_p, ovs_p, bad_p);                                   \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-    } while (0)
-#define ORDER(PA, PB)                                                                                                  \
-    do {                                                                                                               \
-        if (counted) {                                                                                                 \
-        } else if (a->nnz / a->nrows >= 32)                                                                            \
-            so_row_products_kernel<PA, PB, WAVE><<<(unsigned)ceil_div((int64_t)a->nrows * WAVE, 256), 256>>>(          \
-                (const PA *)a->d_rowptrs, a->d_colinds, a->nrows, (const PB *)b->d_rowptrs, tp_p);         \
-        else                                                                                                           \
-            so_row_products_kernel<PA, PB, 16><<<(unsigned)ceil_div((int64_t)a->nrows * 16, 256), 256>>>(              \
-                (const PA *)a->d_rowptrs, a->d_colinds, a->nrows, (const PB *)b->d_rowptrs, tp_p);         \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-        so_list_rows_kernel<<<gr, 256>>>(tp_p, a->nrows, false, c_rp, cap_long, cursor.as<int32_t>(), nullptr); \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-        so_tiny_kernel<PA, PB, SO_LEAST, SO_SUB><<<gs, 256>>>((const PA *)a->d_rowptrs, a->d_colinds, a->nrows,                \
-                                                      (const PB *)b->d_rowptrs, b->d_colinds, c_rp, c->d_colinds, c_vs, \
-                                                      tp_p, nullptr, 0, oci_p, ovs_p, bad_p);              \
-        CSRK_LAUNCH_CHECK();                                                                                           \
-        CSRK_HIP(hipMemcpy(octaves, cursor.p, sizeof octaves, hipMemcpyDeviceToHost));                                 \
-        int32_t listed = 0;                                                                                            \
-        for (int o = 0; o < SO_OCTAVES; o++) {       /* (63 - o = the octave: rows of [2^(63-o), 2^(64-o)) products) */ \
-            const int32_t cnt = octaves[o];                                                                            \
-            octaves[o] = listed;                                                                                       \
-            listed += cnt;                                                                                             \
-            if (63 - o >= 12) n_long = listed;       /* (SO_MID = 2^12) */                                             \
-            if (63 - o >= 10) n_mid = listed - n_long; /* (SO_WAVE = 2^10) */                                          \
-            if (63 - o >= 8) n_wave = listed - n_long - n_mid; /* (SO_TINY = 2^8) */                                   \
-        }                                                                                                              \
-        n_small = listed - n_long - n_mid - n_wave;                                                                    \
-        if (octaves[SO_OCTAVES]) {                   /* (8 B per entry of C: only for the rows that do not fit LDS) */  \
-            CSRK_TRY(key.alloc((size_t)n * 8));                                                                        \
-            key_p = key.as<unsigned long long>();                                                                      \
-        }                                                                                                              \
-        if (listed > 0) {                                                                                              \
-            CSRK_HIP(hipMemcpyAsync(cursor.p, octaves, sizeof octaves, hipMemcpyHostToDevice, nullptr));               \
-            so_list_rows_kernel<<<gr, 256>>>(tp_p, a->nrows, true, c_rp, cap_long, cursor.as<int32_t>(),   \
-                                             rows.as<int32_t>());                                                      \
-            CSRK_LAUNCH_CHECK();                                                                                       \
-        }                                                                                                              \
-        if (n_long > 0) {                                                                                              \
-            if (cols_mode) WALK_GO(PA, PB, 1024, true, n_long, lds_long, cap_long, win_long, rows.as<int32_t>());      \
-            else WALK_GO(PA, PB, 1024, false, n_long, lds_long, cap_long, win_long, rows.as<int32_t>());               \
-        }                                                                                                              \
-        if (n_mid > 0) WALK_GO(PA, PB, 256, false, n_mid, lds_mid, cap_mid, win_mid, rows.as<int32_t>() + n_long);     \
-        if (n_wave > 0) {                                                                                              \
-            so_tiny_kernel<PA, PB, SO_WAVE, WAVE><<<(unsigned)ceil_div((int64_t)n_wave * WAVE, 256), 256>>>(           \
-                (const PA *)a->d_rowptrs, a->d_colinds, a->nrows, (const PB *)b->d_rowptrs, b->d_colinds, c_rp,        \
-                c->d_colinds, c_vs, tp_p, rows.as<int32_t>() + n_long + n_mid, n_wave, oci_p, ovs_p, bad_p);           \
-            CSRK_LAUNCH_CHECK();                                                                                       \
-        }                                                                                                              \
-        if (n_small > 0) {                                                                                             \
-            so_tiny_kernel<PA, PB, SO_TINY, SO_SUB><<<(unsigned)ceil_div((int64_t)n_small * SO_SUB, 256), 256>>>(      \
-                (const PA *)a->d_rowptrs, a->d_colinds, a->nrows, (const PB *)b->d_rowptrs, b->d_colinds, c_rp,        \
-                c->d_colinds, c_vs, tp_p, rows.as<int32_t>() + n_long + n_mid + n_wave, n_small, oci_p, ovs_p, bad_p); \
-            CSRK_LAUNCH_CHECK();                                                                                       \
-        }                                                                                                              \
-    } while (0)
-    if (a->ptr64) {
-        if (b->ptr64) ORDER(int64_t, int64_t);
-        else ORDER(int64_t, int32_t);
-    } else {
-        if (b->ptr64) ORDER(int32_t, int64_t);
-        else ORDER(int32_t, int32_t);
+    x.lds = soplan::so_lds_plan(lds_max, x.c_ncols, b_nnz);
+    CSRK_REQUIRE(x.lds.ok, "device has too little LDS for the ordering pass");
+    return CSRK_OK;
+}
+
+template <class PA, class PB> static int so_count_products(const SoPass &x)
+{
+    if (x.counted) return CSRK_OK;
+    const bool wave = soplan::wave_per_row(x.a_nnz, x.a_nrows);
+    const auto kernel = wave ? so_row_products_kernel<PA, PB, WAVE> : so_row_products_kernel<PA, PB, 16>;
+    kernel<<<soplan::products_grid(x.a_nrows, wave), 256>>>((const PA *)x.a_rp, x.a_ci, x.a_nrows, (const PB *)x.b_rp, x.tp);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// fill false: the rows of every octave counted (and the memory flag raised); true: the rows listed behind the cursors
+static int so_list_rows(const SoPass &x, bool fill)
+{
+    so_list_rows_kernel<<<soplan::list_grid(x.a_nrows), 256>>>(x.tp, x.a_nrows, fill, x.c_rp, x.lds.cap_long, x.cursor,
+                                                               fill ? x.rows : nullptr);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// so_tiny_kernel on `n_list` rows of `list`, or on every row of A (list == nullptr): the rows of [1, CAPT) products
+template <class PA, class PB, int CAPT, int SUB> static int so_order_tiny(const SoPass &x, unsigned grid, const int32_t *list, int32_t n_list)
+{
+    so_tiny_kernel<PA, PB, CAPT, SUB><<<grid, 256>>>((const PA *)x.a_rp, x.a_ci, x.a_nrows, (const PB *)x.b_rp, x.b_ci, x.c_rp, x.c_ci,
+                                                     x.c_vs, x.tp, list, n_list, x.oci, x.ovs, x.bad);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the octave counts come to the host (waits for the kernels so far), the tiers from them; the key array only when a row needs it
+static int so_read_tiers(SoPass &x, DevBuf &key)
+{
+    int32_t counts[SO_OCTAVES + 1];
+    CSRK_HIP(hipMemcpy(counts, x.cursor, sizeof counts, hipMemcpyDeviceToHost));
+    x.tiers = soplan::so_tiers(counts);
+    if (x.tiers.keys_in_memory) {                    // (8 B per entry of C: only for the rows that do not fit LDS)
+        CSRK_TRY(key.alloc(soplan::key_bytes(x.c_nnz)));
+        x.key = key.as<unsigned long long>();
     }
-#undef ORDER
-#undef WALK_GO
-    if (n_long > 0 && key_p) {                       // (the rows the walk left in key[]: the others leave at once)
-        CSRK_HIP(hipFuncSetAttribute((const void *)so_place_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_place));
-        so_place_kernel<<<(unsigned)n_long, SO_PLACE_THREADS, lds_place>>>(c_rp, c->d_colinds, c_vs, tp_p,
-                                                                           rows.as<int32_t>(), cap_long, key_p, oci_p, ovs_p, bad_p);
-        CSRK_LAUNCH_CHECK();
-    }
+    return CSRK_OK;
+}
+
+static int so_list_tiers(const SoPass &x)
+{
+    if (x.tiers.listed == 0) return CSRK_OK;
+    CSRK_HIP(hipMemcpyAsync(x.cursor, x.tiers.cursor, sizeof x.tiers.cursor, hipMemcpyHostToDevice, nullptr));
+    return so_list_rows(x, true);
+}
+
+// a workgroup of THREADS per row of list[0 .. n): by column (COLS) or by entry, `cap` entries of a row and a window of `win` words in LDS
+template <class PA, class PB, int THREADS, bool COLS>
+static int so_walk(const SoPass &x, int32_t n, size_t lds, int32_t cap, int32_t win, const int32_t *list)
+{
+    if (n == 0) return CSRK_OK;
+    const auto kernel = so_walk_kernel<PA, PB, THREADS, COLS>;
+    CSRK_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kernel<<<(unsigned)n, THREADS, lds>>>((const PA *)x.a_rp, x.a_ci, (const PB *)x.b_rp, x.b_ci, x.c_rp, x.c_ci, x.c_vs, x.tp, x.c_ncols,
+                                          cap, win, list, x.key, x.oci, x.ovs, x.bad);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the rows the 1024-thread walk left in key[] (the others leave at once)
+static int so_place_rows_in_memory(const SoPass &x)
+{
+    if (x.tiers.n_long == 0 || !x.key) return CSRK_OK;
+    CSRK_HIP(hipFuncSetAttribute((const void *)so_place_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x.lds.lds_place));
+    so_place_kernel<<<(unsigned)x.tiers.n_long, SO_PLACE_THREADS, x.lds.lds_place>>>(x.c_rp, x.c_ci, x.c_vs, x.tp, x.rows, x.lds.cap_long,
+                                                                                   x.key, x.oci, x.ovs, x.bad);
+    CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// one pass for row pointers of PA and PB: the rows in five classes by their product count, longest first among the listed
+template <class PA, class PB> static int so_order_rows(SoPass &x, DevBuf &key)
+{
+    using namespace soplan;
+    CSRK_TRY((so_count_products<PA, PB>(x)));
+    CSRK_TRY(so_list_rows(x, false));
+    CSRK_TRY((so_order_tiny<PA, PB, SO_LEAST, SO_SUB>(x, least_grid(x.a_nrows), nullptr, 0)));
+    CSRK_TRY(so_read_tiers(x, key));
+    CSRK_TRY(so_list_tiers(x));
+    const Tiers &t = x.tiers;
+    const LdsPlan &l = x.lds;
+    const int32_t *const mid = x.rows + t.n_long, *const wave = mid + t.n_mid, *const small = wave + t.n_wave;
+    if (l.cols_mode) CSRK_TRY((so_walk<PA, PB, LONG_THREADS, true>(x, t.n_long, l.lds_long, l.cap_long, l.win_long, x.rows)));
+    else CSRK_TRY((so_walk<PA, PB, LONG_THREADS, false>(x, t.n_long, l.lds_long, l.cap_long, l.win_long, x.rows)));
+    CSRK_TRY((so_walk<PA, PB, MID_THREADS, false>(x, t.n_mid, l.lds_mid, l.cap_mid, l.win_mid, mid)));
+    if (t.n_wave > 0) CSRK_TRY((so_order_tiny<PA, PB, SO_WAVE, WAVE>(x, wave_grid(t.n_wave), wave, t.n_wave)));
+    if (t.n_small > 0) CSRK_TRY((so_order_tiny<PA, PB, SO_TINY, SO_SUB>(x, small_grid(t.n_small), small, t.n_small)));
+    return so_place_rows_in_memory(x);
+}
+
+static int so_check_flag(const SoPass &x)
+{
     unsigned int bad = 0;
-    CSRK_HIP(hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost));      // (waits for the kernels)
+    CSRK_HIP(hipMemcpy(&bad, x.bad, 4, hipMemcpyDeviceToHost));      // (waits for the kernels)
     CSRK_REQUIRE(bad == 0, "an entry of the product has no product landing on it (internal error)");
-    // the re-ordered arrays become the product's own (pool blocks both: the old ones go back with the DevBufs)
+    return CSRK_OK;
+}
+
+// the re-ordered arrays become the product's own (pool blocks both: the old ones go back with the DevBufs)
+static int so_adopt(Matrix *c, SoBuffers &buf)
+{
     if (c->owns) {
         void *old_ci = c->d_colinds, *old_vs = c->d_values;
-        c->d_colinds = (int32_t *)oci.take();
-        c->d_values = ovs.take();
+        c->d_colinds = (int32_t *)buf.oci.take();
+        c->d_values = buf.ovs.take();
         pool_free(old_ci);
         pool_free(old_vs);
     } else {
-        CSRK_HIP(hipMemcpy(c->d_colinds, oci.p, (size_t)n * 4, hipMemcpyDeviceToDevice));
-        CSRK_HIP(hipMemcpy(c->d_values, ovs.p, (size_t)n * 8, hipMemcpyDeviceToDevice));
+        CSRK_HIP(hipMemcpy(c->d_colinds, buf.oci.p, soplan::oci_bytes(c->nnz), hipMemcpyDeviceToDevice));
+        CSRK_HIP(hipMemcpy(c->d_values, buf.ovs.p, soplan::ovs_bytes(c->nnz), hipMemcpyDeviceToDevice));
     }
     return CSRK_OK;
+}
+
+// c = a b as the product kernels left it (ascending columns, int32 row pointers, float64 values): re-ordered in place
+int spgemm_apply_reference_order(Matrix *a, Matrix *b, Matrix *c, const DevBuf *products)
+{
+    if (soplan::nothing_to_order(c->nnz, c->nrows, a->nnz)) return CSRK_OK;
+    CSRK_REQUIRE(!c->ptr64 && c->val_type == CSRK_VAL_F64, "product has an unexpected layout");
+    SoBuffers buf;
+    SoPass x;
+    CSRK_TRY(so_take_buffers(a, b, c, products, buf, x));
+    CSRK_TRY(so_read_lds_plan(b->nnz, x));
+    if (a->ptr64) {
+        if (b->ptr64) CSRK_TRY((so_order_rows<int64_t, int64_t>(x, buf.key)));
+        else CSRK_TRY((so_order_rows<int64_t, int32_t>(x, buf.key)));
+    } else {
+        if (b->ptr64) CSRK_TRY((so_order_rows<int32_t, int64_t>(x, buf.key)));
+        else CSRK_TRY((so_order_rows<int32_t, int32_t>(x, buf.key)));
+    }
+    CSRK_TRY(so_check_flag(x));
+    return so_adopt(c, buf);
 }
 
 // the ordering pass's row tiers and the placing window, for csrk_spgemm_limits (spgemm.hip)

@@ -21,6 +21,7 @@
 #include "device_loads.h"
 #include "panel.h"
 #include "sort.h"
+#include "spgemm_order.h"
 #include "spmm_plan.h"
 
 #include <cstdio>
@@ -888,8 +889,6 @@ __global__ void dense_widen_kernel(const float *__restrict__ in, double *__restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (double)in[i];
 }
-
-bool spgemm_reference_order_wanted();      // spgemm_order.hip
 
 // the route's temporaries in the order they are requested from the pool (they go back in reverse, in default-stream order:
 // every launch of the route is on it)

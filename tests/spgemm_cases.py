@@ -3,7 +3,8 @@ Inputs that put the general sparse product (csrc/spgemm.hip, csrc/spgemm_order.h
 both sides of every threshold between them, the NumPy restatement of the routing (`census`) and of the product itself
 (`ref_product`).  No GPU imports: tests/test_spgemm_cases_host.py checks every case's preconditions, the constants against
 csrk_spgemm_limits and the restated product against the oracle; tests/test_gpu_spgemm_routes.py runs the library on the
-same cases and compares csrk_spgemm_last_stats with the census field by field.
+same cases and compares csrk_spgemm_last_stats with the census field by field.  `order_plan` restates what the ordering pass
+does with a product's rows (csrc/spgemm_order_plan.h); tests/test_spgemm_order_plan_host.py holds the header against it.
 
 The routing, restated.  A row of the product is sent by its product count u = sum over the entries (i, j) of A of |B_j| and
 its entry count J (sg_list_rows; the driver's sg_plan decides what is in force):
@@ -783,6 +784,47 @@ def _(name):
 
 
 # ---- the ordering pass -------------------------------------------------------------------------------------------------
+
+# csrc/spgemm_order_plan.h, restated (tests/test_spgemm_order_plan_host.py holds the two against each other on every case)
+ORDER_LDS_MAX = 163840      # LDS a workgroup may have on the MI355X (hipDeviceAttributeMaxSharedMemoryPerBlock)
+SO_LDS_BYTES = 150 * 1024   # dynamic LDS of the 1024-thread walk at most,
+SO_TABLES_BYTES = 18 * 1024  # beside its static batch tables
+SO_WIN_ENTRY = 2048         # bitmap words of its placing window by entry,
+SO_WIN_COLS = (16384, 8192, 4096, 2048, 1024)      # and by column: the first that fits
+
+
+def order_plan(c, lds_max=ORDER_LDS_MAX, lim=LIMITS):
+    """
+    What spgemm_apply_reference_order does with the rows of case c's product on a device of lds_max bytes of LDS per
+    workgroup.  The 1024-thread walk works by column when 4 B per column of C, two bits and a window fit and B has fewer
+    than 2^32 - 1 entries, else by entry with 8 B per entry of the row; a row is `listed` from SO_LEAST products on and then
+    long (1024 threads), mid (256), wave or small by SO_MID, SO_WAVE, SO_TINY; its keys go through memory when it has 2^32 - 1
+    products or, by entry, more entries than LDS holds.  `long_forms`: the forms the long rows take, of 'by column',
+    'by entry in LDS', 'in memory'; `place`: so_place_kernel runs.
+    """
+    u, cnt = c.p.u, c.p.cnt
+    budget = min(SO_LDS_BYTES, lds_max - SO_TABLES_BYTES)
+    by_col = 4 * (c.r.ncols + 2 * ceil_div(c.r.ncols, 32))
+    win_cols = next((w for w in SO_WIN_COLS if by_col + 8 * w <= budget), 0)
+    cols = win_cols > 0 and c.r.nnz < 2 ** 32 - 1
+    win_long = win_cols if cols else SO_WIN_ENTRY
+    cap_long = 2 ** 31 - 1 if cols else max(0, budget - 8 * win_long) // 8
+    listed = u >= lim['SO_LEAST']
+    long = u >= lim['SO_MID']
+    memory = listed & ((u >= 2 ** 32 - 1) | (cnt > cap_long))
+    forms = {'in memory' if memory[i] else 'by column' if cols else 'by entry in LDS' for i in np.flatnonzero(long)}
+    octave = np.array([63 - (int(v).bit_length() - 1) for v in u[listed]], dtype=np.int64)      # leading zeros of an int64
+    counts = np.bincount(octave, minlength=64)
+    return dict(budget=budget, by_col=by_col, win_cols=win_cols, cols_mode=int(cols), win_long=win_long, cap_long=cap_long,
+                lds_long=by_col + 8 * win_long if cols else 8 * cap_long + 8 * win_long, win_mid=lim['SO_MID'] // 32, cap_mid=lim['SO_MID'],
+                lds_mid=8 * lim['SO_MID'] + 8 * (lim['SO_MID'] // 32), lds_place=lim['SO_WIN'] // 32 * 8,
+                ok=int(lim['SO_WIN'] // 32 * 8 + 2048 <= lds_max and cap_long >= lim['SO_MID']),
+                listed=int(listed.sum()), n_long=int(long.sum()), n_mid=int(np.sum((u >= lim['SO_WAVE']) & ~long)),
+                n_wave=int(np.sum((u >= lim['SO_TINY']) & (u < lim['SO_WAVE']))), n_small=int(np.sum(listed & (u < lim['SO_TINY']))),
+                n_least=int(np.sum((u > 0) & ~listed)), keys_in_memory=int(memory.any()),
+                cursors=[int(v) for v in np.concatenate([[0], np.cumsum(counts)[:-1]])], long_forms=forms,
+                place=bool(long.any() and memory.any()))
+
 
 ORDER_TIERS = (63, 64, 255, 256, 1023, 1024, 4095, 4096)
 

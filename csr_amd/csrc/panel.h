@@ -1,7 +1,11 @@
 // Host-side steps shared by the operations that take dense row-major panels (csrk_spmm_dense, csrk_sddmm, csrk_gram_rows,
-// csrk_als_rows, csrk_solve_blocks, csrk_topk_scores, csrk_rank_entries; DESIGN.md section 8, "Taking dense panels"):
+// csrk_als_rows, csrk_solve_blocks, csrk_topk_scores, csrk_rank_entries and the two list forms csrk_topk_scores_for,
+// csrk_rank_entries_for; DESIGN.md section 8, "Taking dense panels"):
 //   checks -> early return -> NULL checks -> pack_panel -> the _device function with packed strides -> unpack_panel
-// The entry points call these in a straight line, and every entry keeps its own ORDER of refusals.
+// The entry points call these in a straight line, and every entry keeps its own ORDER of refusals.  Here: the element size,
+// the 16-B predicate, pack_panel / unpack_panel, panel_rows_from, mark_user_stream, check_transpose_shape and the scalar
+// refusals.  What only the four factor-score drivers share -- the optional handle, the canonical check of `seen`, the listed
+// rows (check_listed_rows, pack_listed_rows), the seen / test agreement and the panel-type ladder -- is score_host.h's.
 #pragma once
 #include "common.h"
 

@@ -25,8 +25,8 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "panel.h"
 #include "rank_list.h"
+#include "score_host.h"
 #include "score_tile.h"
 
 namespace csrk {
@@ -235,6 +235,28 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_kernel(const void *__
     if (!count && sink == 0x7ff8c0dec0dec0deull && tid < nvalid && s_t1[tid] > s_t0[tid]) ranks[s_t0[tid] - base] = 0;      // (keeps the product alive)
 }
 
+// the kernel's arguments in its order (the grid follows from n)
+struct ReLaunch {
+    ScoreCsr seen, test;
+    int32_t row_begin, n;
+    const void *U;
+    int64_t ldu;
+    const void *V;
+    int64_t ldv;
+    int32_t n_items, k;
+    int count;
+    int32_t *ranks;
+    double *scores;
+    hipStream_t s;
+};
+
+template <class T, bool WIDE> static void re_launch(const ReLaunch &a)
+{
+    rank_entries_kernel<T, WIDE><<<(unsigned)score_row_blocks(a.n), TS_THREADS, 0, a.s>>>(
+        a.seen.rp, a.seen.ptr64, a.seen.ci, a.test.rp, a.test.ptr64, a.test.ci, a.row_begin, a.n, (const T *)a.U, a.ldu, (const T *)a.V,
+        a.ldv, a.n_items, a.k, a.count, a.ranks, a.scores);
+}
+
 // the refusals that need no handle come first: they are answered whatever the handles are
 static int re_scalars(int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t k, int panel_type)
 {
@@ -242,36 +264,32 @@ static int re_scalars(int32_t row_begin, int32_t row_end, int64_t ldu, int64_t l
     CSRK_CHECK_TWO_PANELS("rank_entries: ", k, ldu, ldv);
     CSRK_CHECK_PANEL_TYPE("rank_entries: ", panel_type);
     CSRK_CHECK_ROW_ORDER("rank_entries: ", row_begin, row_end);
-    if (k > RE_K_MAX) {
-        set_error("csrk_rank_entries: k=%d is above the largest supported k=%d (csrk_rank_entries_limits)", k, RE_K_MAX);
-        return CSRK_ERR_UNSUPPORTED;
+    return check_supported(re_k_supported(k), "csrk_rank_entries", "k", k, RE_K_MAX, "csrk_rank_entries_limits");
+}
+
+// the scalars, then the handles (seen may be 0) and what they must agree on; the caller holds no lock
+static int re_check(csrk_handle_t seen_h, csrk_handle_t test_h, int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t k,
+                    int panel_type, Matrix **ms, Matrix **mt)
+{
+    CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
+    CSRK_TRY(optional_handle(seen_h, ms));
+    Matrix *const seen = *ms, *const test = from_handle(test_h);
+    if (!test) return CSRK_ERR_INVALID;
+    *mt = test;
+    CSRK_CHECK_ROW_RANGE("rank_entries: ", row_begin, row_end, test->nrows);
+    if (seen) {
+        CSRK_TRY(check_seen_matches_test("rank_entries", seen, test));
+        CSRK_TRY(check_seen_canonical("rank_entries", seen));
     }
     return CSRK_OK;
 }
 
-// then the handles (seen may be 0) and what they must agree on; the caller holds no lock
-static int re_check(csrk_handle_t seen_h, csrk_handle_t test_h, int32_t row_begin, int32_t row_end, Matrix **ms, Matrix **mt)
+static int re_pointers(const void *ranks, const void *scores, const void *U, const void *V, size_t es)
 {
-    Matrix *seen = nullptr, *test = nullptr;
-    if (seen_h) {
-        seen = from_handle(seen_h);
-        if (!seen) return CSRK_ERR_INVALID;
-    }
-    test = from_handle(test_h);
-    if (!test) return CSRK_ERR_INVALID;
-    CSRK_CHECK_ROW_RANGE("rank_entries: ", row_begin, row_end, test->nrows);
-    if (seen) {
-        CSRK_REQUIRE(seen->nrows == test->nrows && seen->ncols == test->ncols, "rank_entries: seen is %d x %d but test is %d x %d",
-                     seen->nrows, seen->ncols, test->nrows, test->ncols);
-        CSRK_REQUIRE(seen->device == test->device, "rank_entries: seen and test are on different devices");
-        std::lock_guard<std::mutex> lk(seen->mu);
-        CSRK_TRY(look_at_rows(seen));                             // (remembered: a device pass only the first time a handle is asked)
-        CSRK_REQUIRE(seen->canonical == 1,
-                     "rank_entries: seen is not canonical: row %d is not strictly ascending in column (csrk_order_columns sorts, "
-                     "csrk_coalesce merges repeats)",
-                     seen->noncanonical_row);
-    }
-    *ms = seen, *mt = test;
+    CSRK_REQUIRE(ranks, "rank_entries: ranks is NULL");
+    CSRK_REQUIRE(U && V, "rank_entries: U or V is NULL");
+    CSRK_REQUIRE(((uintptr_t)U % es) == 0 && ((uintptr_t)V % es) == 0 && ((uintptr_t)scores % 8) == 0 && ((uintptr_t)ranks % 4) == 0,
+                 "rank_entries: U, V, ranks or scores is not aligned to its element size");
     return CSRK_OK;
 }
 
@@ -279,32 +297,32 @@ static int re_check(csrk_handle_t seen_h, csrk_handle_t test_h, int32_t row_begi
 static int re_device(Matrix *seen, Matrix *test, int32_t row_begin, int32_t row_end, const void *dU, int64_t ldu, const void *dV,
                      int64_t ldv, int32_t k, int panel_type, int32_t *dranks, double *dscores, hipStream_t s)
 {
-    CSRK_REQUIRE(dranks, "rank_entries: ranks is NULL");
-    CSRK_REQUIRE(dU && dV, "rank_entries: U or V is NULL");
     const size_t es = panel_es(panel_type);
-    CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 && ((uintptr_t)dranks % 4) == 0,
-                 "rank_entries: U, V, ranks or scores is not aligned to its element size");
+    CSRK_TRY(re_pointers(dranks, dscores, dU, dV, es));
     mark_user_stream(seen, s);
     mark_user_stream(test, s);
-    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
-    const char *env = getenv("CSRK_RANK_ENTRIES_COUNT");          // diagnostic: "0" times the product alone (the outputs are not written)
-    const int count = !(env && env[0] == '0' && !env[1]);
-    const int32_t n = row_end - row_begin;
-    const unsigned grid = (unsigned)ceil_div((int64_t)n, TS_ROWS);
-#define RE_GO(T, W)                                                                                                               \
-    rank_entries_kernel<T, W><<<grid, TS_THREADS, 0, s>>>(seen ? seen->d_rowptrs : nullptr, seen ? seen->ptr64 : 0,               \
-                                                           seen ? seen->d_colinds : nullptr, test->d_rowptrs, test->ptr64,         \
-                                                           test->d_colinds, row_begin, n, (const T *)dU, ldu, (const T *)dV, ldv,  \
-                                                           test->ncols, k, count, dranks, dscores)
-    if (panel_type == CSRK_VAL_F64) {
-        if (wide) RE_GO(double, true);
-        else RE_GO(double, false);
-    } else {
-        if (wide) RE_GO(float, true);
-        else RE_GO(float, false);
-    }
-#undef RE_GO
+    const int count = score_knob_on(getenv("CSRK_RANK_ENTRIES_COUNT"));       // diagnostic: "0" times the product alone (the outputs are not written)
+    const ReLaunch L{score_csr(seen), score_csr(test), row_begin, row_end - row_begin, dU, ldu, dV, ldv, test->ncols, k, count, dranks,
+                     dscores, s};
+    score_for_panel(panel_type, panels_wide(dU, ldu, dV, ldv, k, es),
+                    [&](auto t, auto w) { re_launch<typename decltype(t)::type, decltype(w)::value>(L); });
     CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the entries of the rows [row_begin, row_end) of `test`: two row pointers fetched (the host form is synchronous anyway)
+static int re_fetch_entry_range(const Matrix *test, int32_t row_begin, int32_t row_end, int64_t e[2])
+{
+    for (int i = 0; i < 2; i++) {
+        const int64_t row = i ? row_end : row_begin;
+        if (test->ptr64) {
+            CSRK_HIP(hipMemcpy(&e[i], (const int64_t *)test->d_rowptrs + row, 8, hipMemcpyDeviceToHost));
+        } else {
+            int32_t v = 0;
+            CSRK_HIP(hipMemcpy(&v, (const int32_t *)test->d_rowptrs + row, 4, hipMemcpyDeviceToHost));
+            e[i] = v;
+        }
+    }
     return CSRK_OK;
 }
 
@@ -326,8 +344,7 @@ int csrk_rank_entries_device(csrk_handle_t seen, csrk_handle_t test, int32_t row
                              const void *d_V, int64_t ldv, int32_t k, int panel_type, int32_t *d_ranks, double *d_scores, void *stream)
 {
     Matrix *ms, *mt;
-    CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
-    CSRK_TRY(re_check(seen, test, row_begin, row_end, &ms, &mt));
+    CSRK_TRY(re_check(seen, test, row_begin, row_end, ldu, ldv, k, panel_type, &ms, &mt));
     if (row_begin == row_end || mt->nnz == 0) return CSRK_OK;
     const void *u0 = panel_rows_from(d_U, row_begin, ldu, panel_es(panel_type));
     return re_device(ms, mt, row_begin, row_end, u0, ldu, d_V, ldv, k, panel_type, d_ranks, d_scores, (hipStream_t)stream);
@@ -338,27 +355,13 @@ int csrk_rank_entries(csrk_handle_t seen, csrk_handle_t test, int32_t row_begin,
 {
     Matrix *ms, *mt;
     // argument checks first, with the caller's pointers (the device call below sees packed copies)
-    CSRK_TRY(re_scalars(row_begin, row_end, ldu, ldv, k, panel_type));
-    CSRK_TRY(re_check(seen, test, row_begin, row_end, &ms, &mt));
+    CSRK_TRY(re_check(seen, test, row_begin, row_end, ldu, ldv, k, panel_type, &ms, &mt));
     if (row_begin == row_end || mt->nnz == 0) return CSRK_OK;
-    // the entries of the range: two row pointers (the host form is synchronous anyway)
     int64_t e[2];
-    for (int i = 0; i < 2; i++) {
-        const int64_t row = i ? row_end : row_begin;
-        if (mt->ptr64) {
-            CSRK_HIP(hipMemcpy(&e[i], (const int64_t *)mt->d_rowptrs + row, 8, hipMemcpyDeviceToHost));
-        } else {
-            int32_t v = 0;
-            CSRK_HIP(hipMemcpy(&v, (const int32_t *)mt->d_rowptrs + row, 4, hipMemcpyDeviceToHost));
-            e[i] = v;
-        }
-    }
+    CSRK_TRY(re_fetch_entry_range(mt, row_begin, row_end, e));
     if (e[1] <= e[0]) return CSRK_OK;
-    CSRK_REQUIRE(ranks, "rank_entries: ranks is NULL");
-    CSRK_REQUIRE(U && V, "rank_entries: U or V is NULL");
     const size_t es = panel_es(panel_type);
-    CSRK_REQUIRE(((uintptr_t)U % es) == 0 && ((uintptr_t)V % es) == 0 && ((uintptr_t)scores % 8) == 0 && ((uintptr_t)ranks % 4) == 0,
-                 "rank_entries: U, V, ranks or scores is not aligned to its element size");
+    CSRK_TRY(re_pointers(ranks, scores, U, V, es));
     const size_t n = (size_t)(row_end - row_begin), ne = (size_t)(e[1] - e[0]), n_items = (size_t)mt->ncols;
     DevBuf dU, dV, dR, dS;
     CSRK_TRY(pack_panel(dU, panel_rows_from(U, row_begin, ldu, es), ldu, k, es, n));

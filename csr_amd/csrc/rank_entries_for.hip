@@ -16,22 +16,17 @@
 //
 // LDS: 33 KiB of staging lines + 43.5 KiB of lists and counters + 1 KiB of list rows and offsets = 77.5 KiB per workgroup,
 // two workgroups per CU (160 KiB).
-#include <cstring>
 #include <vector>
 
 #include "common.h"
-#include "panel.h"
 #include "rank_list.h"
+#include "score_host.h"
 #include "score_list.h"
 #include "score_tile.h"
 
 namespace csrk {
 
-constexpr int REF_S_MAX = 64;                   // most splits
-constexpr int REF_W = 512;                      // workgroups that fill the card: two per CU (256 CUs)
-constexpr int REF_LEN_THREADS = 256;
-constexpr int64_t REF_GRID_MAX = 0x7fffffffll;
-
+// (the constants REF_*, the split rule and the item interval of a split: score_plan.h)
 template <class T, bool WIDE>
 __global__ __launch_bounds__(TS_THREADS) void rank_entries_for_kernel(const void *__restrict__ seen_rp, int seen_ptr64,
                                                                      const int32_t *__restrict__ seen_ci, const void *__restrict__ test_rp,
@@ -58,9 +53,8 @@ __global__ __launch_bounds__(TS_THREADS) void rank_entries_for_kernel(const void
     const int tid = threadIdx.x, ty = tid / (TS_TILE / TS_B), tx = tid % (TS_TILE / TS_B);
     const int lane = tid & (WAVE - 1), w = tid / WAVE;
     const int split = blockIdx.y;
-    const int64_t tiles = ((int64_t)n_items + TS_TILE - 1) / TS_TILE;
-    const int64_t j_begin = split * tiles / n_splits * TS_TILE, j_to = (split + 1) * tiles / n_splits * TS_TILE;
-    const int64_t j_end = j_to < n_items ? j_to : (int64_t)n_items;
+    const ScoreItemRange range = score_item_range(split, n_splits, n_items);
+    const int64_t j_begin = range.j_begin, j_end = range.j_end;
     const int64_t r0 = (int64_t)blockIdx.x * TS_ROWS;             // the block's first row, as a place in the list
     const int64_t nvalid = n_rows - r0 < TS_ROWS ? n_rows - r0 : TS_ROWS;
 
@@ -257,17 +251,33 @@ __global__ __launch_bounds__(REF_LEN_THREADS) void rank_entries_for_lens_kernel(
     }
 }
 
-// rule 11: the splits in use, from the constants alone
-static int32_t ref_plan(int64_t n_rows, int32_t n_items, int32_t splits)
+// the kernel's arguments in its order (the grid: row blocks x S)
+struct RefLaunch {
+    ScoreCsr seen, test;
+    const int32_t *rows;
+    int64_t n_rows;
+    int32_t u_rows;
+    int u_packed;
+    const void *U;
+    int64_t ldu;
+    const void *V;
+    int64_t ldv;
+    int32_t n_items, k;
+    const int64_t *offsets;
+    int64_t n_out;
+    int32_t *ranks;
+    double *scores;
+    int S;
+    hipStream_t s;
+};
+
+template <class T, bool WIDE> static void ref_launch(const RefLaunch &a)
 {
-    const int64_t tiles = ceil_div((int64_t)n_items, TS_TILE), blocks = ceil_div(n_rows, TS_ROWS);
-    const int64_t most = tiles < REF_S_MAX ? tiles : REF_S_MAX;
-    int64_t s = 1;
-    if (tiles > 0 && blocks > 0) {
-        s = splits >= 1 ? splits : ceil_div(REF_W, blocks);
-        s = s > most ? most : s;
-    }
-    return (int32_t)s;
+    const dim3 grid((unsigned)score_row_blocks(a.n_rows), (unsigned)a.S);
+    rank_entries_for_kernel<T, WIDE><<<grid, TS_THREADS, 0, a.s>>>(a.seen.rp, a.seen.ptr64, a.seen.ci, a.test.rp, a.test.ptr64, a.test.ci,
+                                                                   a.rows, a.n_rows, a.u_rows, a.u_packed, (const T *)a.U, a.ldu,
+                                                                   (const T *)a.V, a.ldv, a.n_items, a.k, a.offsets, a.n_out, a.ranks,
+                                                                   a.scores, a.S);
 }
 
 // the refusals that need no handle come first: they are answered whatever the handles are
@@ -280,42 +290,27 @@ static int ref_scalars(int64_t n_rows, int32_t u_rows, int64_t ldu, int64_t ldv,
     CSRK_REQUIRE(u_rows >= 0, "rank_entries_for: u_rows must not be negative (u_rows=%d)", u_rows);
     CSRK_REQUIRE(splits >= 0, "rank_entries_for: splits must not be negative (splits=%d)", splits);
     CSRK_REQUIRE(n_out >= 0, "rank_entries_for: n_out must not be negative (n_out=%lld)", (long long)n_out);
-    if (k > RE_K_MAX) {
-        set_error("rank_entries_for: k=%d is above the largest supported k=%d (csrk_rank_entries_limits)", k, RE_K_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
-    return CSRK_OK;
+    return check_supported(re_k_supported(k), "rank_entries_for", "k", k, RE_K_MAX, "csrk_rank_entries_limits");
 }
 
 // then the handles (seen may be 0) and what they must agree on; the caller holds no lock
 static int ref_check(csrk_handle_t seen_h, csrk_handle_t test_h, int64_t n_rows, int32_t u_rows, int32_t splits, Matrix **ms, Matrix **mt)
 {
-    Matrix *seen = nullptr, *test = nullptr;
-    if (seen_h) {
-        seen = from_handle(seen_h);
-        if (!seen) return CSRK_ERR_INVALID;
-    }
-    test = from_handle(test_h);
+    CSRK_TRY(optional_handle(seen_h, ms));
+    Matrix *const seen = *ms, *const test = from_handle(test_h);
     if (!test) return CSRK_ERR_INVALID;
+    *mt = test;
     CSRK_REQUIRE(u_rows == test->nrows, "rank_entries_for: u_rows=%d but test has %d rows", u_rows, test->nrows);
     if (seen) {
-        CSRK_REQUIRE(seen->nrows == test->nrows && seen->ncols == test->ncols, "rank_entries_for: seen is %d x %d but test is %d x %d",
-                     seen->nrows, seen->ncols, test->nrows, test->ncols);
-        CSRK_REQUIRE(seen->device == test->device, "rank_entries_for: seen and test are on different devices");
-        std::lock_guard<std::mutex> lk(seen->mu);
-        CSRK_TRY(look_at_rows(seen));                             // (remembered: a device pass only the first time a handle is asked)
-        CSRK_REQUIRE(seen->canonical == 1,
-                     "rank_entries_for: seen is not canonical: row %d is not strictly ascending in column (csrk_order_columns sorts, "
-                     "csrk_coalesce merges repeats)",
-                     seen->noncanonical_row);
+        CSRK_TRY(check_seen_matches_test("rank_entries_for", seen, test));
+        CSRK_TRY(check_seen_canonical("rank_entries_for", seen));
     }
-    const int64_t blocks = ceil_div(n_rows, TS_ROWS), S = ref_plan(n_rows, test->ncols, splits);
-    if (blocks > REF_GRID_MAX / S) {
+    const int64_t S = ref_splits(n_rows, test->ncols, splits);
+    if (ref_grid_too_large(n_rows, S)) {
         set_error("rank_entries_for: n_rows=%lld in %lld splits makes more workgroups than a grid holds (%lld)", (long long)n_rows,
                   (long long)S, (long long)REF_GRID_MAX);
         return CSRK_ERR_UNSUPPORTED;
     }
-    *ms = seen, *mt = test;
     return CSRK_OK;
 }
 
@@ -333,24 +328,32 @@ static int ref_device(Matrix *seen, Matrix *test, const int32_t *drows, int64_t 
                  "rank_entries_for: rows, offsets, U, V, ranks or scores is not aligned to its element size");
     mark_user_stream(seen, s);
     mark_user_stream(test, s);
-    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
-    const int32_t S = ref_plan(n_rows, test->ncols, splits);
+    const int32_t S = ref_splits(n_rows, test->ncols, splits);
     if (S > 1) CSRK_HIP(hipMemsetAsync(dranks, 0, (size_t)n_out * 4, s));      // the partial ranks add onto zero
-    const dim3 grid((unsigned)ceil_div(n_rows, TS_ROWS), (unsigned)S);
-#define REF_GO(T, W)                                                                                                              \
-    rank_entries_for_kernel<T, W><<<grid, TS_THREADS, 0, s>>>(seen ? seen->d_rowptrs : nullptr, seen ? seen->ptr64 : 0,           \
-                                                               seen ? seen->d_colinds : nullptr, test->d_rowptrs, test->ptr64,     \
-                                                               test->d_colinds, drows, n_rows, u_rows, u_packed, (const T *)dU, ldu, \
-                                                               (const T *)dV, ldv, test->ncols, k, doffsets, n_out, dranks, dscores, S)
-    if (panel_type == CSRK_VAL_F64) {
-        if (wide) REF_GO(double, true);
-        else REF_GO(double, false);
-    } else {
-        if (wide) REF_GO(float, true);
-        else REF_GO(float, false);
-    }
-#undef REF_GO
+    const RefLaunch L{score_csr(seen), score_csr(test), drows, n_rows, u_rows, u_packed, dU, ldu, dV, ldv, test->ncols, k, doffsets, n_out,
+                      dranks, dscores, S, s};
+    score_for_panel(panel_type, panels_wide(dU, ldu, dV, ldv, k, es),
+                    [&](auto t, auto w) { ref_launch<typename decltype(t)::type, decltype(w)::value>(L); });
     CSRK_LAUNCH_CHECK();
+    return CSRK_OK;
+}
+
+// the host form's offsets: the test entries of every listed row, counted on the device and summed here (the host form is
+// synchronous anyway); off[n_rows] is their total
+static int ref_host_offsets(const Matrix *test, const int32_t *drows, int64_t n_rows, int64_t *dlens, std::vector<int64_t> &off)
+{
+    rank_entries_for_lens_kernel<<<(unsigned)ref_lens_grid(n_rows), REF_LEN_THREADS>>>(test->d_rowptrs, test->ptr64, drows, n_rows, dlens);
+    CSRK_LAUNCH_CHECK();
+    const size_t n = (size_t)n_rows;
+    off.resize(n + 1);
+    CSRK_HIP(hipMemcpy(off.data(), dlens, n * 8, hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (size_t r = 0; r < n; r++) {
+        const int64_t len = off[r];
+        off[r] = total;
+        total += len;
+    }
+    off[n] = total;
     return CSRK_OK;
 }
 
@@ -374,7 +377,7 @@ int csrk_rank_entries_for_splits(int64_t n_rows, int32_t n_items, int32_t splits
     CSRK_REQUIRE(n_rows >= 0, "rank_entries_for: n_rows must not be negative (n_rows=%lld)", (long long)n_rows);
     CSRK_REQUIRE(n_items >= 0, "rank_entries_for: n_items must not be negative (n_items=%d)", n_items);
     CSRK_REQUIRE(splits >= 0, "rank_entries_for: splits must not be negative (splits=%d)", splits);
-    *splits_used = ref_plan(n_rows, n_items, splits);
+    *splits_used = ref_splits(n_rows, n_items, splits);
     return CSRK_OK;
 }
 
@@ -404,42 +407,23 @@ int csrk_rank_entries_for(csrk_handle_t seen, csrk_handle_t test, const int32_t 
     }
     CSRK_REQUIRE(rows, "rank_entries_for: rows is NULL");
     CSRK_REQUIRE(((uintptr_t)rows % 4) == 0, "rank_entries_for: rows is not aligned to its element size");
-    for (int64_t r = 0; r < n_rows; r++)                          // the list is looked at before anything is sent
-        CSRK_REQUIRE(rows[r] >= 0 && rows[r] < u_rows, "rank_entries_for: rows[%lld]=%d is outside [0, %d)", (long long)r, rows[r], u_rows);
-    // the offsets: the test entries of every listed row, summed here (the host form is synchronous anyway)
-    const size_t n = (size_t)n_rows;
-    DevBuf dR, dO;
+    CSRK_TRY(check_listed_rows("rank_entries_for", rows, n_rows, u_rows));
+    const size_t n = (size_t)n_rows, ne = (size_t)n_out, es = panel_es(panel_type);
+    DevBuf dR, dO, dU, dV, dK, dS;
+    std::vector<int64_t> off;
     CSRK_TRY(dR.alloc(n * 4));
     CSRK_TRY(dO.alloc((n + 1) * 8));
     CSRK_HIP(hipMemcpy(dR.p, rows, n * 4, hipMemcpyHostToDevice));
-    const int64_t lblocks = ceil_div(n_rows, REF_LEN_THREADS);
-    rank_entries_for_lens_kernel<<<(unsigned)(lblocks < (1 << 20) ? lblocks : (1 << 20)), REF_LEN_THREADS>>>(mt->d_rowptrs, mt->ptr64,
-                                                                                                            dR.as<int32_t>(), n_rows,
-                                                                                                            dO.as<int64_t>());
-    CSRK_LAUNCH_CHECK();
-    std::vector<int64_t> off(n + 1);
-    CSRK_HIP(hipMemcpy(off.data(), dO.p, n * 8, hipMemcpyDeviceToHost));
-    int64_t total = 0;
-    for (size_t r = 0; r < n; r++) {
-        const int64_t len = off[r];
-        off[r] = total;
-        total += len;
-    }
-    off[n] = total;
-    CSRK_REQUIRE(n_out == total, "rank_entries_for: n_out=%lld but the listed rows hold %lld test entries", (long long)n_out,
-                 (long long)total);
+    CSRK_TRY(ref_host_offsets(mt, dR.as<int32_t>(), n_rows, dO.as<int64_t>(), off));
+    CSRK_REQUIRE(n_out == off[n], "rank_entries_for: n_out=%lld but the listed rows hold %lld test entries", (long long)n_out,
+                 (long long)off[n]);
     if (n_out == 0) return CSRK_OK;
     CSRK_REQUIRE(ranks, "rank_entries_for: ranks is NULL");
     CSRK_REQUIRE(U && V, "rank_entries_for: U or V is NULL");
-    const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)U % es) == 0 && ((uintptr_t)V % es) == 0 && ((uintptr_t)scores % 8) == 0 && ((uintptr_t)ranks % 4) == 0,
                  "rank_entries_for: rows, offsets, U, V, ranks or scores is not aligned to its element size");
     CSRK_HIP(hipMemcpy(dO.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    const size_t ne = (size_t)n_out, line = (size_t)k * es;
-    std::vector<char> picked(n * line);                           // the listed rows of U only, in list order
-    for (size_t r = 0; r < n; r++) memcpy(picked.data() + r * line, (const char *)U + (size_t)rows[r] * (size_t)ldu * es, line);
-    DevBuf dU, dV, dK, dS;
-    CSRK_TRY(pack_panel(dU, picked.data(), k, k, es, n));
+    CSRK_TRY(pack_listed_rows(dU, U, ldu, k, es, rows, n));
     CSRK_TRY(pack_panel(dV, V, ldv, k, es, (size_t)mt->ncols));
     CSRK_TRY(dK.alloc(ne * 4));
     if (scores) CSRK_TRY(dS.alloc(ne * 8));

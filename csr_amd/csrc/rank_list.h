@@ -7,9 +7,8 @@
 
 namespace csrk {
 
-constexpr int RE_T = 32;                        // test entries of a row per sweep
+// (RE_T, RE_K_MAX and the REF_* constants: score_plan.h)
 constexpr int RE_LDT = RE_T + 1;                // list line (rows fall into different banks)
-constexpr int RE_K_MAX = 1024;
 constexpr int32_t RE_BAD_ITEM = 0x7fffffff;     // listed for a test column outside [0, n_items): never dereferenced
 static_assert(RE_T <= WAVE, "one lane per listed entry");
 

@@ -16,9 +16,7 @@
 namespace csrk {
 
 constexpr int TS_PASS = TS_TILE / TS_B;         // most survivors a row takes in one pass
-constexpr int TS_K_MAX = 1024;
-constexpr int TS_NTOP_SMALL = 32;
-constexpr int TS_NTOP_MAX = 128;
+// (TS_K_MAX, TS_NTOP_SMALL, TS_NTOP_MAX and the TSF_* constants: score_plan.h)
 
 template <int CLS> struct TsClass;
 template <> struct TsClass<0> { static constexpr int NTOP = TS_NTOP_SMALL, CAP = TS_NTOP_SMALL + TS_PASS; };
@@ -66,8 +64,8 @@ __device__ __forceinline__ void ts_compact(uint64_t *__restrict__ sc, int32_t *_
 
 // The workspace of csrk_topk_scores_for for n_rows output rows, S splits and n_top: three arrays over the slots
 // slot = output row * S + split, one after the other -- score bits [slots][n_top] (8 B), items [slots][n_top] (4 B),
-// counts [slots] (4 B): TSF_SLOT_BYTES + (n_top - 1) * TSF_NTOP_BYTES per slot, every array aligned to its element.
-constexpr int64_t TSF_SLOT_BYTES = 16, TSF_NTOP_BYTES = 12;
+// counts [slots] (4 B): TSF_SLOT_BYTES + (n_top - 1) * TSF_NTOP_BYTES per slot (score_plan.h, tsf_work_bytes), every array
+// aligned to its element.
 struct TsWork {
     uint64_t *sc;
     int32_t *it, *cnt;

@@ -6,13 +6,12 @@
 #pragma once
 #include "common.h"
 #include "device_loads.h"
+#include "score_plan.h"
 #include "topk_order.h"
 
 namespace csrk {
 
-constexpr int TS_THREADS = 256;
-constexpr int TS_ROWS = 64;                     // rows of U per workgroup
-constexpr int TS_TILE = 64;                     // items per tile
+// (TS_THREADS, TS_ROWS, TS_TILE: score_plan.h, with everything else the host side reads)
 constexpr int TS_B = 4;                         // register tile edge
 constexpr int TS_KC = 16;                       // factors per LDS chunk
 constexpr int TS_LD = TS_ROWS + 2;              // doubles per staged line

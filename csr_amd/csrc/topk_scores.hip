@@ -29,7 +29,7 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "panel.h"
+#include "score_host.h"
 #include "score_list.h"
 #include "score_tile.h"
 
@@ -191,10 +191,38 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_kernel(const void *__r
     if (counts && tid < nvalid) counts[r0 + tid] = s_cnt[tid];
 }
 
-// every refusal that needs no look at the pointers; with a handle, the caller holds no lock
-static int ts_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t n_items, int32_t k, int panel_type,
-                    int32_t n_top, double min_score, int64_t ldi, int64_t lds)
+// the kernel's arguments in its order (the grid follows from n)
+struct TsLaunch {
+    ScoreCsr seen;
+    int32_t row_begin, n;
+    const void *U;
+    int64_t ldu;
+    const void *V;
+    int64_t ldv;
+    int32_t n_items, k, n_top;
+    double min_score;
+    int select;
+    int32_t *items;
+    int64_t ldi;
+    double *scores;
+    int64_t lds;
+    int32_t *counts;
+    hipStream_t s;
+};
+
+template <class T, bool WIDE, int CLS> static void ts_launch(const TsLaunch &a)
 {
+    topk_scores_kernel<T, WIDE, CLS><<<(unsigned)score_row_blocks(a.n), TS_THREADS, 0, a.s>>>(
+        a.seen.rp, a.seen.ptr64, a.seen.ci, a.row_begin, a.n, (const T *)a.U, a.ldu, (const T *)a.V, a.ldv, a.n_items, a.k, a.n_top,
+        a.min_score, a.select, a.items, a.ldi, a.scores, a.lds, a.counts);
+}
+
+// the handle (seen may be 0), then every refusal that needs no look at the pointers; the caller holds no lock
+static int ts_check(csrk_handle_t seen, int32_t row_begin, int32_t row_end, int64_t ldu, int64_t ldv, int32_t n_items, int32_t k,
+                    int panel_type, int32_t n_top, double min_score, int64_t ldi, int64_t lds, Matrix **mp)
+{
+    Matrix *m;
+    CSRK_TRY(optional_handle(seen, &m));
     CSRK_CHECK_K("topk_scores: ", k);
     CSRK_REQUIRE(n_top >= 1, "topk_scores: n_top must be at least 1 (n_top=%d)", n_top);
     CSRK_REQUIRE(n_items >= 0, "topk_scores: n_items must not be negative (n_items=%d)", n_items);
@@ -207,21 +235,19 @@ static int ts_check(Matrix *m, int32_t row_begin, int32_t row_end, int64_t ldu, 
     if (m) {
         CSRK_CHECK_ROW_RANGE("topk_scores: ", row_begin, row_end, m->nrows);
         CSRK_REQUIRE(n_items == m->ncols, "topk_scores: n_items=%d but seen has %d columns", n_items, m->ncols);
-        std::lock_guard<std::mutex> lk(m->mu);
-        CSRK_TRY(look_at_rows(m));                                // (remembered: a device pass only the first time a handle is asked)
-        CSRK_REQUIRE(m->canonical == 1,
-                     "topk_scores: seen is not canonical: row %d is not strictly ascending in column (csrk_order_columns sorts, "
-                     "csrk_coalesce merges repeats)",
-                     m->noncanonical_row);
+        CSRK_TRY(check_seen_canonical("topk_scores", m));
     }
-    if (k > TS_K_MAX) {
-        set_error("csrk_topk_scores: k=%d is above the largest supported k=%d (csrk_topk_scores_limits)", k, TS_K_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
-    if (n_top > TS_NTOP_MAX) {
-        set_error("csrk_topk_scores: n_top=%d is above the largest supported n_top=%d (csrk_topk_scores_limits)", n_top, TS_NTOP_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
+    CSRK_TRY(check_supported(ts_k_supported(k), "csrk_topk_scores", "k", k, TS_K_MAX, "csrk_topk_scores_limits"));
+    CSRK_TRY(check_supported(ts_ntop_supported(n_top), "csrk_topk_scores", "n_top", n_top, TS_NTOP_MAX, "csrk_topk_scores_limits"));
+    *mp = m;
+    return CSRK_OK;
+}
+
+static int ts_nulls(const void *items, const void *scores, const void *U, const void *V, int32_t n_items)
+{
+    CSRK_REQUIRE(items && scores, "topk_scores: items or scores is NULL");
+    CSRK_REQUIRE(U, "topk_scores: U is NULL");
+    CSRK_REQUIRE(V || n_items == 0, "topk_scores: V is NULL");
     return CSRK_OK;
 }
 
@@ -231,37 +257,20 @@ static int ts_device(Matrix *m, int32_t row_begin, int32_t row_end, const void *
                      double *dscores, int64_t lds, int32_t *dcounts, hipStream_t s)
 {
     if (row_begin == row_end) return CSRK_OK;
-    CSRK_REQUIRE(ditems && dscores, "topk_scores: items or scores is NULL");
-    CSRK_REQUIRE(dU, "topk_scores: U is NULL");
-    CSRK_REQUIRE(dV || n_items == 0, "topk_scores: V is NULL");
+    CSRK_TRY(ts_nulls(ditems, dscores, dU, dV, n_items));
     const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 &&
                      ((uintptr_t)ditems % 4) == 0 && ((uintptr_t)dcounts % 4) == 0,
                  "topk_scores: U, V, items, scores or counts is not aligned to its element size");
     mark_user_stream(m, s);
-    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
-    const char *env = getenv("CSRK_TOPK_SCORES_SELECT");          // diagnostic: "0" times the product alone (the outputs are not written)
-    const int select = !(env && env[0] == '0' && !env[1]);
-    const int32_t n = row_end - row_begin;
-    const unsigned grid = (unsigned)ceil_div((int64_t)n, TS_ROWS);
-#define TS_GO(T, W, CLS)                                                                                                          \
-    topk_scores_kernel<T, W, CLS><<<grid, TS_THREADS, 0, s>>>(m ? m->d_rowptrs : nullptr, m ? m->ptr64 : 0, m ? m->d_colinds : nullptr, \
-                                                               row_begin, n, (const T *)dU, ldu, (const T *)dV, ldv, n_items, k, n_top, \
-                                                               min_score, select, ditems, ldi, dscores, lds, dcounts)
-#define TS_CLS(T, W)                                                                                                              \
-    do {                                                                                                                         \
-        if (n_top <= TS_NTOP_SMALL) TS_GO(T, W, 0);                                                                              \
-        else TS_GO(T, W, 1);                                                                                                     \
-    } while (0)
-    if (panel_type == CSRK_VAL_F64) {
-        if (wide) TS_CLS(double, true);
-        else TS_CLS(double, false);
-    } else {
-        if (wide) TS_CLS(float, true);
-        else TS_CLS(float, false);
-    }
-#undef TS_CLS
-#undef TS_GO
+    const int select = score_knob_on(getenv("CSRK_TOPK_SCORES_SELECT"));      // diagnostic: "0" times the product alone (the outputs are not written)
+    const TsLaunch L{score_csr(m), row_begin, row_end - row_begin, dU, ldu, dV, ldv, n_items, k, n_top, min_score, select, ditems, ldi,
+                     dscores, lds, dcounts, s};
+    score_for_panel(panel_type, panels_wide(dU, ldu, dV, ldv, k, es), [&](auto t, auto w) {
+        using T = typename decltype(t)::type;
+        if (ts_small_class(n_top)) ts_launch<T, decltype(w)::value, 0>(L);
+        else ts_launch<T, decltype(w)::value, 1>(L);
+    });
     CSRK_LAUNCH_CHECK();
     return CSRK_OK;
 }
@@ -284,12 +293,8 @@ int csrk_topk_scores_device(csrk_handle_t seen, int32_t row_begin, int32_t row_e
                             int64_t ldv, int32_t n_items, int32_t k, int panel_type, int32_t n_top, double min_score, int32_t *d_items,
                             int64_t ldi, double *d_scores, int64_t lds, int32_t *d_counts, void *stream)
 {
-    Matrix *m = nullptr;
-    if (seen) {
-        m = from_handle(seen);
-        if (!m) return CSRK_ERR_INVALID;
-    }
-    CSRK_TRY(ts_check(m, row_begin, row_end, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds));
+    Matrix *m;
+    CSRK_TRY(ts_check(seen, row_begin, row_end, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, &m));
     const void *u0 = panel_rows_from(d_U, row_begin, ldu, panel_es(panel_type));
     return ts_device(m, row_begin, row_end, u0, ldu, d_V, ldv, n_items, k, panel_type, n_top, min_score, d_items, ldi, d_scores, lds,
                      d_counts, (hipStream_t)stream);
@@ -299,19 +304,12 @@ int csrk_topk_scores(csrk_handle_t seen, int32_t row_begin, int32_t row_end, con
                      int32_t n_items, int32_t k, int panel_type, int32_t n_top, double min_score, int32_t *items, int64_t ldi,
                      double *scores, int64_t lds, int32_t *counts)
 {
-    Matrix *m = nullptr;
-    if (seen) {
-        m = from_handle(seen);
-        if (!m) return CSRK_ERR_INVALID;
-    }
+    Matrix *m;
     // argument checks first, with the caller's pointers (the device call below sees packed copies)
-    CSRK_TRY(ts_check(m, row_begin, row_end, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds));
+    CSRK_TRY(ts_check(seen, row_begin, row_end, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, &m));
     if (row_begin == row_end) return CSRK_OK;
-    CSRK_REQUIRE(items && scores, "topk_scores: items or scores is NULL");
-    CSRK_REQUIRE(U, "topk_scores: U is NULL");
-    CSRK_REQUIRE(V || n_items == 0, "topk_scores: V is NULL");
-    const size_t es = panel_es(panel_type);
-    const size_t n = (size_t)(row_end - row_begin);
+    CSRK_TRY(ts_nulls(items, scores, U, V, n_items));
+    const size_t es = panel_es(panel_type), n = (size_t)(row_end - row_begin);
     int dev = 0;
     CSRK_HIP(hipGetDevice(&dev));                                           // (without a handle nothing vouches for a device)
     DevBuf dU, dV, dI, dS, dC;

@@ -12,23 +12,14 @@
 //           of entries that come before it there: a binary search each.  Places below n_top are written, the rest of the
 //           row is padding.  Places are counted, nothing is appended in arrival order; there is no atomic at all.
 // No workgroup waits for another, and neither kernel has a loop without a bound.
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
 #include "common.h"
-#include "panel.h"
+#include "score_host.h"
 #include "score_list.h"
 #include "score_tile.h"
 
 namespace csrk {
 
-constexpr int TSF_S_MAX = 64;                   // most splits: the merge looks at no more than 64 x 128 candidates per row
-constexpr int TSF_W_SMALL = 512;                // workgroups that fill the card: two per CU for n_top <= 32 (256 CUs) ...
-constexpr int TSF_W_LARGE = 256;                // ... one per CU above that (topk_scores.hip, the two list classes)
-constexpr int TSF_MERGE_THREADS = 256;
-constexpr int64_t TSF_GRID_MAX = 0x7fffffffll;
-
+// (the constants TSF_*, the split rule and the item interval of a split: score_plan.h)
 template <class T, bool WIDE, int CLS>
 __global__ __launch_bounds__(TS_THREADS) void topk_scores_for_kernel(const void *__restrict__ rp, int ptr64, const int32_t *__restrict__ ci,
                                                                     const int32_t *__restrict__ rows, int64_t n_rows, int32_t u_rows,
@@ -39,10 +30,9 @@ __global__ __launch_bounds__(TS_THREADS) void topk_scores_for_kernel(const void 
                                                                     int32_t *__restrict__ counts, void *__restrict__ work, int n_splits)
 {
     const int split = blockIdx.y;
-    const int64_t tiles = ((int64_t)n_items + TS_TILE - 1) / TS_TILE;
-    const int64_t j_begin = split * tiles / n_splits * TS_TILE, j_to = (split + 1) * tiles / n_splits * TS_TILE;
-    ts_sweep<T, WIDE, CLS>(rp, ptr64, ci, n_rows, rows, u_rows, u_packed, U, ldu, V, ldv, j_begin, j_to < n_items ? j_to : n_items, k, n_top,
-                           min_score, items, ldi, scores, lds, counts, work, split, n_splits);
+    const ScoreItemRange j = score_item_range(split, n_splits, n_items);
+    ts_sweep<T, WIDE, CLS>(rp, ptr64, ci, n_rows, rows, u_rows, u_packed, U, ldu, V, ldv, j.j_begin, j.j_end, k, n_top, min_score, items,
+                           ldi, scores, lds, counts, work, split, n_splits);
 }
 
 __global__ __launch_bounds__(TSF_MERGE_THREADS) void topk_scores_for_merge_kernel(const int32_t *__restrict__ rows, int64_t n_rows,
@@ -95,42 +85,56 @@ __global__ __launch_bounds__(TSF_MERGE_THREADS) void topk_scores_for_merge_kerne
     }
 }
 
-// rule 4: the splits in use and the bytes of the workspace, from the constants alone
-static int tsf_plan(int64_t n_rows, int32_t n_items, int32_t n_top, int32_t splits, int32_t *splits_used, int64_t *bytes)
+// the sweep's arguments in its order (the grid: row blocks x S)
+struct TsfLaunch {
+    ScoreCsr seen;
+    const int32_t *rows;
+    int64_t n_rows;
+    int32_t u_rows;
+    int u_packed;
+    const void *U;
+    int64_t ldu;
+    const void *V;
+    int64_t ldv;
+    int32_t n_items, k, n_top;
+    double min_score;
+    int32_t *items;
+    int64_t ldi;
+    double *scores;
+    int64_t lds;
+    int32_t *counts;
+    void *work;
+    int S;
+    hipStream_t s;
+};
+
+template <class T, bool WIDE, int CLS> static void tsf_launch(const TsfLaunch &a)
 {
-    const int64_t tiles = ceil_div((int64_t)n_items, TS_TILE), blocks = ceil_div(n_rows, TS_ROWS);
-    const int64_t most = tiles < TSF_S_MAX ? tiles : TSF_S_MAX;
-    int64_t s = 1;
-    if (tiles > 0 && blocks > 0) {
-        s = splits >= 1 ? splits : ceil_div(n_top <= TS_NTOP_SMALL ? TSF_W_SMALL : TSF_W_LARGE, blocks);
-        s = s > most ? most : s;
-    }
-    *splits_used = (int32_t)s;
-    *bytes = s == 1 ? 0 : ceil_div(n_rows * s * (TSF_SLOT_BYTES + (n_top - 1) * TSF_NTOP_BYTES), 16) * 16;
-    return CSRK_OK;
+    const dim3 grid((unsigned)score_row_blocks(a.n_rows), (unsigned)a.S);
+    topk_scores_for_kernel<T, WIDE, CLS><<<grid, TS_THREADS, 0, a.s>>>(a.seen.rp, a.seen.ptr64, a.seen.ci, a.rows, a.n_rows, a.u_rows,
+                                                                       a.u_packed, (const T *)a.U, a.ldu, (const T *)a.V, a.ldv, a.n_items,
+                                                                       a.k, a.n_top, a.min_score, a.items, a.ldi, a.scores, a.lds, a.counts,
+                                                                       a.work, a.S);
 }
 
 static int tsf_unsupported(int64_t n_rows, int32_t k, int32_t n_top)
 {
-    if (k > TS_K_MAX) {
-        set_error("topk_scores_for: k=%d is above the largest supported k=%d (csrk_topk_scores_limits)", k, TS_K_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
-    if (n_top > TS_NTOP_MAX) {
-        set_error("topk_scores_for: n_top=%d is above the largest supported n_top=%d (csrk_topk_scores_limits)", n_top, TS_NTOP_MAX);
-        return CSRK_ERR_UNSUPPORTED;
-    }
-    if (ceil_div(n_rows, TS_ROWS) > TSF_GRID_MAX) {
+    CSRK_TRY(check_supported(ts_k_supported(k), "topk_scores_for", "k", k, TS_K_MAX, "csrk_topk_scores_limits"));
+    CSRK_TRY(check_supported(ts_ntop_supported(n_top), "topk_scores_for", "n_top", n_top, TS_NTOP_MAX, "csrk_topk_scores_limits"));
+    if (tsf_grid_too_large(n_rows)) {
         set_error("topk_scores_for: n_rows=%lld makes more row blocks than a grid holds (%lld)", (long long)n_rows, (long long)TSF_GRID_MAX);
         return CSRK_ERR_UNSUPPORTED;
     }
     return CSRK_OK;
 }
 
-// every refusal that needs no look at the pointers, in csrk_topk_scores' order; with a handle, the caller holds no lock
-static int tsf_check(Matrix *m, int64_t n_rows, int32_t u_rows, int64_t ldu, int64_t ldv, int32_t n_items, int32_t k, int panel_type,
-                     int32_t n_top, double min_score, int64_t ldi, int64_t lds, int32_t splits)
+// the handle (seen may be 0), then every refusal that needs no look at the pointers, in csrk_topk_scores' order; the caller
+// holds no lock
+static int tsf_check(csrk_handle_t seen, int64_t n_rows, int32_t u_rows, int64_t ldu, int64_t ldv, int32_t n_items, int32_t k,
+                     int panel_type, int32_t n_top, double min_score, int64_t ldi, int64_t lds, int32_t splits, Matrix **mp)
 {
+    Matrix *m;
+    CSRK_TRY(optional_handle(seen, &m));
     CSRK_CHECK_K("topk_scores_for: ", k);
     CSRK_REQUIRE(n_top >= 1, "topk_scores_for: n_top must be at least 1 (n_top=%d)", n_top);
     CSRK_REQUIRE(n_items >= 0, "topk_scores_for: n_items must not be negative (n_items=%d)", n_items);
@@ -145,14 +149,30 @@ static int tsf_check(Matrix *m, int64_t n_rows, int32_t u_rows, int64_t ldu, int
     if (m) {
         CSRK_REQUIRE(u_rows == m->nrows, "topk_scores_for: u_rows=%d but seen has %d rows", u_rows, m->nrows);
         CSRK_REQUIRE(n_items == m->ncols, "topk_scores_for: n_items=%d but seen has %d columns", n_items, m->ncols);
-        std::lock_guard<std::mutex> lk(m->mu);
-        CSRK_TRY(look_at_rows(m));                                // (remembered: a device pass only the first time a handle is asked)
-        CSRK_REQUIRE(m->canonical == 1,
-                     "topk_scores_for: seen is not canonical: row %d is not strictly ascending in column (csrk_order_columns sorts, "
-                     "csrk_coalesce merges repeats)",
-                     m->noncanonical_row);
+        CSRK_TRY(check_seen_canonical("topk_scores_for", m));
     }
+    *mp = m;
     return tsf_unsupported(n_rows, k, n_top);
+}
+
+static int tsf_nulls(const void *items, const void *scores, const void *rows, const void *U, const void *V, int32_t n_items)
+{
+    CSRK_REQUIRE(items && scores, "topk_scores_for: items or scores is NULL");
+    CSRK_REQUIRE(rows, "topk_scores_for: rows is NULL");
+    CSRK_REQUIRE(U, "topk_scores_for: U is NULL");
+    CSRK_REQUIRE(V || n_items == 0, "topk_scores_for: V is NULL");
+    return CSRK_OK;
+}
+
+// S > 1: the caller's workspace holds the partial lists
+static int tsf_check_workspace(const void *dwork, int64_t work_bytes, int64_t need, int32_t S)
+{
+    if (need == 0) return CSRK_OK;
+    CSRK_REQUIRE(dwork, "topk_scores_for: the workspace is NULL but %lld bytes are needed (splits_used=%d)", (long long)need, S);
+    CSRK_REQUIRE(((uintptr_t)dwork % 16) == 0, "topk_scores_for: the workspace is not aligned to 16 bytes");
+    CSRK_REQUIRE(work_bytes >= need, "topk_scores_for: work_bytes=%lld but %lld bytes are needed (splits_used=%d)", (long long)work_bytes,
+                 (long long)need, S);
+    return CSRK_OK;
 }
 
 // u_packed: dU holds the listed rows only, in list order (the host form); drows names rows of `seen` either way
@@ -162,50 +182,25 @@ static int tsf_device(Matrix *m, const int32_t *drows, int64_t n_rows, int32_t u
                       int64_t work_bytes, hipStream_t s)
 {
     if (n_rows == 0) return CSRK_OK;
-    CSRK_REQUIRE(ditems && dscores, "topk_scores_for: items or scores is NULL");
-    CSRK_REQUIRE(drows, "topk_scores_for: rows is NULL");
-    CSRK_REQUIRE(dU, "topk_scores_for: U is NULL");
-    CSRK_REQUIRE(dV || n_items == 0, "topk_scores_for: V is NULL");
+    CSRK_TRY(tsf_nulls(ditems, dscores, drows, dU, dV, n_items));
     const size_t es = panel_es(panel_type);
     CSRK_REQUIRE(((uintptr_t)dU % es) == 0 && ((uintptr_t)dV % es) == 0 && ((uintptr_t)dscores % 8) == 0 &&
                      ((uintptr_t)ditems % 4) == 0 && ((uintptr_t)dcounts % 4) == 0 && ((uintptr_t)drows % 4) == 0,
                  "topk_scores_for: rows, U, V, items, scores or counts is not aligned to its element size");
-    int32_t S = 1;
-    int64_t need = 0;
-    CSRK_TRY(tsf_plan(n_rows, n_items, n_top, splits, &S, &need));
-    if (need > 0) {
-        CSRK_REQUIRE(dwork, "topk_scores_for: the workspace is NULL but %lld bytes are needed (splits_used=%d)", (long long)need, S);
-        CSRK_REQUIRE(((uintptr_t)dwork % 16) == 0, "topk_scores_for: the workspace is not aligned to 16 bytes");
-        CSRK_REQUIRE(work_bytes >= need, "topk_scores_for: work_bytes=%lld but %lld bytes are needed (splits_used=%d)", (long long)work_bytes,
-                     (long long)need, S);
-    }
+    const int32_t S = tsf_splits(n_rows, n_items, n_top, splits);
+    CSRK_TRY(tsf_check_workspace(dwork, work_bytes, tsf_work_bytes(n_rows, S, n_top), S));
     mark_user_stream(m, s);
-    const bool wide = panel_16b(dU, ldu, es) && panel_16b(dV, ldv, es) && k % panel_per16(es) == 0;
-    const dim3 grid((unsigned)ceil_div(n_rows, TS_ROWS), (unsigned)S);
-    void *work = S > 1 ? dwork : nullptr;
-#define TSF_GO(T, W, CLS)                                                                                                         \
-    topk_scores_for_kernel<T, W, CLS><<<grid, TS_THREADS, 0, s>>>(m ? m->d_rowptrs : nullptr, m ? m->ptr64 : 0, m ? m->d_colinds : nullptr, \
-                                                                   drows, n_rows, u_rows, u_packed, (const T *)dU, ldu, (const T *)dV, ldv, \
-                                                                   n_items, k, n_top, min_score, ditems, ldi, dscores, lds, dcounts, work, S)
-#define TSF_CLS(T, W)                                                                                                             \
-    do {                                                                                                                         \
-        if (n_top <= TS_NTOP_SMALL) TSF_GO(T, W, 0);                                                                             \
-        else TSF_GO(T, W, 1);                                                                                                    \
-    } while (0)
-    if (panel_type == CSRK_VAL_F64) {
-        if (wide) TSF_CLS(double, true);
-        else TSF_CLS(double, false);
-    } else {
-        if (wide) TSF_CLS(float, true);
-        else TSF_CLS(float, false);
-    }
-#undef TSF_CLS
-#undef TSF_GO
+    const TsfLaunch L{score_csr(m), drows, n_rows, u_rows, u_packed, dU, ldu, dV, ldv, n_items, k, n_top, min_score, ditems, ldi,
+                      dscores, lds, dcounts, S > 1 ? dwork : nullptr, S, s};
+    score_for_panel(panel_type, panels_wide(dU, ldu, dV, ldv, k, es), [&](auto t, auto w) {
+        using T = typename decltype(t)::type;
+        if (ts_small_class(n_top)) tsf_launch<T, decltype(w)::value, 0>(L);
+        else tsf_launch<T, decltype(w)::value, 1>(L);
+    });
     CSRK_LAUNCH_CHECK();
     if (S > 1) {
-        const int64_t blocks = ceil_div(n_rows, TSF_MERGE_THREADS / WAVE);
-        topk_scores_for_merge_kernel<<<(unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)), TSF_MERGE_THREADS, 0, s>>>(
-            drows, n_rows, u_rows, n_top, S, dwork, ditems, ldi, dscores, lds, dcounts);
+        topk_scores_for_merge_kernel<<<(unsigned)tsf_merge_grid(n_rows), TSF_MERGE_THREADS, 0, s>>>(drows, n_rows, u_rows, n_top, S, dwork,
+                                                                                                  ditems, ldi, dscores, lds, dcounts);
         CSRK_LAUNCH_CHECK();
     }
     return CSRK_OK;
@@ -233,7 +228,9 @@ int csrk_topk_scores_for_workspace(int64_t n_rows, int32_t n_items, int32_t n_to
     CSRK_REQUIRE(n_rows >= 0, "topk_scores_for: n_rows must not be negative (n_rows=%lld)", (long long)n_rows);
     CSRK_REQUIRE(splits >= 0, "topk_scores_for: splits must not be negative (splits=%d)", splits);
     CSRK_TRY(tsf_unsupported(n_rows, 1, n_top));
-    return tsf_plan(n_rows, n_items, n_top, splits, splits_used, bytes);
+    *splits_used = tsf_splits(n_rows, n_items, n_top, splits);
+    *bytes = tsf_work_bytes(n_rows, *splits_used, n_top);
+    return CSRK_OK;
 }
 
 int csrk_topk_scores_for_device(csrk_handle_t seen, const int32_t *d_rows, int64_t n_rows, int32_t u_rows, const void *d_U, int64_t ldu,
@@ -241,12 +238,8 @@ int csrk_topk_scores_for_device(csrk_handle_t seen, const int32_t *d_rows, int64
                                 int32_t *d_items, int64_t ldi, double *d_scores, int64_t lds, int32_t *d_counts, int32_t splits, void *d_work,
                                 int64_t work_bytes, void *stream)
 {
-    Matrix *m = nullptr;
-    if (seen) {
-        m = from_handle(seen);
-        if (!m) return CSRK_ERR_INVALID;
-    }
-    CSRK_TRY(tsf_check(m, n_rows, u_rows, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, splits));
+    Matrix *m;
+    CSRK_TRY(tsf_check(seen, n_rows, u_rows, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, splits, &m));
     return tsf_device(m, d_rows, n_rows, u_rows, 0, d_U, ldu, d_V, ldv, n_items, k, panel_type, n_top, min_score, d_items, ldi, d_scores, lds,
                       d_counts, splits, d_work, work_bytes, (hipStream_t)stream);
 }
@@ -255,32 +248,20 @@ int csrk_topk_scores_for(csrk_handle_t seen, const int32_t *rows, int64_t n_rows
                          int64_t ldv, int32_t n_items, int32_t k, int panel_type, int32_t n_top, double min_score, int32_t *items,
                          int64_t ldi, double *scores, int64_t lds, int32_t *counts, int32_t splits)
 {
-    Matrix *m = nullptr;
-    if (seen) {
-        m = from_handle(seen);
-        if (!m) return CSRK_ERR_INVALID;
-    }
+    Matrix *m;
     // argument checks first, with the caller's pointers (the device call below sees packed copies)
-    CSRK_TRY(tsf_check(m, n_rows, u_rows, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, splits));
+    CSRK_TRY(tsf_check(seen, n_rows, u_rows, ldu, ldv, n_items, k, panel_type, n_top, min_score, ldi, lds, splits, &m));
     if (n_rows == 0) return CSRK_OK;
-    CSRK_REQUIRE(items && scores, "topk_scores_for: items or scores is NULL");
-    CSRK_REQUIRE(rows, "topk_scores_for: rows is NULL");
-    CSRK_REQUIRE(U, "topk_scores_for: U is NULL");
-    CSRK_REQUIRE(V || n_items == 0, "topk_scores_for: V is NULL");
-    for (int64_t r = 0; r < n_rows; r++)                          // the list is looked at before anything is sent
-        CSRK_REQUIRE(rows[r] >= 0 && rows[r] < u_rows, "topk_scores_for: rows[%lld]=%d is outside [0, %d)", (long long)r, rows[r], u_rows);
-    const size_t es = panel_es(panel_type), n = (size_t)n_rows, line = (size_t)k * es;
-    std::vector<char> picked(n * line);                           // the listed rows of U only, in list order
-    for (size_t r = 0; r < n; r++) memcpy(picked.data() + r * line, (const char *)U + (size_t)rows[r] * (size_t)ldu * es, line);
-    int32_t S = 1;
-    int64_t need = 0;
-    CSRK_TRY(tsf_plan(n_rows, n_items, n_top, splits, &S, &need));
+    CSRK_TRY(tsf_nulls(items, scores, rows, U, V, n_items));
+    CSRK_TRY(check_listed_rows("topk_scores_for", rows, n_rows, u_rows));
+    const size_t es = panel_es(panel_type), n = (size_t)n_rows;
+    const int64_t need = tsf_work_bytes(n_rows, tsf_splits(n_rows, n_items, n_top, splits), n_top);
     int dev = 0;
     CSRK_HIP(hipGetDevice(&dev));                                           // (without a handle nothing vouches for a device)
     DevBuf dR, dU, dV, dI, dS, dC, dW;
     CSRK_TRY(dR.alloc(n * 4));
     CSRK_HIP(hipMemcpy(dR.p, rows, n * 4, hipMemcpyHostToDevice));
-    CSRK_TRY(pack_panel(dU, picked.data(), k, k, es, n));
+    CSRK_TRY(pack_listed_rows(dU, U, ldu, k, es, rows, n));
     CSRK_TRY(pack_panel(dV, V, ldv, k, es, n_items));
     CSRK_TRY(dI.alloc(n * n_top * 4));
     CSRK_TRY(dS.alloc(n * n_top * 8));

@@ -1224,6 +1224,19 @@ def _splits(splits):
     return min(int(splits), np.iinfo('i4').max)
 
 
+def _row_list(users, nrows):
+    "users as a contiguous int32 list of row indices in [0, nrows): 1-D, integers, any order, repeats allowed; else ValueError"
+    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
+    if users.ndim != 1:
+        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
+    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
+        raise ValueError(f'users must hold integers, not {users.dtype}')
+    bad = np.flatnonzero((users < 0) | (users >= nrows))
+    if len(bad):
+        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
+    return np.ascontiguousarray(users, dtype=np.int32)
+
+
 def topk_scores_for_workspace(n_rows, n_items, n, splits=None):
     """
     (splits_used, bytes): into how many ranges topk_scores_for cuts the items for n_rows listed rows, n_items items and
@@ -1248,15 +1261,8 @@ def topk_scores_for_args(h, users, U, V, n, min_score=None, splits=None):
     order, repeats allowed; no library call is made.
     """
     U, ldu, V, ldv, n_items, k, code, n, ms, _, nrows = topk_scores_args(h, U, V, n, min_score, None)
-    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
-    if users.ndim != 1:
-        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
-    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
-        raise ValueError(f'users must hold integers, not {users.dtype}')
-    bad = np.flatnonzero((users < 0) | (users >= nrows))
-    if len(bad):
-        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
-    return np.ascontiguousarray(users, dtype=np.int32), U, ldu, V, ldv, n_items, k, code, n, ms, _splits(splits), nrows
+    users = _row_list(users, nrows)
+    return users, U, ldu, V, ldv, n_items, k, code, n, ms, _splits(splits), nrows
 
 
 def topk_scores_for(h, users, U, V, n, min_score=None, splits=None):
@@ -1355,15 +1361,8 @@ def rank_entries_for_args(seen_h, test_h, users, U, V, splits=None):
     order, repeats allowed; no library call is made.
     """
     U, ldu, V, ldv, k, code, _, nrows = rank_entries_args(seen_h, test_h, U, V, None)
-    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
-    if users.ndim != 1:
-        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
-    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
-        raise ValueError(f'users must hold integers, not {users.dtype}')
-    bad = np.flatnonzero((users < 0) | (users >= nrows))
-    if len(bad):
-        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
-    return np.ascontiguousarray(users, dtype=np.int32), U, ldu, V, ldv, k, code, _splits(splits), nrows
+    users = _row_list(users, nrows)
+    return users, U, ldu, V, ldv, k, code, _splits(splits), nrows
 
 
 def rank_entries_for(seen_h, test_h, users, U, V, splits=None):
@@ -1419,15 +1418,7 @@ def knn_scores_args(model, ratings, users, max_nbrs=0, min_nbrs=1, aggregate='we
         raise ValueError(f'min_nbrs must be an integer that is at least 1, not {min_nbrs!r}')
     if int(model.ncols) != int(ratings.ncols):
         raise ValueError(f'model is {model.nrows} x {model.ncols} but ratings is {ratings.nrows} x {ratings.ncols}: the columns differ')
-    users = np.asarray(users, np.int32) if isinstance(users, (list, tuple)) and len(users) == 0 else np.asarray(users)
-    if users.ndim != 1:
-        raise ValueError(f'users must be 1-D, not of shape {users.shape}')
-    if users.dtype == np.bool_ or not np.issubdtype(users.dtype, np.integer):
-        raise ValueError(f'users must hold integers, not {users.dtype}')
-    nrows = int(ratings.nrows)
-    bad = np.flatnonzero((users < 0) | (users >= nrows))
-    if len(bad):
-        raise ValueError(f'users[{int(bad[0])}] = {int(users[bad[0]])} is outside [0, {nrows})')
+    users = _row_list(users, int(ratings.nrows))
     if offsets is not None:
         offsets = np.asarray(offsets)
         if offsets.dtype == np.bool_ or not (np.issubdtype(offsets.dtype, np.floating) or np.issubdtype(offsets.dtype, np.integer)):
@@ -1436,7 +1427,7 @@ def knn_scores_args(model, ratings, users, max_nbrs=0, min_nbrs=1, aggregate='we
             raise ValueError(f'offsets must hold one number per user ({len(users)}), not shape {offsets.shape}')
         offsets = np.ascontiguousarray(offsets, dtype=np.float64)
     i4 = np.iinfo('i4').max
-    return np.ascontiguousarray(users, dtype=np.int32), min(int(max_nbrs), i4), min(int(min_nbrs), i4), _KNN_AGGREGATES[aggregate], offsets
+    return users, min(int(max_nbrs), i4), min(int(min_nbrs), i4), _KNN_AGGREGATES[aggregate], offsets
 
 
 _KNN_ROUTES = ('walk', 'reach')

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import rank_entries_ref as R
+import score_rules as RULES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('csrk_rank_entries_for', 'csrk_rank_entries_for_device', 'csrk_rank_entries_for_splits', 'csrk_rank_entries_for_limits')
@@ -49,30 +50,18 @@ def test_limits_need_no_device():
     assert lib.csrk_rank_entries_for_limits(two, 1) == 0 and two[0] == lim[0] and two[1] == -1
 
 
-def _rule11(n_rows, n_items, splits, s_max, W, block, tile):
-    "rule 11, restated"
-    T = -(-n_items // tile)
-    if T == 0 or n_rows == 0:
-        return 1
-    if splits is not None:
-        return min(splits, T, s_max)
-    return max(1, min(-(-W // -(-n_rows // block)), T, s_max))
-
-
 def test_splits_follow_rule_11():
+    "(the restatement of rule 11 and the grid of requests: tests/score_rules.py, shared with test_score_plan_host.py)"
     from csr_amd.kernels import hip as K
     (s_max, W), rlim = K.rank_entries_for_limits(), K.rank_entries_limits()
     block, tile = rlim[1], rlim[2]
     assert (block, tile) == (64, 64)
     seen = set()
-    for n_rows in (0, 1, 64, 65, 64 * W, 64 * W + 1, 1024, 65536):
-        for T in (0, 1, s_max, s_max + 1):
-            for n_items in sorted({T * tile, max(T * tile - tile + 1, 0)} if T else {0}):
-                for splits in (None, 1, 2, 3, 5, s_max, s_max + 1, T + 1, 1000):
-                    got = K.rank_entries_for_splits(n_rows, n_items, splits)
-                    assert got == _rule11(n_rows, n_items, splits, s_max, W, block, tile), (n_rows, n_items, splits, got)
-                    assert 1 <= got <= max(1, min(T, s_max))          # forced splits above T and above S_max are clamped
-                    seen.add(got)
+    for n_rows, n_items, splits, T in RULES.rule11_grid(s_max, W, tile):
+        got = K.rank_entries_for_splits(n_rows, n_items, splits)
+        assert got == RULES.rule11(n_rows, n_items, splits, s_max, W, block, tile), (n_rows, n_items, splits, got)
+        assert 1 <= got <= max(1, min(T, s_max))          # forced splits above T and above S_max are clamped
+        seen.add(got)
     assert {1, 2, 3, 5, s_max} <= seen
     # the cases the automatic choice is made for
     assert K.rank_entries_for_splits(1, 2_000_000) == 64 and K.rank_entries_for_splits(64, 2_000_000) == 64

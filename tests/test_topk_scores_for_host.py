@@ -11,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import score_rules as RULES
 import topk_scores_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,38 +47,21 @@ def test_limits_need_no_device():
     assert lib.csrk_topk_scores_for_limits(two, 1) == 0 and two[0] == lim[0] and two[1] == -1
 
 
-def _rule4(n_rows, n_items, n, splits, lim, tlim):
-    "rule 4 and the workspace size, restated"
-    s_max, w_small, w_large, slot, per = lim
-    block, tile = tlim[2], tlim[3]
-    T = -(-n_items // tile)
-    if T == 0 or n_rows == 0:
-        S = 1
-    elif splits is not None:
-        S = min(splits, T, s_max)
-    else:
-        W = w_small if n <= 32 else w_large
-        S = max(1, min(-(-W // -(-n_rows // block)), T, s_max))
-    nbytes = 0 if S == 1 else -(-(n_rows * S * (slot + per * (n - 1))) // 16) * 16
-    return S, nbytes
-
-
 def test_workspace_follows_rule_4():
+    "(the restatement of rule 4 and the grid of requests: tests/score_rules.py, shared with test_score_plan_host.py)"
     from csr_amd.kernels import hip as K
     lim, tlim = K.topk_scores_for_limits(), K.topk_scores_limits()
     s_max, tile = lim[0], tlim[3]
     seen = set()
-    for n in (1, 2, 20, 32, 33, 128):
+    for n in RULES.RULE4_NS:
         W = lim[1] if n <= 32 else lim[2]
-        for n_rows in (1, 64, 65, 1024, 64 * W, 64 * W - 64, 0):
-            for n_items in (0, 1, 64, 65, 261, 64 * (s_max + 1), 2_000_000):
-                for splits in (None, 1, 2, 3, 5, s_max, s_max + 1, 1000):
-                    got = K.topk_scores_for_workspace(n_rows, n_items, n, splits)
-                    assert got == _rule4(n_rows, n_items, n, splits, lim, tlim), (n_rows, n_items, n, splits, got)
-                    assert (got[1] == 0) == (got[0] == 1) and got[1] % 16 == 0
-                    T = -(-n_items // tile)
-                    assert 1 <= got[0] <= max(1, min(T, s_max))          # forced splits above T and above S_max are clamped
-                    seen.add(got[0])
+        for n_rows, n_items, splits in RULES.rule4_grid(n, lim):
+            got = K.topk_scores_for_workspace(n_rows, n_items, n, splits)
+            assert got == RULES.rule4(n_rows, n_items, n, splits, lim, tlim), (n_rows, n_items, n, splits, got)
+            assert (got[1] == 0) == (got[0] == 1) and got[1] % 16 == 0
+            T = -(-n_items // tile)
+            assert 1 <= got[0] <= max(1, min(T, s_max))          # forced splits above T and above S_max are clamped
+            seen.add(got[0])
         assert K.topk_scores_for_workspace(64 * W, 2_000_000, n)[0] == 1          # as many row blocks as fill the card: no split
         assert K.topk_scores_for_workspace(65536, 2_000_000, n)[0] == 1
     assert {1, 2, 3, 5, s_max} <= seen
